@@ -1,8 +1,21 @@
 #!/usr/bin/env python3
 """Throughput of PULPo's registration training step (forward + backward + gradient all-reduce + Adam) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the outputs if --dump-outputs is given, and prints the line: nothing is
+bracketed inside the timed region and nothing runs after it.  --full adds everything else the line can carry, as described below: the
+HIP-event brackets of the timed region (roofline, conv_kernels, time_split), the extra untimed steps (hbm_rooflines, roofline["serialized"],
+the other loops, the other determinism mode) and the CPU baseline.  --no-trace / --no-loops / --no-cpu-baseline leave parts of it out.
+
+--dump-outputs DIR: after the timed steps, what the timed call returned in its last step, as DIR/<name>.npy in float32 - for the training
+step the loss and, in model.parameters() order, the updated parameters and their gradients; for --mode infer / mc8 every tensor of the
+returned structure.  An array larger than its share of 64 MB is replaced by a fixed sample of its flattened elements (sorted indices drawn
+by torch.randperm from a generator seeded with 0, the same for every array of that length).  Rank 0 writes.  Model weights, inputs and
+noise are seeded, and the last timed training step starts from the seeded weights and a fresh optimizer (seeded_state below), so the
+same arguments give it the same inputs on every run and two builds can be compared output for output: two runs of one build differ by the
+rounding of the backward pass's float atomics (bit for bit with --deterministic).
 
 `--gpus N` with N > 1 and no torchrun environment (WORLD_SIZE unset): this process becomes a launcher.  Before anything touches the
 GPU it starts N fresh rank processes of this same script (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, rank r
@@ -10,7 +23,7 @@ pinned to GPU r), relays rank 0's single JSON line, and exits non-zero if any ra
 
 Workload (BASELINE.json `metric`): synthetic 160^3 fp32 volume pairs, 4-level latent pyramid (total_levels 5,
 latent_levels 4, n0 = 32), batch 1 per GPU, weak scaling over GPUs.  One "step" = one training step on one pair per
-GPU.  Inputs live in HBM before the timed region.  Rank 0 prints ONE JSON line (see the task contract) carrying
+GPU.  Inputs live in HBM before the timed region.  Rank 0 prints ONE JSON line (see the task contract) carrying, with --full,
   roofline      : the dominant kernel (the MFMA 3x3x3 convolution), algorithmic FLOP / launch over its HIP-event
                   measured mean launch time inside the timed region, against the dense fp32 MFMA peak (157.3 TFLOP/s);
   cpu_baseline  : the CPU oracle (oracle/pulpo_oracle.py, the same ATen op sequence as the reference) timed on this
@@ -75,20 +88,64 @@ def parse():
                          "train.py runs); plain-autograd = loss.backward() + torch.optim.Adam with every fast-path switch off (one GPU only)")
     ap.add_argument("--deterministic", action="store_true",
                     help="run the measured loop in deterministic mode (pulpo_amd.ops.set_deterministic: ordered sums instead of float atomics in the "
-                         "backward kernels; bit-identical gradients run to run).  Default: off; the line reports the mode's step time either way")
+                         "backward kernels; bit-identical gradients run to run).  Default: off; with --full the line reports the other mode's step time too")
     ap.add_argument("--graph", action="store_true",
                     help="stepper loop only: zero_grad + forward + backward + gradient finishing replayed from ONE HIP graph (dp.DataParallelStepper(graph=True)); "
                          "gradient exchange, fused Adam and weight re-pack stay eager.  For the short bf16 steps, which the host barely keeps ahead of")
-    ap.add_argument("--no-loops", action="store_true", help="do not time the other two loops after the measurement (one GPU, train mode)")
+    ap.add_argument("--no-loops", action="store_true", help="--full without timing the other two loops and the other determinism mode after the measurement")
     ap.add_argument("--host-input", action="store_true",
                     help="feed every step from host memory through pulpo_amd.prefetch.DevicePrefetcher (PCIe-inclusive rate; the default "
                          "keeps the pair resident in HBM as the metric prescribes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-trace", action="store_true", help="do not bracket conv launches with HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: HIP-event brackets in the timed region, the extra untimed trace / loop / determinism steps and "
+                         "the CPU baseline (default: the timed steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-trace", action="store_true", help="--full without the HIP-event brackets of conv launches")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="TEST HOOK, not a measurement: run only the launch / rendezvous / barrier / max-over-ranks / JSON plumbing with a trivial "
                          "CPU all-reduce as the 'step' (no kernels, no GPU); the line it prints carries \"valid\": false")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 64 << 20           # all files together
+DUMP_MAX_ELEMS = 1 << 21        # per array
+DUMP_SEED = 0
+
+
+def _tensors(obj, name: str, out: dict) -> dict:
+    """name -> tensor for every tensor of a nested dict / list / tuple (keys and positions joined with '_')"""
+    if torch.is_tensor(obj):
+        out[name] = obj
+    elif isinstance(obj, dict):
+        for k in obj:
+            _tensors(obj[k], f"{name}_{k}", out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _tensors(v, f"{name}_{i}", out)
+    return out
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """arrays: name -> tensor, written as path/<name>.npy in float32; an array larger than its share of DUMP_BYTES becomes a fixed sample
+    of its flattened elements (the same sorted indices for every array of that length)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = min(DUMP_MAX_ELEMS, DUMP_BYTES // 4 // max(1, len(arrays)))
+    index = {}
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > cap:
+            n = a.numel()
+            if n not in index:
+                index[n] = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))[:cap].sort().values
+            a = a.reshape(-1)[index[n].to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
 
 
 # ------------------------------------------------------------------------------------------------ self-launch (--gpus N without torchrun)
@@ -293,6 +350,35 @@ def pmc_traffic(kernel: str) -> dict:
                               "gathers by scripts/probes/fetch_calib.hip, profiles/r3_fetch_calibration.md)"}
 
 
+def seeded_state(model, stepper, run):
+    """-> restore(): puts the weights the model has now back in place and the optimizer back to its fresh state (zero moments, step 0).
+    Called once, right before the last timed step, so that the step --dump-outputs reports computes from the seeded weights, pair and noise
+    stream alone: the float atomics of the backward pass sum in a different order on every run, and carried from step to step through the
+    weights that rounding grows without bound (160^3: 1e-6 of the loss after one step, 1 % after 25).  The copy is timed with the step."""
+    from pulpo_amd import ops
+    if stepper is not None:
+        live, opt = stepper.arena.data, stepper.opt
+        saved = live.detach().clone()
+        assert opt.t == 0, "seeded_state() must be taken before the first step"
+
+        def restore():
+            live.data.copy_(saved)              # written behind torch's back, as the fused Adam update writes: the cached packs follow in one launch
+            opt.m.zero_()
+            opt.v.zero_()
+            opt.t = 0
+            ops.refresh_weight_packs()
+    else:
+        params = [p for p in model.parameters() if p.requires_grad]
+        saved = [p.detach().clone() for p in params]
+
+        def restore():
+            with torch.no_grad():
+                for p, s_ in zip(params, saved):
+                    p.copy_(s_)                 # (through torch: the version counters move and the packs are made afresh)
+            run.opt.state.clear()               # torch.optim.Adam starts a parameter without state at step 0 with zero moments
+    return restore
+
+
 def make_loop(kind: str, model, graph: bool = False):
     """-> (run(batch) -> loss, the dp.DataParallelStepper behind it or None, the name reported in the line's "loop" field)"""
     from pulpo_amd import dp
@@ -315,6 +401,7 @@ def make_loop(kind: str, model, graph: bool = False):
         loss.backward()
         opt.step()
         return loss.detach()
+    run.opt = opt
     return run, None, "plain-autograd"
 
 
@@ -359,6 +446,7 @@ def main():
     if args.graph and args.loop != "stepper":
         raise SystemExit("bench: --graph belongs to --loop stepper")
     run_step, stepper, loop_name = make_loop(args.loop, model, graph=args.graph)       # stepper: the dp.DataParallelStepper that owns arena / streams (None: plain autograd)
+    restore = None if args.mode != "train" else seeded_state(model, stepper, run_step)
     fallback = "relaunched" if os.environ.get("PULPO_BENCH_RELAUNCHED") == "1" else "none"
     from pulpo_amd import synthetic
     x, y = (synthetic.oasis_like_pair if args.data == "oasis" else synthetic.uniform_pair)(size, B, 1234 + rank, dev)
@@ -371,19 +459,25 @@ def main():
         torch.cuda.synchronize()
 
     infer = args.mode in ("infer", "mc8")
+    last = {}                   # --dump-outputs, inference modes: what the timed call returned in the latest step
+    keep = args.dump_outputs is not None
     if args.mode == "mc8":
         from pulpo_amd.uncertainty import mc_uncertainty
         model.eval()
 
         def one_step():
             res = mc_uncertainty(model, x[:1], y[:1], 8)
+            if keep:
+                last["mc8"] = res
             return res["output_std"][0].sum()
     elif infer:
         model.eval()
 
         def one_step():
             with torch.no_grad():
-                out, _ = model.predict_deterministic(x, y)
+                out, dfs = model.predict_deterministic(x, y)
+            if keep:
+                last["infer"] = (out, dfs)
             return out[0].sum()
     elif args.host_input:
         from pulpo_amd.prefetch import DevicePrefetcher
@@ -439,16 +533,19 @@ def main():
         one_step()
     barrier()
     graph_replay = bool(args.graph and stepper is not None and stepper._graph is not None)
-    if not args.no_trace and not graph_replay:
+    tracing = args.full and not args.no_trace
+    if tracing and not graph_replay:
         ops.CONV_TRACE = []
         ops.CONV_TRACE_STRIDE = 7        # one in seven conv launches of the timed region is bracketed (drawn at random: no fixed stride can lock onto a layer)
     ops.CONV_TRACE_STRIDE_USED = ops.CONV_TRACE_STRIDE
-    if stepper is not None and world > 1:
+    if args.full and stepper is not None and world > 1:
         stepper.exchange_events = []        # HIP events around the waits for the gradient exchange: what of it is NOT hidden under the backward pass
     host_enq = []                           # host time spent inside each step's enqueue (no synchronisation inside a step: the host runs ahead)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
         th = time.perf_counter()
+        if restore is not None and i == args.steps - 1:
+            restore()                       # the last timed step computes from the seeded state (seeded_state)
         loss = one_step()
         host_enq.append(time.perf_counter() - th)
     barrier()
@@ -456,7 +553,17 @@ def main():
     peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9     # (of the measured loop: the extra steps below - other loops, deterministic mode - allocate their own)
     trace, ops.CONV_TRACE = ops.CONV_TRACE, None
     trace_steps = args.steps
-    if graph_replay and not args.no_trace:
+    if keep and rank == 0:              # (before any extra step below changes the weights)
+        if infer:
+            arrays = _tensors(last, "out", {})
+        else:
+            params = [p for p in model.parameters() if p.requires_grad]
+            arrays = {"loss": loss.reshape(1),
+                      "params": torch.cat([p.detach().reshape(-1) for p in params]),
+                      "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])}
+        dump_outputs(args.dump_outputs, arrays)
+        last.clear()
+    if graph_replay and tracing:
         # the timed region replayed a HIP graph (no per-launch events): the dominant kernel's brackets come from two extra EAGER steps of the same
         # loop, every launch bracketed (the step falls back to its eager form while a trace is armed)
         ops.CONV_TRACE, ops.CONV_TRACE_STRIDE = [], 1
@@ -511,7 +618,7 @@ def main():
     # the other two loops on fresh models of the same seed, a few steps each (one GPU, train mode): what an unchanged train.py gets
     # ("lightning-hooks") and what it got before the hooks existed ("plain-autograd"), beside the measured loop
     loops_ms = None
-    if world == 1 and not infer and not args.no_loops and not args.host_input:
+    if args.full and world == 1 and not infer and not args.no_loops and not args.host_input:
         loops_ms = {loop_name: dt / args.steps * 1e3}
         n_ab = max(3, min(args.steps, 10))
         for other, name2 in (("stepper", "stepper"), ("lightning", "lightning-hooks"), ("plain-autograd", "plain-autograd")):
@@ -534,7 +641,7 @@ def main():
 
     # ... and the same loop in the other determinism mode (a few untimed-region steps): what the ordered sums cost
     det_ms = None
-    if world == 1 and not infer and not args.no_loops and not args.host_input:
+    if args.full and world == 1 and not infer and not args.no_loops and not args.host_input:
         ops.set_deterministic(not args.deterministic)
         for _ in range(2):
             one_step()
@@ -641,6 +748,7 @@ def main():
             "config": {"workload": f"{size[0]}x{size[1]}x{size[2]} synthetic pair, {L}-level pyramid (total_levels {T}), {prec_name}, batch {B} per GPU, "
                                    + ("eval-mode forward (mu path, no sampling)" if infer else "fwd+bwd+grad all-reduce+Adam"), "global_batch": world * B, "parallelism": f"dp{world}"},
             "loop": loop_name,
+            "full": bool(args.full),
             "deterministic": {"measured_in_deterministic_mode": bool(args.deterministic),
                               ("ms_per_step_atomic_mode" if args.deterministic else "ms_per_step_deterministic_mode"): det_ms,
                               "note": "deterministic mode (PULPO_DETERMINISTIC=1): weight-gradient partial sums through ordered per-split slabs, VecInt / warp "
@@ -670,7 +778,7 @@ def main():
                                      "alg_bytes_frac_of_8TBps": BYTES_ALG_PER_PAIR_160 * per_gpu / 8.0e12,
                                      "note": "whole step: SURVEY 8(d)'s 5.708 TFLOP (direct-convolution count) and 41.98 GB per pair over the step time; "
                                              "the first is an effective rate (Winograd kernels issue fewer FLOP), not a utilisation"}
-        if world == 1 and not args.no_cpu_baseline and not bf16 and not infer:
+        if args.full and world == 1 and not args.no_cpu_baseline and not bf16 and not infer:
             out["cpu_baseline"] = cpu_baseline(size, T, L, B)
         else:
             out["cpu_baseline"] = None

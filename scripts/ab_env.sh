@@ -2,6 +2,6 @@
 R=$1; S=$2; shift 2
 for i in $(seq 1 $R); do
   for cfg in "$@"; do
-    ( export $cfg; python bench.py --steps $S --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$cfg', round(d['ms_per_step'],3), round(d['roofline']['frac'],4))" )
+    ( export $cfg; python bench.py --steps $S --full --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$cfg', round(d['ms_per_step'],3), round(d['roofline']['frac'],4))" )
   done
 done

@@ -16,7 +16,7 @@ RUNS = [
 ]
 rows = []
 for name, extra in RUNS:
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "3", "--no-cpu-baseline", "--no-loops"] + extra, capture_output=True, text=True, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-loops"] + extra, capture_output=True, text=True, cwd=ROOT)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not line:
         rows.append(f"| {name} | failed: {r.stderr[-200:]!r} | | | | |")
@@ -27,7 +27,7 @@ for name, extra in RUNS:
     rows.append(f"| {name} | {d['value']:.2f} | {d['ms_per_step']:.2f} | {rf.get('kernel', '')} | {rf.get('frac', float('nan')):.3f} | {'' if ser is None else f'{ser:.3f}'} | {d.get('hbm_peak_allocated_GB', float('nan')):.1f} |")
     print(rows[-1], flush=True)
 with open(sys.argv[1], "w") as f:
-    f.write("# BASELINE configs on one MI355X (python bench.py --steps 16 --warmup 3 --no-cpu-baseline --no-loops + the options of the config)\n\n"
+    f.write("# BASELINE configs on one MI355X (python bench.py --steps 16 --warmup 3 --full --no-cpu-baseline --no-loops + the options of the config)\n\n"
             "`frac` = FLOP the dominant kernel issues on the matrix pipe over its live-bracketed time in the overlapped step, against the dense peak of its "
             "operand type (157.3 TFLOP/s fp32, 2500 bf16); `serialized` = the same bracket with the weight-gradient stream off.\n\n"
             "| config | pairs/s | ms/step | dominant kernel | roofline.frac | serialized.frac | HBM peak GB |\n|---|---|---|---|---|---|---|\n" + "\n".join(rows) + "\n")

@@ -2,11 +2,11 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
 # 1. headline bench (with cpu baseline) - the line the driver would produce
-python bench.py > $O/r5_bench_final.json 2> $O/r5_bench_final.err
+python bench.py --full > $O/r5_bench_final.json 2> $O/r5_bench_final.err
 # 2. kernel trace + stats of the same command r2 used
-rocprofv3 --kernel-trace --stats -d $O/p1 -o r5 --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-loops > $O/r5_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/p1 -o r5 --output-format csv -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-loops > $O/r5_under_rocprof.json 2>/dev/null
 F=$(find $O/p1 -name "*kernel_stats.csv" | head -1)
-python scripts/summarize_profile.py $F $O/r5_bench160_summary.md 12 "Round 5 - rocprofv3 --kernel-trace --stats of python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-loops (2 warm-up + 5 timed + 2 untimed steps with every memory-bound launch bracketed + 3 untimed serialized-trace steps)" > /dev/null
+python scripts/summarize_profile.py $F $O/r5_bench160_summary.md 12 "Round 5 - rocprofv3 --kernel-trace --stats of python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-loops (2 warm-up + 5 timed + 2 untimed steps with every memory-bound launch bracketed + 3 untimed serialized-trace steps)" > /dev/null
 cp $F $O/r5_bench160_kernel_stats.csv; rm -rf $O/p1
 # 3. timeline of the overlapped step (no event brackets, no serialized steps)
 rocprofv3 --kernel-trace -d $O/p2 -o r5t --output-format csv -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-trace --no-loops > /dev/null 2>&1

@@ -1184,7 +1184,7 @@ def test_bench_two_rank_rehearsal(tmp_path, loop):
     env = dict(os.environ, PULPO_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", _free_port(),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "32", "32", "32", "--levels", "3", "2",
-           "--no-cpu-baseline", "--loop", loop]
+           "--full", "--no-cpu-baseline", "--loop", loop]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1233,12 +1233,12 @@ def test_bench_self_launch_two_ranks_without_torchrun():
 
 
 def test_bench_json_contract_single_gpu():
-    """the one JSON line bench.py prints (driver contract): every required key, the roofline and cpu_baseline objects, and the
+    """the one JSON line bench.py --full prints (driver contract): every required key, the roofline and cpu_baseline objects, and the
     arithmetic value = pairs / time - on a small workload so that the CPU-baseline leg takes seconds"""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "32", "32", "32",
-                        "--levels", "3", "2"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--levels", "3", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -1263,6 +1263,59 @@ def test_bench_json_contract_single_gpu():
         assert k in cb, k
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1
     assert d["value"] > cb["value"]
+    assert d["full"] is True
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_its_outputs(tmp_path):
+    """a plain bench.py run (no --full) is the timed steps alone: no brackets, no extra steps, no CPU baseline in the line.  --dump-outputs
+    writes the last timed step's loss, updated parameters and gradients in float32.  That step starts from the seeded weights and a fresh
+    optimizer, so two runs with the same arguments write the same numbers: the loss bit for bit (the forward pass has no atomics), the
+    gradients to the rounding of the backward pass's float atomics, the parameters to Adam's first update of it - lr * g / (|g| + eps) turns
+    the rounding noise of a gradient that is zero in exact arithmetic (conv biases in front of a BatchNorm) into up to +-lr.  In deterministic
+    mode the files are identical.  --mode infer writes what predict_deterministic returned."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(out, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "32", "32", "32",
+                            "--levels", "3", "2", "--dump-outputs", str(tmp_path / out)] + list(extra), capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    def load(out):
+        names = sorted(os.listdir(tmp_path / out))
+        assert names == ["grads.npy", "loss.npy", "params.npy"], names
+        d = {n[:-4]: np.load(tmp_path / out / n) for n in names}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in d.values())
+        assert sum(a.nbytes for a in d.values()) <= 64 << 20
+        return d
+
+    d = run("a")
+    assert d["full"] is False and d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    assert d["unit"] == "volume-pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    for k in ("roofline", "cpu_baseline", "loops_ms_per_step", "hbm_rooflines", "time_split"):
+        assert d[k] is None, k
+    assert d["conv_kernels"] == {} and d["deterministic"]["ms_per_step_deterministic_mode"] is None
+    run("b")
+    a, b = load("a"), load("b")
+    assert np.array_equal(a["loss"], b["loss"])
+    g = np.abs(a["grads"]).max()
+    assert g > 0 and np.abs(a["grads"] - b["grads"]).max() <= 1e-5 * g
+    assert np.linalg.norm(a["grads"] - b["grads"]) <= 1e-5 * np.linalg.norm(a["grads"])
+    assert np.abs(a["params"] - b["params"]).max() <= 2.5e-4                     # 2 lr (lr = 1e-4) and float32 rounding
+    assert np.linalg.norm(a["params"] - b["params"]) <= 1e-3 * np.linalg.norm(a["params"])
+    run("d1", "--deterministic")
+    run("d2", "--deterministic")
+    d1, d2 = load("d1"), load("d2")
+    for k in d1:
+        assert np.array_equal(d1[k], d2[k]), k
+    run("c", "--mode", "infer")
+    inf = sorted(os.listdir(tmp_path / "c"))
+    assert inf and all(n.startswith("out_infer_") for n in inf), inf
+    assert all(np.load(tmp_path / "c" / n).dtype == np.float32 for n in inf)
 
 
 def test_training_resumes_bit_identically_from_a_checkpoint(api, tmp_path):

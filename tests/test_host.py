@@ -454,3 +454,37 @@ def test_bench_refuses_a_world_size_mismatch():
     """--gpus N under a torchrun environment of a different size is an error, not a silently different measurement"""
     r = _bench(["--gpus", "4", "--steps", "1", "--warmup", "0"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
+
+
+def test_bench_refuses_zero_timed_steps():
+    """--steps is the number of timed steps the line's ms_per_step divides by: fewer than one is an error"""
+    r = _bench(["--steps", "0", "--plumbing-only"], {})
+    assert r.returncode != 0 and "--steps" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")], r.stdout
+
+
+def test_bench_dump_outputs_writes_float32_within_budget(tmp_path):
+    """bench.dump_outputs: every array as <name>.npy in float32; one larger than its share of the 64 MB budget becomes the same fixed,
+    sorted sample of its flattened elements on every call (so two builds' dumps compare element for element)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 12345, dtype=torch.float64)
+    nested = bench._tensors({"a": [torch.ones(2, 3, dtype=torch.bfloat16), big], "b": 7}, "out", {})
+    assert list(nested) == ["out_a_0", "out_a_1"]
+    arrays = dict(nested, loss=torch.tensor([1.5]), twin=big + 1)
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    names = sorted(os.listdir(tmp_path / "x"))
+    assert names == ["loss.npy", "out_a_0.npy", "out_a_1.npy", "twin.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "x" / n), np.load(tmp_path / "y" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "x" / "out_a_0.npy").shape == (2, 3) and float(np.load(tmp_path / "x" / "loss.npy")[0]) == 1.5
+    s = np.load(tmp_path / "x" / "out_a_1.npy")
+    assert s.shape == (bench.DUMP_MAX_ELEMS,) and (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < big.numel()
+    assert np.array_equal(np.load(tmp_path / "x" / "twin.npy"), s + 1)      # same length, same indices
