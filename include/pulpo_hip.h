@@ -286,6 +286,31 @@ int pulpo_warp_landmarks(const float* lm /*(nlm,nd)*/, const float* df /*(nsamp,
 int pulpo_mc_moments_update(const float* sample, float* mean, float* m2, int64_t n, int k, void* stream);
 int pulpo_mc_moments_std(const float* m2, const float* scale /*nullable (B,V)*/, float* out /*(B,V)*/, int B, int C, int64_t V, int k, void* stream);
 
+/* ------------------------------------------------------------------------------- label maps (Monte-Carlo segmentation uncertainty)
+ * pulpo_warp_labels = warp3d(df, one_hot(labels, C)) without the one-hot map: SpatialTransformer (src/network_blocks.py:101-121) applied
+ * to a segmentation, as evaluate.py:252-274 does per sample in 2-D (the 3-D branch gives segmentations up, evaluate.py:208).
+ *   df (B,3,Dg,Hg,Wg); labels (B,1,Di,Hi,Wi) of dtype ldt (0 = uint8, 1 = int32), 1 <= C <= 256; grid and map may differ in size, depth 1 =
+ *   the 2-D form, as in pulpo_warp3d_fwd.  Every output is optional (NULL = not computed):
+ *     onehot (B,C,Dg,Hg,Wg)  the warped one-hot map; equal to pulpo_warp3d_fwd on one_hot(labels) bit for bit
+ *     amax   (B,1,Dg,Hg,Wg)  arg-max label (dtype ldt), the lowest class on ties
+ *     dice   (B,C)           with target (B,1,Dg,Hg,Wg, dtype ldt): per-class Evaluate.dsc (evaluate.py:321-327) of the warped one-hot map
+ *                            against one_hot(target); deterministic (64-bit fixed-point sums); ws: pulpo_warp_labels_ws_bytes(B, C) bytes
+ *     mean, m2 (B,C,Dg,Hg,Wg) fold the warped one-hot map in as sample k: the arithmetic of pulpo_mc_moments_update
+ *   *flag = 1 when a gathered or target label lies outside [0, C) (zeroed here).
+ * pulpo_labels_check: *flag = 1 when any of the n labels lies outside [0, C) (zeroed here).
+ * pulpo_labels_from_onehot: (B,C,V) fp32 -> (B,V) labels of dtype ldt, arg-max over C with the lowest class on ties (the reference's
+ *   one-hot loader output, src/data/OASIS/oasis.py:17,78, converted once).
+ * pulpo_map_ncc: Evaluate.ncc (evaluate.py:334-353, zero-normed, population std, eps 1e-15) of two maps of n floats, in double;
+ *   partial: 5 * pulpo_map_ncc_blocks(n) doubles; out: 1 double. */
+size_t pulpo_warp_labels_ws_bytes(int B, int C);
+int pulpo_warp_labels(const float* df, const void* labels, int ldt, int C, const void* target /*nullable*/, float* onehot /*nullable*/,
+                      void* amax /*nullable*/, float* dice /*nullable iff target is*/, float* mean /*nullable*/, float* m2 /*nullable iff mean is*/,
+                      int k, void* ws, int* flag, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, void* stream);
+int pulpo_labels_check(const void* labels, int ldt, int64_t n, int C, int* flag, void* stream);
+int pulpo_labels_from_onehot(const float* seg, void* labels, int ldt, int B, int C, int64_t V, void* stream);
+int pulpo_map_ncc_blocks(int64_t n);
+int pulpo_map_ncc(const float* a, const float* b, int64_t n, double* partial, double* out, void* stream);
+
 /* --------------------------------------------------------------------------------------------------- optimizer
  * torch.optim.Adam(lr) defaults (src/models.py:398-400) over a flat fp32 arena; gscale pre-multiplies the gradient. */
 int pulpo_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step, float gscale,

@@ -1,0 +1,321 @@
+// Warping an integer label map as if it were one-hot, for the Monte-Carlo evaluation of segmentations (evaluate.py:252-274, 2-D branch;
+// the 3-D branch gives them up for memory, evaluate.py:208).  The operation is warp3d(df, one_hot(labels, C)): per output voxel the
+// probability of class c is the sum of the trilinear corner weights whose corner carries label c.  The coordinate (sampling.h) and the
+// weight products are warp.hip's, in the same order; a one-hot channel multiplies every weight by 0 or 1 exactly, so the per-class sum
+// of the matching weights, added in corner order, is bitwise what warp_fwd_kernel computes on the one-hot map.
+// One thread per output voxel: displacement planes coalesced, 8 one- or four-byte corner gathers from L1/L2, the <= 8 distinct classes
+// deduplicated in registers.  Optional outputs, each selected by a nullable pointer: the dense one-hot warp, the arg-max label, per-class
+// Dice sums against a target label map and a Welford update of per-(class, voxel) moments (the arithmetic of pulpo_mc_moments_update).
+// Dice sums are 64-bit fixed point (weights in units of 2^-32, target counts as integers): integer adds are associative, so the wave
+// reduction, the LDS adds and the one global add per block and class give the same bits in any order.
+#include "common.h"
+#include "sampling.h"
+
+namespace {
+
+using pulpo::Corner;
+using pulpo::sample_coord;
+
+constexpr int kMaxClasses = 256;
+constexpr double kFix = 4294967296.0;        // 2^32: fixed-point unit of the Dice weight sums
+
+inline int eblocks(long items, int cap) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, cap)); }
+
+__device__ __forceinline__ unsigned long long to_fix(float p) { return (unsigned long long)__float2ull_rn(p * 4294967296.f); }
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <typename LT>
+__device__ __forceinline__ int load_label(const LT* p, long i) { return (int)p[i]; }
+
+// grid (nblk, B); sums: (B, C, 3) u64 = (sum p t, sum t^2, sum p^2) for p = warped one-hot, t = one-hot of the target
+template <typename LT>
+__global__ __launch_bounds__(256) void warp_labels_kernel(const float* __restrict__ df, const LT* __restrict__ lab, int C, const LT* __restrict__ tgt,
+                                                            float* __restrict__ onehot, LT* __restrict__ amax, float* __restrict__ mean,
+                                                            float* __restrict__ m2, int k, unsigned long long* __restrict__ sums, int* __restrict__ flag,
+                                                            int Dg, int Hg, int Wg, int Di, int Hi, int Wi) {
+    __shared__ unsigned long long sh[3 * kMaxClasses];
+    const int b = blockIdx.y;
+    const long Vg = (long)Dg * Hg * Wg, Vi = (long)Di * Hi * Wi;
+    const LT* lb = lab + b * Vi;
+    if (tgt != nullptr) {
+        for (int j = threadIdx.x; j < 3 * C; j += 256) sh[j] = 0ull;
+        __syncthreads();
+    }
+    const float inv = 1.f / (float)k;
+    bool bad = false;
+    // block-uniform trip count: every lane of a wave takes part in the Dice exchange below
+    for (long base = (long)blockIdx.x * 256; base < Vg; base += (long)gridDim.x * 256) {
+        const long v = base + threadIdx.x;
+        const bool valid = v < Vg;
+        int cl[8];
+        float p[8];
+        bool first[8];
+        int tc = -1;
+        if (valid) {
+            const int vi = (int)v;
+            const int x = vi % Wg, y = (vi / Wg) % Hg, z = vi / (Wg * Hg);
+            const float* d = df + (long)b * 3 * Vg + v;
+            const Corner cz = sample_coord((float)z, d[0], Dg, Di);
+            const Corner cy = sample_coord((float)y, d[Vg], Hg, Hi);
+            const Corner cx = sample_coord((float)x, d[2 * Vg], Wg, Wi);
+            const long o00 = ((long)cz.i0 * Hi + cy.i0) * Wi, o01 = ((long)cz.i0 * Hi + cy.i1) * Wi;
+            const long o10 = ((long)cz.i1 * Hi + cy.i0) * Wi, o11 = ((long)cz.i1 * Hi + cy.i1) * Wi;
+            const float wz0 = 1.f - cz.f, wy0 = 1.f - cy.f, wx0 = 1.f - cx.f;
+            // corner order and weight products of warp_fwd_kernel
+            const float w[8] = {wz0 * wy0 * wx0, wz0 * wy0 * cx.f, wz0 * cy.f * wx0, wz0 * cy.f * cx.f,
+                                cz.f * wy0 * wx0, cz.f * wy0 * cx.f, cz.f * cy.f * wx0, cz.f * cy.f * cx.f};
+            cl[0] = load_label(lb, o00 + cx.i0); cl[1] = load_label(lb, o00 + cx.i1);
+            cl[2] = load_label(lb, o01 + cx.i0); cl[3] = load_label(lb, o01 + cx.i1);
+            cl[4] = load_label(lb, o10 + cx.i0); cl[5] = load_label(lb, o10 + cx.i1);
+            cl[6] = load_label(lb, o11 + cx.i0); cl[7] = load_label(lb, o11 + cx.i1);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const bool ok = cl[i] >= 0 && cl[i] < C;
+                bad |= !ok;
+                bool f = ok;
+#pragma unroll
+                for (int h = 0; h < i; ++h) f &= cl[h] != cl[i];
+                first[i] = f;
+                float s = 0.f;                                 // matching weights added in corner order, starting from 0 like the warp's sum
+#pragma unroll
+                for (int j = i; j < 8; ++j) s += cl[j] == cl[i] ? w[j] : 0.f;
+                p[i] = s;
+            }
+            if (tgt != nullptr) {
+                tc = load_label(tgt, (long)b * Vg + v);
+                if (tc < 0 || tc >= C) { bad = true; tc = -1; }
+            }
+            if (amax != nullptr) {                             // highest probability; ties -> the lowest class
+                int bc = C;
+                float bp = -1.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    if (first[i] && (p[i] > bp || (p[i] == bp && cl[i] < bc))) { bp = p[i]; bc = cl[i]; }
+                amax[(long)b * Vg + v] = (LT)(bc < C ? bc : 0);
+            }
+            if (onehot != nullptr || mean != nullptr) {
+                for (int c = 0; c < C; ++c) {
+                    float val = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) val = (first[i] && cl[i] == c) ? p[i] : val;
+                    const long oi = ((long)b * C + c) * Vg + v;
+                    if (onehot != nullptr) onehot[oi] = val;
+                    if (mean != nullptr) {
+                        float mu = 0.f, q = 0.f;
+                        if (k > 1) { mu = mean[oi]; q = m2[oi]; }
+                        pulpo::welford_step(val, mu, q, k, inv);
+                        mean[oi] = mu;
+                        m2[oi] = q;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { cl[i] = -1; p[i] = 0.f; first[i] = false; }
+        }
+        if (tgt != nullptr) {
+            // Per class present in the wave: every lane's contribution, one integer wave sum, one LDS add.  The loop runs once per
+            // distinct class among the wave's corners and targets (one to three in the interior of a structure).
+            unsigned pending = (tc >= 0 ? 0x100u : 0u);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) pending |= first[i] ? (1u << i) : 0u;
+            while (true) {
+                const unsigned long long act = __ballot(pending != 0u);
+                if (act == 0ull) break;
+                int cand = -1;
+#pragma unroll
+                for (int i = 7; i >= 0; --i) cand = (pending >> i) & 1u ? cl[i] : cand;
+                if (cand < 0 && (pending & 0x100u)) cand = tc;
+                const int c = __shfl(cand, __ffsll((long long)act) - 1, 64);
+                unsigned long long u0 = 0ull, u1 = 0ull, u2 = 0ull;
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    if (((pending >> i) & 1u) && cl[i] == c) {
+                        u2 += to_fix(p[i] * p[i]);
+                        if (tc == c) u0 += to_fix(p[i]);
+                        pending &= ~(1u << i);
+                    }
+                if ((pending & 0x100u) && tc == c) {
+                    u1 = 1ull;
+                    pending &= ~0x100u;
+                }
+                u0 = wave_sum_u64(u0);
+                u1 = wave_sum_u64(u1);
+                u2 = wave_sum_u64(u2);
+                if ((threadIdx.x & 63) == 0) {
+                    if (u0) atomicAdd(&sh[3 * c], u0);
+                    if (u1) atomicAdd(&sh[3 * c + 1], u1);
+                    if (u2) atomicAdd(&sh[3 * c + 2], u2);
+                }
+            }
+        }
+    }
+    if (bad) atomicOr(flag, 1);
+    if (tgt != nullptr) {
+        __syncthreads();
+        unsigned long long* dst = sums + (long)b * C * 3;
+        for (int j = threadIdx.x; j < 3 * C; j += 256)
+            if (sh[j]) atomicAdd(dst + j, sh[j]);
+    }
+}
+
+// dice[b][c] = (2 mean(p t) + 1e-6) / (mean(t^2) + mean(p^2) + 1e-6) over the grid's V voxels: pulpo_dsc's formula for the plane (b, c)
+__global__ void dice_from_sums_kernel(const unsigned long long* __restrict__ sums, int n, double V, float* __restrict__ dice) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double s0 = (double)sums[3 * i] / kFix, s1 = (double)sums[3 * i + 1], s2 = (double)sums[3 * i + 2] / kFix;
+    dice[i] = (float)((2.0 * s0 / V + 1e-6) / (s1 / V + s2 / V + 1e-6));
+}
+
+template <typename LT>
+__global__ __launch_bounds__(256) void labels_check_kernel(const LT* __restrict__ lab, long n, int C, int* __restrict__ flag) {
+    bool bad = false;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const int l = (int)lab[e];
+        bad |= l < 0 || l >= C;
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+// (B, C, V) fp32 -> (B, V) labels: arg-max over the channels, the lowest class on ties
+template <typename LT>
+__global__ __launch_bounds__(256) void labels_from_onehot_kernel(const float* __restrict__ seg, LT* __restrict__ out, int C, long V, long total) {
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long b = e / V, v = e - b * V;
+        const float* s = seg + b * C * V + v;
+        float best = s[0];
+        int bc = 0;
+        for (int c = 1; c < C; ++c) {
+            const float x = s[(long)c * V];
+            if (x > best) { best = x; bc = c; }
+        }
+        out[e] = (LT)bc;
+    }
+}
+
+// Evaluate.ncc (evaluate.py:334-353), zero-normed: sum((a - ma) (b - mb)) / ((std(a) n + 1e-15) (std(b) + 1e-15)), population std.
+// Pass 1: block partials of (sum a, sum b); pass 2: every block re-sums pass 1 in the same order for the means, then partials of the
+// centred (sum da db, sum da^2, sum db^2); the finalize sums those in block order.  All in double, no atomics.
+__device__ __forceinline__ double block_sum_d(double v, double* sh) {
+    v = pulpo::wave_sum_d(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__global__ __launch_bounds__(256) void ncc_sums_kernel(const float* __restrict__ a, const float* __restrict__ b, long n, double* __restrict__ part) {
+    __shared__ double sh[4];
+    double sa = 0.0, sb = 0.0;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        sa += a[e];
+        sb += b[e];
+    }
+    const double ta = block_sum_d(sa, sh), tb = block_sum_d(sb, sh);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = ta; part[2 * blockIdx.x + 1] = tb; }
+}
+
+__global__ __launch_bounds__(256) void ncc_centred_kernel(const float* __restrict__ a, const float* __restrict__ b, long n, const double* __restrict__ part,
+                                                            double* __restrict__ part2) {
+    __shared__ double sh[4];
+    __shared__ double mab[2];
+    if (threadIdx.x == 0) {
+        double sa = 0.0, sb = 0.0;
+        for (int k = 0; k < (int)gridDim.x; ++k) { sa += part[2 * k]; sb += part[2 * k + 1]; }
+        mab[0] = sa / (double)n;
+        mab[1] = sb / (double)n;
+    }
+    __syncthreads();
+    const double ma = mab[0], mb = mab[1];
+    double sab = 0.0, saa = 0.0, sbb = 0.0;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const double da = (double)a[e] - ma, db = (double)b[e] - mb;
+        sab += da * db;
+        saa += da * da;
+        sbb += db * db;
+    }
+    const double t0 = block_sum_d(sab, sh), t1 = block_sum_d(saa, sh), t2 = block_sum_d(sbb, sh);
+    if (threadIdx.x == 0) { part2[3 * blockIdx.x] = t0; part2[3 * blockIdx.x + 1] = t1; part2[3 * blockIdx.x + 2] = t2; }
+}
+
+__global__ void ncc_finalize_kernel(const double* __restrict__ part2, int nblk, long n, double* __restrict__ out) {
+    if (threadIdx.x != 0) return;
+    double sab = 0.0, saa = 0.0, sbb = 0.0;
+    for (int k = 0; k < nblk; ++k) { sab += part2[3 * k]; saa += part2[3 * k + 1]; sbb += part2[3 * k + 2]; }
+    const double sa = sqrt(saa / (double)n), sb = sqrt(sbb / (double)n);
+    out[0] = sab / ((sa * (double)n + 1e-15) * (sb + 1e-15));
+}
+
+}  // namespace
+
+PULPO_API size_t pulpo_warp_labels_ws_bytes(int B, int C) { return sizeof(unsigned long long) * 3 * (size_t)std::max(B, 0) * std::max(C, 0); }
+
+PULPO_API int pulpo_warp_labels(const float* df, const void* labels, int ldt, int C, const void* target, float* onehot, void* amax, float* dice,
+                                float* mean, float* m2, int k, void* ws, int* flag, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi,
+                                void* stream) {
+    PULPO_REQUIRE(df && labels && flag && B > 0 && (ldt == 0 || ldt == 1) && C >= 1 && C <= kMaxClasses, "warp_labels: bad arguments (1 <= C <= 256)");
+    PULPO_REQUIRE(Dg >= 1 && Hg > 1 && Wg > 1 && Di > 0 && Hi > 0 && Wi > 0 && (Dg > 1 || Di == 1),
+                  "warp_labels: grid H, W must be > 1 (depth 1 = 2-D form, with a depth-1 label map)");
+    PULPO_REQUIRE((long)Dg * Hg * Wg < (1L << 31), "warp_labels: grids of 2^31 voxels and more are not supported");
+    PULPO_REQUIRE((target == nullptr) == (dice == nullptr) && (target == nullptr || ws != nullptr), "warp_labels: target, dice and ws go together");
+    PULPO_REQUIRE((mean == nullptr) == (m2 == nullptr) && (mean == nullptr || k >= 1), "warp_labels: mean and m2 go together (k >= 1)");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st);
+    if (e == hipSuccess && target != nullptr) e = hipMemsetAsync(ws, 0, pulpo_warp_labels_ws_bytes(B, C), st);
+    if (e != hipSuccess) return pulpo::fail((int)e, "warp_labels memset: %s", hipGetErrorString(e));
+    const long Vg = (long)Dg * Hg * Wg;
+    const dim3 grid(eblocks(Vg, std::max(1, 2048 / B)), B);
+    unsigned long long* sums = (unsigned long long*)ws;
+    if (ldt == 0)
+        hipLaunchKernelGGL(warp_labels_kernel<uint8_t>, grid, dim3(256), 0, st, df, (const uint8_t*)labels, C, (const uint8_t*)target, onehot,
+                           (uint8_t*)amax, mean, m2, k, sums, flag, Dg, Hg, Wg, Di, Hi, Wi);
+    else
+        hipLaunchKernelGGL(warp_labels_kernel<int32_t>, grid, dim3(256), 0, st, df, (const int32_t*)labels, C, (const int32_t*)target, onehot,
+                           (int32_t*)amax, mean, m2, k, sums, flag, Dg, Hg, Wg, Di, Hi, Wi);
+    int rc = pulpo::check_launch("warp_labels");
+    if (rc || target == nullptr) return rc;
+    const int n = B * C;
+    hipLaunchKernelGGL(dice_from_sums_kernel, dim3((n + 255) / 256), dim3(256), 0, st, sums, n, (double)Vg, dice);
+    return pulpo::check_launch("warp_labels dice");
+}
+
+PULPO_API int pulpo_labels_check(const void* labels, int ldt, int64_t n, int C, int* flag, void* stream) {
+    PULPO_REQUIRE(labels && flag && n > 0 && (ldt == 0 || ldt == 1), "labels_check: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st);
+    if (e != hipSuccess) return pulpo::fail((int)e, "labels_check memset: %s", hipGetErrorString(e));
+    if (ldt == 0) hipLaunchKernelGGL(labels_check_kernel<uint8_t>, dim3(eblocks(n, 2048)), dim3(256), 0, st, (const uint8_t*)labels, (long)n, C, flag);
+    else hipLaunchKernelGGL(labels_check_kernel<int32_t>, dim3(eblocks(n, 2048)), dim3(256), 0, st, (const int32_t*)labels, (long)n, C, flag);
+    return pulpo::check_launch("labels_check");
+}
+
+PULPO_API int pulpo_labels_from_onehot(const float* seg, void* labels, int ldt, int B, int C, int64_t V, void* stream) {
+    PULPO_REQUIRE(seg && labels && B > 0 && C >= 1 && V > 0 && (ldt == 1 || (ldt == 0 && C <= 256)), "labels_from_onehot: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const long total = (long)B * V;
+    if (ldt == 0) hipLaunchKernelGGL(labels_from_onehot_kernel<uint8_t>, dim3(eblocks(total, 4096)), dim3(256), 0, st, seg, (uint8_t*)labels, C, (long)V, total);
+    else hipLaunchKernelGGL(labels_from_onehot_kernel<int32_t>, dim3(eblocks(total, 4096)), dim3(256), 0, st, seg, (int32_t*)labels, C, (long)V, total);
+    return pulpo::check_launch("labels_from_onehot");
+}
+
+PULPO_API int pulpo_map_ncc_blocks(int64_t n) { return eblocks(n, 1024); }
+
+PULPO_API int pulpo_map_ncc(const float* a, const float* b, int64_t n, double* partial, double* out, void* stream) {
+    PULPO_REQUIRE(a && b && partial && out && n > 0, "map_ncc: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = pulpo_map_ncc_blocks(n);
+    double* part2 = partial + 2 * nblk;
+    hipLaunchKernelGGL(ncc_sums_kernel, dim3(nblk), dim3(256), 0, st, a, b, (long)n, partial);
+    int rc = pulpo::check_launch("map_ncc sums");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ncc_centred_kernel, dim3(nblk), dim3(256), 0, st, a, b, (long)n, partial, part2);
+    rc = pulpo::check_launch("map_ncc centred");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ncc_finalize_kernel, dim3(1), dim3(64), 0, st, part2, nblk, (long)n, out);
+    return pulpo::check_launch("map_ncc finalize");
+}

@@ -3,6 +3,7 @@
 // channels; here each sample is folded into running (mean, M2) images as it is produced (Welford), so N never enters the
 // memory footprint.  HBM-bound: one read of the sample, one read-modify-write of the two state images per update.
 #include "common.h"
+#include "sampling.h"
 
 namespace {
 
@@ -13,17 +14,11 @@ __global__ __launch_bounds__(256) void mc_update_kernel(const float* __restrict_
                                                           int k) {
     const float inv = 1.f / (float)k;
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-        const float x = sample[e];
-        if (k == 1) {
-            mean[e] = x;
-            m2[e] = 0.f;
-        } else {
-            const float mu = mean[e];
-            const float d = x - mu;
-            const float mu2 = mu + d * inv;
-            mean[e] = mu2;
-            m2[e] += d * (x - mu2);
-        }
+        float mu = 0.f, q = 0.f;
+        if (k > 1) { mu = mean[e]; q = m2[e]; }
+        pulpo::welford_step(sample[e], mu, q, k, inv);        // (sampling.h: the label warp folds its one-hot samples with the same step)
+        mean[e] = mu;
+        m2[e] = q;
     }
 }
 

@@ -7,37 +7,13 @@
 // HBM/L2-bound gather kernels: one thread per output voxel, displacement planes read coalesced, 8-corner gather
 // served by L1/L2; the backward scatters with float atomics (memory-side adds, MI355X_MICROARCH.md).
 #include "common.h"
+#include "sampling.h"
 #include <stdlib.h>
 
 namespace {
 
-struct Corner {
-    int i0, i1;
-    float f;       // fraction towards i1
-    float dscale;  // d(coord)/d(displacement); 0 where the coordinate was clamped
-};
-
-__device__ __forceinline__ Corner sample_coord(float pos, float disp, int Sg, int Si) {
-    if (Sg == 1) {            // a depth-1 grid is the reference's 2-D case (bilinear grid_sample over H, W): no coordinate along this axis
-        Corner r;
-        r.i0 = 0; r.i1 = 0; r.f = 0.f; r.dscale = 0.f;
-        return r;
-    }
-    float t = pos + disp;
-    t = t / (float)(Sg - 1);
-    t = t - 0.5f;
-    t = 2.f * t;
-    float c = ((t + 1.f) * (float)Si - 1.f) / 2.f;
-    Corner r;
-    const float hi = (float)(Si - 1);
-    r.dscale = (c > 0.f && c < hi) ? (float)Si / (float)(Sg - 1) : 0.f;   // ATen clip_coordinates_set_grad
-    c = fminf(hi, fmaxf(c, 0.f));
-    const float fl = floorf(c);
-    r.i0 = (int)fl;
-    r.i1 = min(r.i0 + 1, Si - 1);
-    r.f = c - fl;
-    return r;
-}
+using pulpo::Corner;
+using pulpo::sample_coord;
 
 // out[b][c][v] = trilinear(img[b][c], grid position v displaced by df[b][:, v]);  optional residual: out += add[b][c][v]
 template <int C>

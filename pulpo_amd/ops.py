@@ -1916,6 +1916,12 @@ class StreamingMoments:
             raise ValueError("StreamingMoments: no samples")
         return self._mean
 
+    def m2(self) -> torch.Tensor:
+        """the running sum of squared deviations from the mean (Welford's M2): var = M2 / (count - 1)"""
+        if self._m2 is None:
+            raise ValueError("StreamingMoments: no samples")
+        return self._m2
+
     def std_map(self, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self._m2 is None:
             raise ValueError("StreamingMoments: no samples")
@@ -1991,4 +1997,157 @@ def warp_landmarks(lm, df):
              ctypes.cast(flag.data_ptr(), ctypes.POINTER(ctypes.c_int)), _stream())
     if int(flag.item()):
         raise IndexError("warp_landmarks: landmark index out of bounds of the displacement field")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ label maps (MC segmentation uncertainty)
+# Evaluation-time operators: no autograd (call them under torch.no_grad(); the outputs carry no graph).  Label maps are uint8 or int32.
+_LABEL_DT = {torch.uint8: 0, torch.int32: 1}
+
+
+def _require_labels(*ts: Optional[torch.Tensor]):
+    for t in ts:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise PulpoHipError("pulpo_amd operators run on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype not in _LABEL_DT:
+            raise PulpoHipError(f"label maps are uint8 or int32 (got {t.dtype})")
+
+
+def _int_ptr(t: torch.Tensor, i: int = 0):
+    return ctypes.cast(t.data_ptr() + 4 * i, ctypes.POINTER(ctypes.c_int))
+
+
+def _check_labels(labels: torch.Tensor, num_classes: int, flag: torch.Tensor, i: int) -> None:
+    lib.call("pulpo_labels_check", _ptr(labels), _LABEL_DT[labels.dtype], labels.numel(), int(num_classes), _int_ptr(flag, i), _stream())
+
+
+def _raise_on_flag(flag: torch.Tensor, what: str) -> None:
+    if int(flag.max().item()):                     # one host read
+        raise IndexError(f"{what}: label outside [0, num_classes)")
+
+
+def _warp_labels_raw(df, labels, C: int, target, onehot, amax, dice, mean, m2, k: int, flag, fi: int):
+    """df (B,3,Dg,Hg,Wg) planar fp32, labels (B,1,Di,Hi,Wi), target (B,1,Dg,Hg,Wg) of the labels' dtype: one pulpo_warp_labels launch"""
+    B, _, Dg, Hg, Wg = df.shape
+    Di, Hi, Wi = labels.shape[2:]
+    ws = torch.empty(lib.query("pulpo_warp_labels_ws_bytes", B, C), device=df.device, dtype=torch.uint8) if target is not None else None
+    lib.call("pulpo_warp_labels", _ptr(df), _ptr(labels), _LABEL_DT[labels.dtype], C, _ptr(target), _ptr(onehot), _ptr(amax), _ptr(dice),
+             _ptr(mean), _ptr(m2), int(k), _ptr(ws), _int_ptr(flag, fi), B, Dg, Hg, Wg, int(Di), int(Hi), int(Wi), _stream())
+
+
+def _lift_labels(df, labels, target):
+    """2-D inputs -> the depth-1 3-D form of warp3d; label maps as contiguous (B,1,D,H,W), the target in the labels' dtype"""
+    if _is2d(df):
+        df, labels, target = _lift_field(df), _lift(labels), _lift(target)
+    df, labels = planar(df.detach()), labels.contiguous()
+    if labels.dim() != 5 or labels.shape[1] != 1 or labels.shape[0] != df.shape[0]:
+        raise PulpoHipError(f"label map (B, 1, ...) expected for a field of shape {tuple(df.shape)}, got {tuple(labels.shape)}")
+    if target is not None:
+        target = target.to(labels.dtype).contiguous()
+        if tuple(target.shape) != (df.shape[0], 1) + tuple(df.shape[2:]):
+            raise PulpoHipError(f"target label map (B, 1) + the field's grid expected, got {tuple(target.shape)}")
+    return df, labels, target
+
+
+@torch.no_grad()
+def warp_labels(df, labels, num_classes: int, target=None, onehot: bool = False, argmax: bool = False):
+    """warp3d(df, one_hot(labels, num_classes)) without the one-hot maps (SpatialTransformer on a segmentation, evaluate.py:252-274).
+    df (B, 3, D, H, W) fp32 (2-D: (B, 2, H, W)); labels (B, 1, ...) uint8 / int32 on the moving map's grid, which may differ from the field's.
+    Returns the requested outputs in this order - onehot: the warped one-hot map (B, C, grid) fp32; argmax: its arg-max label map
+    (B, 1, grid) in the labels' dtype, the lowest class on ties; target (B, 1, grid): per-class Dice (B, C) of the warped one-hot map against
+    one_hot(target) (Evaluate.dsc per class, evaluate.py:321-327) - a single tensor when one output is requested.  A label outside
+    [0, num_classes) raises IndexError (one host read).  Evaluation only: no autograd."""
+    if not (onehot or argmax or target is not None):
+        raise ValueError("warp_labels: request at least one of onehot, argmax, target")
+    _require_gpu(df)
+    _require_labels(labels, target)
+    is2d = _is2d(df)
+    df, labels, target = _lift_labels(df, labels, target)
+    B, C = df.shape[0], int(num_classes)
+    grid = tuple(df.shape[2:])
+    dev = df.device
+    oh = torch.empty((B, C) + grid, device=dev, dtype=torch.float32) if onehot else None
+    am = torch.empty((B, 1) + grid, device=dev, dtype=labels.dtype) if argmax else None
+    dice = torch.empty((B, C), device=dev, dtype=torch.float32) if target is not None else None
+    flag = torch.zeros(3, device=dev, dtype=torch.int32)
+    _check_labels(labels, C, flag, 1)
+    if target is not None:
+        _check_labels(target, C, flag, 2)
+    _warp_labels_raw(df, labels, C, target, oh, am, dice, None, None, 1, flag, 0)
+    _raise_on_flag(flag, "warp_labels")
+    out = [t.squeeze(2) if is2d else t for t in (oh, am) if t is not None] + ([dice] if dice is not None else [])
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+class LabelMoments(StreamingMoments):
+    """StreamingMoments of warp3d(df, one_hot(labels, C)) without a per-sample C-channel tensor: update(df, labels) folds the warped one-hot
+    map in (the arithmetic of StreamingMoments.update, so N updates equal StreamingMoments over the N warped one-hot maps); mean() and
+    std_map() are StreamingMoments'.  update(..., target=...) also returns that sample's per-class Dice (B, C), from the same pass.
+    Evaluation only: no autograd."""
+
+    def __init__(self, num_classes: int) -> None:
+        super().__init__()
+        self.num_classes = int(num_classes)
+        self._checked = None
+
+    @torch.no_grad()
+    def update(self, df, labels, target=None):
+        _require_gpu(df)
+        _require_labels(labels, target)
+        shape2d = (df.shape[0], self.num_classes) + tuple(df.shape[2:]) if _is2d(df) else None
+        df, labels, target = _lift_labels(df, labels, target)
+        B, C = df.shape[0], self.num_classes
+        shape = shape2d or (B, C) + tuple(df.shape[2:])
+        if self._mean is None:
+            self._mean = torch.empty(shape, device=df.device, dtype=torch.float32)
+            self._m2 = torch.empty_like(self._mean)
+        elif tuple(self._mean.shape) != tuple(shape):
+            raise ValueError(f"LabelMoments: sample shape {tuple(shape)} differs from {tuple(self._mean.shape)}")
+        flag = torch.zeros(3, device=df.device, dtype=torch.int32)
+        # the whole label map is range-checked (one host read) whenever it is a map not seen before; the samples of a Monte-Carlo loop
+        # share one map and then run without a host synchronisation
+        key = (labels.data_ptr(), tuple(labels.shape), labels.dtype, None if target is None else (target.data_ptr(), tuple(target.shape)))
+        check = key != self._checked
+        if check:
+            _check_labels(labels, C, flag, 1)
+            if target is not None:
+                _check_labels(target, C, flag, 2)
+            _raise_on_flag(flag, "LabelMoments.update")
+            self._checked = key
+        dice = torch.empty((B, C), device=df.device, dtype=torch.float32) if target is not None else None
+        self.count += 1
+        _warp_labels_raw(df, labels, C, target, None, None, dice, self._mean, self._m2, self.count, flag, 0)
+        return dice
+
+
+@torch.no_grad()
+def labels_from_onehot(seg, dtype: Optional[torch.dtype] = None):
+    """(B, C, ...) fp32 one-hot (or soft) segmentation -> (B, 1, ...) label map: arg-max over C, the lowest class on ties.  Converts the
+    reference's one-hot loader output (src/data/OASIS/oasis.py:17,78) once per pair.  dtype: uint8 (default for C <= 256) or int32.
+    Evaluation only: no autograd."""
+    _require_gpu(seg)
+    s = seg.detach().contiguous()
+    B, C = int(s.shape[0]), int(s.shape[1])
+    dtype = dtype or (torch.uint8 if C <= 256 else torch.int32)
+    if dtype not in _LABEL_DT:
+        raise PulpoHipError(f"label maps are uint8 or int32 (got {dtype})")
+    out = torch.empty((B, 1) + tuple(s.shape[2:]), device=s.device, dtype=dtype)
+    lib.call("pulpo_labels_from_onehot", _ptr(s), _ptr(out), _LABEL_DT[dtype], B, C, s[0, 0].numel(), _stream())
+    return out
+
+
+@torch.no_grad()
+def map_ncc(a, b):
+    """Evaluate.ncc(a, b) (evaluate.py:334-353: zero-normed, population std, eps 1e-15) of two maps of equal size, accumulated in double
+    on the device with a deterministic two-stage reduction; returns a 0-d float64 device tensor.  Evaluation only: no autograd."""
+    _require_gpu(a, b)
+    x, y = a.detach().contiguous(), b.detach().contiguous()
+    if x.numel() != y.numel():
+        raise PulpoHipError(f"map_ncc: maps of {x.numel()} and {y.numel()} elements")
+    n = x.numel()
+    part = torch.empty(5 * lib.query("pulpo_map_ncc_blocks", n), device=x.device, dtype=torch.float64)
+    out = torch.empty((), device=x.device, dtype=torch.float64)
+    lib.call("pulpo_map_ncc", _ptr(x), _ptr(y), n, _ptr(part), _ptr(out), _stream())
     return out
