@@ -232,9 +232,10 @@ PULPO_API int pulpo_heads_bwd_t(const void* h, int h_dt, int64_t ps, const float
     PULPO_REQUIRE((nout == 3 && g0) || (nout == 6 && sigma), "heads_bwd: nout must be 3 (with g0) or 6 (with sigma)");
     PULPO_REQUIRE_DT(h_dt, "heads_bwd");
     hipStream_t st = (hipStream_t)stream;
-    const bool v4 = C % 4 == 0;
-    if (v4) PULPO_REQUIRE(ps % 4 == 0 && dps % 4 == 0 && ((((uintptr_t)h) | ((uintptr_t)dh)) % (h_dt ? 8 : 16)) == 0, "heads_bwd: unaligned operands");
-    PULPO_REQUIRE(C / (v4 ? 4 : 1) <= 256, "heads_bwd: too many channels");
+    // unaligned operands (a channel slice of a wider channels-last buffer at an odd offset, which the forward takes with its scalar loads) take the
+    // VEC = 1 instance like the forward does, instead of refusing a tensor whose forward pass already ran
+    const bool v4 = C % 4 == 0 && ps % 4 == 0 && dps % 4 == 0 && ((((uintptr_t)h) | ((uintptr_t)dh)) % (h_dt ? 8 : 16)) == 0;
+    PULPO_REQUIRE(C / (v4 ? 4 : 1) <= 256, "heads_bwd: too many channels (%d%s)", C, v4 || C % 4 != 0 ? "" : ", unaligned operands");
     const int nblk = pulpo_heads_bwd_blocks(B, V, C);
     const int RB = std::max(1, 256 / (C / (v4 ? 4 : 1)));
     const size_t lds = ((size_t)RB * (nout * C + nout) + (nout == 6 ? (size_t)2 * RB * 16 : 0)) * sizeof(float);       // reduction rows + (nout 6) the per-pixel operand rows

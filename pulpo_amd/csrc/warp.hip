@@ -540,15 +540,19 @@ PULPO_API int pulpo_warp3d_bwd_det(const float* df, const float* img, const floa
     PULPO_REQUIRE(ws != nullptr || gimg == nullptr, "warp3d_bwd_det: workspace of pulpo_warp3d_bwd_det_ws_bytes() bytes required for the image gradient");
     hipStream_t st = (hipStream_t)stream;
     const long total = (long)B * Dg * Hg * Wg, ni = (long)B * C * Di * Hi * Wi;
-    unsigned* slots = (unsigned*)ws;
-    long long* acc = gimg ? (long long*)((char*)ws + 256) : nullptr;
-    if (gimg != nullptr) {
-        hipError_t e = hipMemsetAsync(ws, 0, 256 + sizeof(long long) * (size_t)ni, st);
-        if (e != hipSuccess) return pulpo::fail((int)e, "warp3d_bwd_det memset: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(absmax_kernel, dim3(fx_blocks((long)B * C * Dg * Hg * Wg)), dim3(256), 0, st, gout, (long)B * C * Dg * Hg * Wg, slots);
+    if (gimg == nullptr) {
+        // the displacement gradient alone is a gather with plain stores, deterministic as it is: the plain kernel (the fixed-point one reads its
+        // scale slot from the workspace, which this call need not pass)
+        hipLaunchKernelGGL(warp_bwd_kernel<false>, dim3(eblocks(total)), dim3(256), 0, st, df, img, gout, gdf, (float*)nullptr, B, Dg, Hg, Wg, Di, Hi, Wi, C);
+        return pulpo::check_launch("warp3d_bwd_det");
     }
+    unsigned* slots = (unsigned*)ws;
+    long long* acc = (long long*)((char*)ws + 256);
+    hipError_t e = hipMemsetAsync(ws, 0, 256 + sizeof(long long) * (size_t)ni, st);
+    if (e != hipSuccess) return pulpo::fail((int)e, "warp3d_bwd_det memset: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(absmax_kernel, dim3(fx_blocks((long)B * C * Dg * Hg * Wg)), dim3(256), 0, st, gout, (long)B * C * Dg * Hg * Wg, slots);
     hipLaunchKernelGGL(warp_bwd_fx_kernel<false>, dim3(eblocks(total)), dim3(256), 0, st, df, img, gout, gdf, acc, slots, B, Dg, Hg, Wg, Di, Hi, Wi, C);
-    if (gimg != nullptr) hipLaunchKernelGGL(fx_to_float_kernel, dim3(fx_blocks(ni)), dim3(256), 0, st, acc, gimg, ni, slots, 1.0f, (unsigned*)nullptr);
+    hipLaunchKernelGGL(fx_to_float_kernel, dim3(fx_blocks(ni)), dim3(256), 0, st, acc, gimg, ni, slots, 1.0f, (unsigned*)nullptr);
     return pulpo::check_launch("warp3d_bwd_det");
 }
 

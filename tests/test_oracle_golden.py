@@ -423,3 +423,82 @@ def test_models_py_class_api_fixture(golden, res):
         close(rec_l[l], g[f"train.logged.recon_loss_level.{l}"], rtol=2e-6, atol=1e-7)
         close(kl_l[l], g[f"train.logged.kl_loss_level.{l}"], rtol=2e-6, atol=1e-7)
         close(reg_l[l], g[f"train.logged.regularization_loss_level.{l}"], rtol=2e-6, atol=1e-7)
+
+
+# ------------------------------------------------------------------------------------------------ float64 references of the pyramid tests
+def test_pyramid_references_match_the_oracle():
+    """tests/pyramid_ref.py restates the head, loss and field operators with cumsum / einsum / separable passes so that the pyramid tests can
+    evaluate them in float64 at full size: here each one is held to the oracle's form of the same operator at small shapes"""
+    import pyramid_ref as R
+    import torch.nn.functional as F
+    gen = torch.Generator().manual_seed(21)
+    dbl = dict(dtype=torch.float64)
+    # heads: the oracle's two 1x1x1 convs + softplus (sigma pre-activations spread over the softplus threshold), the sample and the plain head
+    h = torch.randn(2, 6, 5, 7, 4, generator=gen, **dbl)
+    sd = {"m._conv_mu.weight": torch.randn(3, 6, 1, 1, 1, generator=gen, **dbl), "m._conv_mu.bias": torch.randn(3, generator=gen, **dbl),
+          "m._conv_sigma.0.weight": 8 * torch.randn(3, 6, 1, 1, 1, generator=gen, **dbl), "m._conv_sigma.0.bias": torch.randn(3, generator=gen, **dbl)}
+    eps = torch.randn(2, 3, 5, 7, 4, generator=gen, **dbl)
+    mu, sg = O.mu_sigma(h, sd, "m")
+    rmu, rsg, rz = R.mu_sigma_ref(h, sd["m._conv_mu.weight"], sd["m._conv_mu.bias"], sd["m._conv_sigma.0.weight"], sd["m._conv_sigma.0.bias"], eps)
+    assert float((rmu - mu).abs().max()) < 1e-12 and float((rsg - sg).abs().max()) < 1e-12
+    assert float((rz - (mu + sg * eps)).abs().max()) < 1e-12 and bool((rsg > 20).any()) and bool((rsg < 1).any())
+    assert R.mu_sigma_ref(h, sd["m._conv_mu.weight"], sd["m._conv_mu.bias"], sd["m._conv_sigma.0.weight"], sd["m._conv_sigma.0.bias"], None)[2] is not None
+    w, b = torch.randn(3, 6, 1, 1, 1, generator=gen, **dbl), torch.randn(3, generator=gen, **dbl)
+    assert float((R.conv1x1_ref(h, w, b) - F.conv3d(h, w, b)).abs().max()) < 1e-12
+    # NCC: separable prefix-sum box sums, the loss and its closed-form gradient (and the 2-D window count at depth 1)
+    for win, size, B in ((3, (6, 7, 5), 2), (9, (12, 10, 16), 1), (11, (3, 12, 9), 1), (13, (8, 9, 10), 1), (5, (4, 4, 4), 1)):
+        t, p = torch.rand(B, 1, *size, generator=gen, **dbl), torch.rand(B, 1, *size, generator=gen, **dbl)
+        assert float((R.box_sum(t, win) - O.box_sum(t, win)).abs().max()) < 1e-12
+        assert abs(float(R.ncc_ref(p, t, win, 0.05)) - float(O.ncc(p, t, win, 0.05))) < 1e-12
+        assert float((R.ncc_grad_ref(p, t, win, 0.05) - O.ncc_grad_closed_form(p, t, win, 0.05)).abs().max()) < 1e-12
+        pg = p.clone().requires_grad_(True)
+        ga, = torch.autograd.grad(O.ncc(pg, t, win, 0.05), [pg])
+        assert float((R.ncc_grad_ref(p, t, win, 0.05) - ga).abs().max()) < 1e-10 * float(ga.abs().max())
+    t, p = torch.rand(2, 1, 1, 9, 12, generator=gen, **dbl), torch.rand(2, 1, 1, 9, 12, generator=gen, **dbl)
+    k2 = torch.ones(1, 1, 5, 5, **dbl)
+    s2 = [F.conv2d(v[:, :, 0], k2, padding=2) for v in (t, p, t * t, p * p, t * p)]
+    u = [s2[0] / 25, s2[1] / 25]
+    cross, Iv, Jv = s2[4] - u[1] * s2[0] - u[0] * s2[1] + u[0] * u[1] * 25, s2[2] - 2 * u[0] * s2[0] + u[0] ** 2 * 25, s2[3] - 2 * u[1] * s2[1] + u[1] ** 2 * 25
+    assert abs(float(R.ncc_ref(p, t, 5, 0.05)) + 0.05 / 2 * float((cross * cross / (Iv * Jv + 1e-8)).sum())) < 1e-12
+    pg = p.clone().requires_grad_(True)
+    ga, = torch.autograd.grad(R.ncc_ref(pg, t, 5, 0.05), [pg])
+    assert float((R.ncc_grad_ref(p, t, 5, 0.05) - ga).abs().max()) < 1e-10 * float(ga.abs().max())
+    # KL with and without the second distribution, the regulariser (3-D and the depth-1 form)
+    m0, s0 = torch.randn(2, 3, 4, 5, 6, generator=gen, **dbl), torch.rand(2, 3, 4, 5, 6, generator=gen, **dbl) + 1e-3
+    m1, s1 = torch.randn(2, 3, 4, 5, 6, generator=gen, **dbl), torch.rand(2, 3, 4, 5, 6, generator=gen, **dbl) + 1e-3
+    assert abs(float(R.kl_ref(m0, s0)) - float(O.kl_diag(m0, s0))) < 1e-9 * abs(float(O.kl_diag(m0, s0)))
+    assert abs(float(R.kl_ref(m0, s0, m1, s1)) - float(O.kl_diag(m0, s0, m1, s1))) < 1e-9 * abs(float(O.kl_diag(m0, s0, m1, s1)))
+    df = torch.randn(2, 3, 5, 6, 7, generator=gen, **dbl)
+    assert abs(float(R.l2reg_ref(df, 0.025)) - float(O.l2_reg(df, 0.025))) < 1e-12
+    f2 = torch.randn(2, 3, 1, 6, 7, generator=gen, **dbl)
+    want = (((f2[..., 1:, 1:] - f2[..., :-1, 1:]) ** 2 + (f2[..., 1:, 1:] - f2[..., 1:, :-1]) ** 2).mean() * 0.025 * 42)
+    assert abs(float(R.l2reg_ref(f2, 0.025)) - float(want)) < 1e-12
+    # warp (the oracle's grid_sample) and its sample coordinates against the explicit gather's clamp / floor; resize against F.interpolate
+    df, img = torch.randn(2, 3, 6, 7, 8, generator=gen, **dbl) * 3, torch.rand(2, 1, 9, 5, 8, generator=gen, **dbl)
+    assert float((R.warp_ref(df, img) - O.warp_explicit(df, img)).abs().max()) < 1e-12
+    c = R.warp_coords(df, img.shape[2:])
+    assert c.shape == (3, 2, 6, 7, 8) and float(c.min()) < 0 and float(c[0].max()) > 8
+    for si, so in (((5, 6, 7), (10, 12, 14)), ((9, 8, 11), (4, 4, 5)), ((7, 6, 5), (12, 9, 3)), ((4, 4, 4), (4, 4, 4))):
+        x = torch.randn(2, 3, *si, generator=gen, **dbl)
+        assert float((R.resize_ref(x, so) - F.interpolate(x, size=so, mode="trilinear", align_corners=False)).abs().max()) < 1e-12
+    for si, f in (((9, 8, 11), 0.5), ((5, 6, 7), 2.0), ((8, 10, 6), 1.5)):
+        x = torch.randn(1, 3, *si, generator=gen, **dbl)
+        want = F.interpolate(x, scale_factor=f, mode="trilinear", align_corners=False)
+        assert float((R.resize_ref(x, want.shape[2:], (1 / f,) * 3) - want).abs().max()) < 1e-12
+
+
+def test_pyramid_comparison_rejects_a_one_element_error():
+    """the element-wise bound of the pyramid tests has power: moving one element of the reference by 1e-3 max|ref| - on a border plane, in
+    the last pixel block - is rejected at the tolerances those tests use"""
+    import pyramid_ref as R
+    gen = torch.Generator().manual_seed(3)
+    ref = torch.randn(2, 3, 6, 7, 8, generator=gen, dtype=torch.float64)
+    got = ref.float()
+    tol = 1e-5 * float(ref.abs().max())
+    assert R.ratio(got, ref, tol) <= 1.0
+    for idx in (0, ref.numel() - 1, 3 * 6 * 7 * 8 - 1):
+        assert R.ratio(got, R.perturbed(ref, idx), tol) > 1.0
+    assert R.ratio(got, ref, torch.full_like(ref, tol)) <= 1.0 and R.ratio(got, R.perturbed(ref, -1), torch.full_like(ref, tol)) > 1.0
+    bad = got.clone()
+    bad[-1, -1, -1, -1, -1] = float("nan")
+    assert R.ratio(bad, ref, tol) == float("inf")
