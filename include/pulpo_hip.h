@@ -72,7 +72,7 @@ int pulpo_conv3d_k3_fwd_wino2(const float* in, int64_t in_bs, int64_t in_ps, int
                               float slope, float* out, int64_t out_bs, int64_t out_ps, int64_t out_cs, float* stats,
                               float* scratch /*nullable if the query is 0*/, int B, int D, int H, int W, int K, int N, void* stream);
 /* 1 when the _wino2 entry points run the pipelined kernel (conv3d_wino2p.hip: double-buffered halo images, weights global -> registers) for a
- * channels-last 16-byte-aligned operand: K % 8 == 0 and D*H*W*in_ps*4 < 2^31.  Otherwise (and with PULPO_W2_PIPE=0) the round-2 kernel runs.
+ * channels-last 16-byte-aligned operand: K % 8 == 0 and D*H*W*in_ps*4 < 2^31.  Otherwise the round-2 kernel runs.
  * Same results either way (network_blocks.py:23). */
 int pulpo_conv3d_k3_wino2_pipelined(int D, int H, int W, int K, int64_t in_ps);
 /* The data-gradient convolution of a ConvUnit (in = dy of that unit, wp packed with dgrad = 1, N = the unit's input channels) with the
@@ -98,7 +98,7 @@ int pulpo_conv3d_k3_pack_weights_multi(const PulpoPackJob* jobs, int njobs, void
 /* weight gradient: dw[Cout][Cin][27] = sum_voxels in[v + tap - 1][ci] * dy[v][co]; scratch is overwritten */
 size_t pulpo_conv3d_k3_wgrad_scratch_floats(int Cin, int Cout);
 /* which weight-gradient kernel pulpo_conv3d_k3_wgrad runs for a shape: 3 = Winograd F(2x2x2,3x3x3) (even depths), 2 = Winograd F(2x2,3x3) in
- * (y, x), 1 = Winograd F(2,3) along x, 0 = direct.  vec != 0: both operands channels-last, 16-byte aligned, channel counts multiples of 4 (diagnostics / roofline accounting) */
+ * (y, x), 0 = direct.  (1, F(2,3) along x only, was retired.)  vec != 0: both operands channels-last, 16-byte aligned, channel counts multiples of 4 (diagnostics / roofline accounting) */
 int pulpo_conv3d_k3_wgrad_algo(int B, int D, int H, int W, int Cin, int Cout, int vec);
 /* accumulate: 0 dw = result, 1 dw += result, 2 DEFERRED - `scratch` must arrive all zero, keeps the packed sums [27][Cin][NPad] and dw (may
  * be NULL) is not touched: the caller finishes every deferred gradient of a backward pass with one pulpo_grad_finish_multi launch (which

@@ -11,11 +11,10 @@
 // tile issued back to back) and re-used by all 27 taps; the 27 weight slabs stream through a double-buffered LDS tile, prefetched
 // global->registers one tap ahead.
 // Volumes of >= 20^3 voxels (depth % 4 == 0) run the Winograd forms further down instead: F(2x2,3x3) in (y, x) for forward / data
-// gradient (conv3d_k3_wino2p_mfma / conv3d_k3_wino2_mfma) and F(2x2,3x3) / F(2,3) along x for the weight gradient
-// (conv3d_k3_wgrad_wino) - fewer matrix instructions, all arithmetic still fp32.
+// gradient (conv3d_k3_wino2p_mfma / conv3d_k3_wino2_mfma) and F(2x2,3x3) / F(2x2x2,3x3x3) for the weight gradient
+// (conv3d_wgrad_w2.hip) - fewer matrix instructions, all arithmetic still fp32.
 #include "conv_shared.h"
 #include "act_io.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -679,11 +678,9 @@ static int conv_fwd_impl(const float* in, int64_t in_bs, int64_t in_ps, int64_t 
     const bool vec = (in_cs == 1) && (in_ps % 4 == 0) && (in_bs % 4 == 0) && (K % 4 == 0) && (((uintptr_t)in & 15) == 0) && CH >= 16;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    // the persistent kernel of the 2- / 3-channel input layers (PULPO_CONV_SMALLK_PW=0: the one-tile-per-workgroup kernel, A/B switch)
-    static int spw = -1;
-    if (spw < 0) { const char* e = getenv("PULPO_CONV_SMALLK_PW"); spw = e ? atoi(e) : 1; }
+    // the persistent kernel of the 2- / 3-channel input layers where the shape allows it; the one-tile-per-workgroup kernel otherwise
     const long in_span = (((long)K - 1) * in_cs + ((long)D * H * W - 1) * in_ps + 1) * 4;
-    if (spw && CH <= 4 && tz == 4 && N % 32 == 0 && D % 4 == 0 && H % TY == 0 && W % TX == 0 && out_cs == 1 && out_ps % 4 == 0 && out_bs % 4 == 0 &&
+    if (CH <= 4 && tz == 4 && N % 32 == 0 && D % 4 == 0 && H % TY == 0 && W % TX == 0 && out_cs == 1 && out_ps % 4 == 0 && out_bs % 4 == 0 &&
         (((uintptr_t)out & 15) == 0) && in_span > 0 && in_span < (1L << 31) && in_cs >= 0 && in_ps >= 0 && (long)D * H * W * out_ps * 4 < (1L << 31)) {
         a.ncot = N / 32;
         const long nwork = (long)B * a.ntz * a.nty * a.ntx * a.ncot;
@@ -722,9 +719,6 @@ PULPO_API int pulpo_conv3d_k3_stat_tiles(int B, int D, int H, int W) {
 // reduction channels up, channels-last operands), 2 = Winograd F(2x2,3x3) in (y, x) (where it applies: 4x8x8-tiled volumes, > 4 reduction
 // channels; the 10^3 level - depth not a multiple of 4 - where the pipelined kernel runs it with split-K work items), 0 = direct implicit GEMM.  (1, F(2,3) along x only, was retired in round 3.)
 PULPO_API int pulpo_conv3d_k3_algo(int B, int D, int H, int W, int K, int N) {
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("PULPO_CONV_WINOGRAD"); force = e ? atoi(e) + 1 : 0; }     // unset: policy; 0 / 1: force off / on
-    if (force == 1) return 0;
     if (pulpo_conv::wino3_shape_ok(B, D, H, W, K, N)) return 3;
     return (K > 4 && (conv_tz(D, H, W) == 4 || pulpo_conv::wino2_ragged_depth_ok(B, D, H, W, K, N))) ? 2 : 0;
 }

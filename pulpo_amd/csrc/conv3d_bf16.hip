@@ -11,21 +11,6 @@
 #include "conv_shared.h"
 #include "act_io.h"
 
-#ifndef PULPO_PW_ABL
-#define PULPO_PW_ABL 0                                  // diagnostic builds of the persistent kernel (scripts/build_variant.sh): 1 no output stores, 2 no halo
-#endif                                                  // loads, 4 no MFMAs, 8 no halo LDS stores, 16 no weight loads / stores, 64 phase stamps
-#if PULPO_PW_ABL & 64
-// g_pw_stamps[block][8 k + p]: clock at phase p of the block's k-th tile (0 start, 1 halo in LDS, 2.. end of each weight group, then stores issued, statistics done)
-__device__ unsigned long long g_pw_stamps[512 * 128];
-#define PW_STAMP(k, p) do { __builtin_amdgcn_sched_barrier(0); if (threadIdx.x == 0 && (k) < 10) g_pw_stamps[blockIdx.x * 128 + 12 * (k) + (p)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-PULPO_API int pulpo_debug_read_stamps_pw(void* dst, size_t bytes) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_pw_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define PW_STAMP(k, p) do {} while (0)
-#endif
-
-#include <stdlib.h>
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
@@ -35,13 +20,10 @@ namespace {
 using pulpo_conv::TY; using pulpo_conv::TX; using pulpo_conv::HY; using pulpo_conv::HX;
 using pulpo_conv::npad;
 
-// z extent of this kernel's voxel tile (its own policy: the 4x8x8 tile pays from 64^3 up; pulpo_conv3d_k3_fwd_bf16_stat_tiles follows it)
-inline long conv_tz4_min_voxels() {
-    static long v = -1;
-    if (v < 0) { const char* e = getenv("PULPO_CONV_BF16_TZ4_MIN"); v = e ? atol(e) : 40L * 40 * 40; }     // (round 5: 40^3 - config 4 14.51 -> 14.38 ms per step; 64^3 before)
-    return v;
-}
-inline int conv_tz(int D, int H, int W) { return (D % 4 == 0 && (long)D * H * W >= conv_tz4_min_voxels()) ? 4 : 2; }
+// z extent of this kernel's voxel tile (its own policy; pulpo_conv3d_k3_fwd_bf16_stat_tiles follows it): the 4x8x8 tile pays from 40^3 voxels up
+// (round 5: config 4 14.51 -> 14.38 ms per step against the 64^3 threshold before)
+constexpr long TZ4_MIN_VOXELS = 40L * 40 * 40;
+inline int conv_tz(int D, int H, int W) { return (D % 4 == 0 && (long)D * H * W >= TZ4_MIN_VOXELS) ? 4 : 2; }
 
 constexpr int CH = 32;            // channels per staged chunk = two K=16 MFMA steps
 constexpr int CP = CH + 8;        // LDS row length in bf16 elements
@@ -146,10 +128,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16(ConvArgsH a) {
     constexpr int NN = NT / 32;
     constexpr int MT = TZv / 2;
     constexpr int HV = (TZv + 2) * HY * HX;
-#ifndef PULPO_BF16_TPB32
-#define PULPO_BF16_TPB32 1
-#endif
-    constexpr int TPB = (TZv == 4 && (NT == 64 || PULPO_BF16_TPB32 == 3)) ? 3 : 1;  // taps (one dx row) per barrier: 3 on the big 64-cout tiles = 24 MFMAs per wave between
+    constexpr int TPB = (TZv == 4 && NT == 64) ? 3 : 1;  // taps (one dx row) per barrier: 3 on the big 64-cout tiles = 24 MFMAs per wave between
                                                           // barriers (on the 32-cout tiles the extra registers cost the third wave per SIMD: measured slower)
     constexpr int WSLAB = TPB * NT * CP;                // bf16 elements of one LDS weight slab set [TPB][NT][CP]
     extern __shared__ __attribute__((aligned(16))) uint16_t smem_h[];
@@ -399,10 +378,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
         hlds[u] = hv * CH + ((q ^ (hy & 3)) << 3);
     }
     uint4 hreg[PW_HP];
-    if (PULPO_PW_ABL & 2) {
-#pragma unroll
-        for (int u = 0; u < PW_HP; ++u) hreg[u] = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-    }
     // which halo planes / rows / columns of a tile lie inside the volume, as one mask in hbit's layout (a piece is inside when all three of
     // its bits are set); outside pieces load from beyond num_records: zeros
     auto inside_mask = [&](const Tile& t) {
@@ -418,13 +393,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
         const unsigned origin = (unsigned)(((t.z0 - 1) * a.H + (t.y0 - 1)) * a.W + (t.x0 - 1)) * ps_bytes;        // modulo 2^32
         const unsigned mask = inside_mask(t);
         const int c0b = chunk * CH * 2;
-        if (PULPO_PW_ABL & 2) return;
 #pragma unroll
         for (int u = u0; u < u1; ++u)
             hreg[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((mask & hbit[u]) == hbit[u] ? origin + hrel[u] : PW_OOB), c0b, 0));
     };
     auto store_halo = [&]() {
-        if (PULPO_PW_ABL & 8) return;
 #pragma unroll
         for (int u = 0; u < PW_HP; ++u)
             if (u + 1 < PW_HP || tid < PW_HV * 4 - (PW_HP - 1) * 256) *reinterpret_cast<uint4*>(xs + hlds[u]) = hreg[u];
@@ -450,7 +423,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
         return reinterpret_cast<uint4*>(ws + buf * WGE + (tapl * NT + n) * CH + ((q ^ ((n >> 2) & 3)) << 3));
     };
     auto load_wg = [&](int co0, int chunk, int g) {
-        if (PULPO_PW_ABL & 16) return;
         const int soff = ((chunk * 27 + g * TPB) * a.NPad + co0) * CH * 2;
         if (w_has(0)) wr0 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wv0, soff, 0));
         if (w_has(1)) wr1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wv1, soff, 0));
@@ -459,7 +431,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
         if (w_has(4)) wr4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wv4, soff, 0));
     };
     auto store_wg = [&](int buf) {
-        if (PULPO_PW_ABL & 16) return;
         if (w_has(0)) *w_dst(buf, 0) = wr0;
         if (w_has(1)) *w_dst(buf, 1) = wr1;
         if (w_has(2)) *w_dst(buf, 2) = wr2;
@@ -491,7 +462,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
     store_wg(0);
     store_halo();
     int buf = 0;
-    [[maybe_unused]] int tile_no = 0;
     int pend_tile = -1, pend_co0 = 0;                   // tile whose partial statistics wait in `red`
     auto flush_stats = [&]() {                          // (behind a barrier that followed the writes of `red`; the next writes are four barriers away)
         if (a.stats != nullptr && pend_tile >= 0 && tid < 2 * NT) {
@@ -503,7 +473,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
     };
 
     for (;;) {
-        PW_STAMP(tile_no, 0);
         const int next_work = work + nwg;
         const bool has_next = next_work < nwork;
         const Tile nxt = has_next ? describe(next_work) : cur;      // (after the last tile: its own halo again, into registers nobody stores)
@@ -531,7 +500,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
         do {                                            // (at least one chunk: a zero-trip path would make the compiler's vmcnt bookkeeping drain
                                                         //  every load in flight at the epilogue's first use of a constant loaded above)
             __syncthreads();                            // the chunk's halo and its first weight group are in place
-            PW_STAMP(tile_no, 1);
             if (chunk == 0) { flush_stats(); pend_tile = -1; }
             const bool lastc = chunk + 1 == nchunk;
             const Tile& ht = lastc ? nxt : cur;         // whose halo the registers take next
@@ -568,21 +536,17 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
                     for (int n = 0; n < NN; ++n)
 #pragma unroll
                         for (int m = 0; m < MT; ++m) {
-                            if (PULPO_PW_ABL & 4) { acc[m][n][0] += (float)av[st % SLOTS][m][0] * (float)bv[st % SLOTS][n][0]; continue; }
                             acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[st % SLOTS][m], bv[st % SLOTS][n], acc[m][n], 0, 0, 0);
                         }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                PW_STAMP(tile_no, 8 + g);
                 store_wg(buf ^ 1);                      // (the other buffer was last read a group ago: every wave has passed that barrier)
                 __syncthreads();
-                PW_STAMP(tile_no, 2 + g);
                 buf ^= 1;
             }
             // the registers' halo (the next chunk's, or the next tile's first) goes to LDS as soon as every wave has left this one: in front
             // of the epilogue, whose arithmetic and stores then cover the writes and the wait for the last slice
             store_halo();
-            PW_STAMP(tile_no, 7);
         } while (++chunk < nchunk);
 
         // ---- epilogue: bias, optional eval-mode BatchNorm + LeakyReLU, rounding, stores, partial statistics of the tensor as stored.
@@ -629,18 +593,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
                     xw[((r & 3) + 8 * (r >> 2)) * 16] = __builtin_amdgcn_perm(nbh, h, psel);
                 }
                 const uint4 p0 = xr[0], p1 = xr[64];
-                if (!(PULPO_PW_ABL & 1) || p0.x == 0x12345678u) {
-                    const unsigned soff = (unsigned)(m * 4) * row_b + (unsigned)n * 64u;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, p0), ors, (int)st_off, (int)soff, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, p1), ors, (int)st_off, (int)(soff + 2 * row_b), 0);
-                }
-                if (n == 0 && m == 0) PW_STAMP(tile_no, 11);
+                const unsigned soff = (unsigned)(m * 4) * row_b + (unsigned)n * 64u;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, p0), ors, (int)st_off, (int)soff, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, p1), ors, (int)st_off, (int)(soff + 2 * row_b), 0);
             }
             const float s = s2.x + s2.y, q = q2.x + q2.y;
             ssum[n] = s + __shfl_xor(s, 32, 64);
             ssq[n] = q + __shfl_xor(q, 32, 64);
         }
-        PW_STAMP(tile_no, 5);
         // the waves' partial sums go to LDS; they are added and written behind the NEXT barrier every wave passes anyway (the next tile's
         // "halo in place", or the one after the loop) - no barrier of their own
         if (a.stats != nullptr && lane < 32) {
@@ -651,8 +611,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
             }
         }
         pend_tile = cur.tile_lin; pend_co0 = cur.co0;
-        PW_STAMP(tile_no, 6);
-        ++tile_no;
         if (!has_next) break;
         work = next_work;
         cur = nxt;
@@ -964,7 +922,7 @@ int conv_ksplit_bf16(int B, int D, int H, int W, int K, int N) {
 
 template <int NT, bool VEC, int TZv, typename T>
 int launch_bf16(const ConvArgsH& a, int nblk, hipStream_t st) {
-    constexpr size_t lds = (size_t)((TZv + 2) * HY * HX * CP + 2 * ((TZv == 4 && (NT == 64 || PULPO_BF16_TPB32 == 3)) ? 3 : 1) * NT * CP) * sizeof(uint16_t);
+    constexpr size_t lds = (size_t)((TZv + 2) * HY * HX * CP + 2 * ((TZv == 4 && NT == 64) ? 3 : 1) * NT * CP) * sizeof(uint16_t);
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_k3_mfma_bf16<NT, VEC, TZv, T>),
@@ -989,15 +947,6 @@ int launch_bf16_pw(const ConvArgsH& a, long nwork, hipStream_t st) {
     const int nwg = (int)std::min<long>(nwork, 512);    // persistent workgroups: two per CU
     hipLaunchKernelGGL((conv3d_k3_mfma_bf16_pw<NN, TPB>), dim3(nwg), dim3(256), lds, st, a);
     return pulpo::check_launch("conv3d_k3_mfma_bf16_pw");
-}
-
-// PULPO_CONV_BF16_PW (A/B switch): 0 = never, 1 = the 32-cout tiles only, 2 (default) = the 64-cout tiles as well.
-// Measured on one MI355X (scripts/pw_ab.sh), modes 0 / 1 / 2: config 4 step 61.7 / 65.4 / 67.3 pairs/s, config 5 step 38.1 / 40.4 / 41.6,
-// config 4 inference 190 / 211 / 222.
-int bf16_pw_mode() {
-    static int mode = -1;
-    if (mode < 0) { const char* e = getenv("PULPO_CONV_BF16_PW"); mode = e ? atoi(e) : 2; }
-    return mode;
 }
 
 }  // namespace
@@ -1055,11 +1004,12 @@ static int conv_fwd_bf16_impl(const void* in, int64_t in_bs, int64_t in_ps, int6
                           "conv3d_k3_fwd_bf16: bf16 channels-last output must be 4-byte aligned with even strides");
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    // the persistent kernel: bf16-stored activations in 16-byte pieces, whole 32-channel chunks, whole 4 x 8 x 8 tiles, whole cout tiles
+    // the persistent kernel: bf16-stored activations in 16-byte pieces, whole 32-channel chunks, whole 4 x 8 x 8 tiles, whole cout tiles.
+    // On the 32- and the 64-cout tiles alike: measured on one MI355X with the persistent kernel on neither / the 32-cout tiles only / both,
+    // config 4 step 61.7 / 65.4 / 67.3 pairs/s, config 5 step 38.1 / 40.4 / 41.6, config 4 inference 190 / 211 / 222.
     const bool pw_ok = dt == 1 && vec && tz == 4 && a.ksplit == 1 && K % CH == 0 && N % NT == 0 && D % 4 == 0 && H % TY == 0 && W % TX == 0 &&
                        (long)D * H * W * in_ps * 2 < (1L << 31) && out_cs == 1 && (long)D * H * W * out_ps * 2 < (1L << 31) &&
-                       out_ps % 8 == 0 && out_bs % 8 == 0 && (((uintptr_t)out & 15) == 0) &&
-                       bf16_pw_mode() >= (NT == 64 ? 2 : 1);
+                       out_ps % 8 == 0 && out_bs % 8 == 0 && (((uintptr_t)out & 15) == 0);
     if (pw_ok) return NT == 64 ? launch_bf16_pw<2, 3>(a, nblk_l, st) : launch_bf16_pw<1, 9>(a, nblk_l, st);
 #define PULPO_BF16(NTV, VECV, TT) (tz == 4 ? launch_bf16<NTV, VECV, 4, TT>(a, nblk, st) : launch_bf16<NTV, VECV, 2, TT>(a, nblk, st))
 #define PULPO_BF16_T(TT)                                                                          \
@@ -1128,10 +1078,8 @@ static int wgrad_bf16_impl(const void* in, int64_t in_bs, int64_t in_ps, int64_t
     // other multiplies) take 484 of a SIMD's 512, and no kernel of the main stream starts on a CU until a workgroup retires - every
     // BatchNorm-backward launch of the step then waited ~100 us for one (colsum_slices 109 instead of 8 us: 3 ms per bf16 step).  Measured
     // per 160^3 bf16 step for 512 / 448 / 384 / 320 / 256 / 192 / 128 workgroups: 23.1 / 20.3 / 20.3 / 20.2 / 20.3 / 21.0 / 24.4 ms.
-    // PULPO_WGRAD_BF16_WGS overrides (A/B switch).
-    static int wgs = -1;
-    if (wgs < 0) { const char* e = getenv("PULPO_WGRAD_BF16_WGS"); wgs = e ? atoi(e) : 256; }
-    a.nsplit = std::min(std::max(1, wgs / npair), ntile);
+    constexpr int WGS = 256;
+    a.nsplit = std::min(std::max(1, WGS / npair), ntile);
     if (slabs) a.nsplit = std::min(a.nsplit, nslab);
     const bool deferred = accumulate == 2;                 // see pulpo_conv3d_k3_wgrad
     if (!deferred) {
@@ -1152,14 +1100,10 @@ static int wgrad_bf16_impl(const void* in, int64_t in_bs, int64_t in_ps, int64_t
     const int ntw = (nrt_max + 3) / 4;
     constexpr size_t lds = (size_t)(WHV + WMV) * CP * sizeof(uint16_t);
     const int nblk = npair * a.nsplit;
-    // transposing LDS reads where every 16-lane group's rows are 16 channels of one tap (PULPO_WGRAD_BF16_TR=0: the 2-byte gathers, A/B switch)
-    static int tr_on = -1;
-    if (tr_on < 0) { const char* e = getenv("PULPO_WGRAD_BF16_TR"); tr_on = e ? atoi(e) : 1; }
-    const bool tr = tr_on && Cin % 16 == 0;
-    // register-prefetched staging (PULPO_WGRAD_BF16_PF=0: the staged form, A/B switch): bf16 tensors in 16-byte pieces below 2 GB, tiles whole in x / y
-    static int pf_on = -1;
-    if (pf_on < 0) { const char* e = getenv("PULPO_WGRAD_BF16_PF"); pf_on = e ? atoi(e) : 1; }
-    const bool pf = pf_on && tr && dt == 1 && vec && H % TY == 0 && W % TX == 0 && (long)D * H * W * in_ps * 2 < (1L << 31) &&
+    // transposing LDS reads where every 16-lane group's rows are 16 channels of one tap (else the 2-byte gathers)
+    const bool tr = Cin % 16 == 0;
+    // register-prefetched staging (else the staged form): bf16 tensors in 16-byte pieces below 2 GB, tiles whole in x / y
+    const bool pf = tr && dt == 1 && vec && H % TY == 0 && W % TX == 0 && (long)D * H * W * in_ps * 2 < (1L << 31) &&
                     (long)D * H * W * dy_ps * 2 < (1L << 31);
 #define PULPO_WGRAD_H(NTWV, VECV, TT)                                                                                             \
     do {                                                                                                                            \

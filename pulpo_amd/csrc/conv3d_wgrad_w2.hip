@@ -21,14 +21,6 @@
 // ranges of the linearised (column, z) plane steps, so the load balance is exact to one plane.  Flush: G^T M G (in-lane over the wave's px,
 // across the waves through LDS), three float atomics per (dz, ci, co) triple into the packed scratch shared with the other wgrad kernels.
 #include "conv_shared.h"
-
-#ifndef PULPO_ABL
-#define PULPO_ABL 0          // diagnostic builds (scripts/ablate.py): 21 no matrix instructions, 22 no staging writes, 23 no global loads, 24 no barrier per plane step
-#endif
-#ifndef PULPO_ABLX
-#define PULPO_ABLX 0         // diagnostic builds of the eight-wave kernel (bit mask): 1 no barrier per plane step, 2 no staging writes, 4 no global loads, 32 / 64 (F(2x2x2) kernel) input / gradient taps from one 64 KB window,
-#endif                       // 8 no flush, 16 no operand combinations
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -215,13 +207,11 @@ __global__ __launch_bounds__(256, 1) void conv3d_k3_wgrad_w2(Wgrad2Args a) {
         }
 #pragma unroll 1
         for (int j = zs; j < ze; ++j) {
-#if PULPO_ABL != 24
             __syncthreads();                              // staged planes visible; everybody has finished the previous iteration's reads
-#endif
             const int xs_slot = (j + 3) & 3, es = j & 1;
             // eight groups (g, px) of 12 MFMAs; the eight ds_read_b128 of group k + 1 are requested before the MFMAs of group k are issued
             // (two register sets: with one wave per SIMD nothing else hides the LDS round trip).
-            // Measured (round 2, scripts/ablate.py w2_*): with ONE wave per SIMD a wave's own MFMAs and its other instructions do not overlap -
+            // Measured (round 2, ablation builds): with ONE wave per SIMD a wave's own MFMAs and its other instructions do not overlap -
             // the kernel takes matrix time + everything-else time (0.73 + 0.50 ms for 32->32 at 160^3; 12 bare MFMAs 724 clocks, the same 12
             // with 8 LDS reads and 20 VALU operations slotted one by one between them 896).  A version with every piece of side work pinned
             // between two MFMAs (volatile-asm arithmetic, branch-free loads and staging so that the loop stays one basic block) gained 3 % for
@@ -253,26 +243,18 @@ __global__ __launch_bounds__(256, 1) void conv3d_k3_wgrad_w2(Wgrad2Args a) {
                     const float4 pa_ = av[set][dz], pb_ = bv[set][dz];
                     const float v4[4] = {fmaf(sa, pb_.x, pa_.x), fmaf(sa, pb_.y, pa_.y), fmaf(sa, pb_.z, pa_.z), fmaf(sa, pb_.w, pa_.w)};
 #pragma unroll
-#if PULPO_ABL == 21
-                    for (int s_ = 0; s_ < 4; ++s_) acc[px][dz][s_] = fmaf(v4[s_], ev[s_], acc[px][dz][s_]);
-#else
                     for (int s_ = 0; s_ < 4; ++s_) acc[px][dz] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4[s_], ev[s_], acc[px][dz], 0, 0, 0);
-#endif
                     if (dz == 0 && gi < 4) {
                         // behind the group's first MFMAs: the registers (planes j + 2 / j + 1, requested half an iteration ago) are transformed
                         // and written, one point per group; after the fourth they are free and the next planes are requested, which leaves
                         // those loads groups 4..7 and the barrier to land
                         __builtin_amdgcn_sched_barrier(0);
                         if (gi == 0) touch_raw();
-#if PULPO_ABL != 22
                         stage_part(gi, xs_slot, es ^ 1);
-#endif
-#if PULPO_ABL != 23
                         if (gi == 3) {
                             issue_x(j + 3);
                             issue_e(j + 2);
                         }
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -490,9 +472,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_w2x(Wgrad2Args a) {
         }
 #pragma unroll 1
         for (int j = zs; j < ze; ++j) {
-#if !(PULPO_ABLX & 1)
             __syncthreads();                              // staged planes visible; everybody has finished the previous iteration's reads
-#endif
             const int xs_slot = (j + 3) & 3, es = j & 1;
             // four groups (g, pl) of 12 MFMAs, ONE register set of operand rows (the other wave of the SIMD covers the LDS round trip - see
             // profiles/r2_mfma_probe.md - and the registers saved keep two such waves at 2 x 208).  The planes fetched during the previous step
@@ -531,26 +511,18 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_w2x(Wgrad2Args a) {
 #pragma unroll
                 for (int dz = 0; dz < 3; ++dz) {
 #pragma unroll
-#if PULPO_ABLX & 16
-                    for (int s_ = 0; s_ < 4; ++s_) acc[pl][dz] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[dz].x, e0.x, acc[pl][dz], 0, 0, 0);      // (no combinations)
-#else
                     for (int s_ = 0; s_ < 4; ++s_) acc[pl][dz] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[dz][s_], ev[s_], acc[pl][dz], 0, 0, 0);
-#endif
                     if (dz == 0 && gi < 2) {
                         __builtin_amdgcn_sched_barrier(0);
                         if (gi == 0) touch_raw();
-#if !(PULPO_ABLX & 2)
                         write_x(2 * gi, xs_slot);
                         write_x(2 * gi + 1, xs_slot);
                         write_e(2 * gi, es ^ 1);
                         write_e(2 * gi + 1, es ^ 1);
-#endif
-#if !(PULPO_ABLX & 4)
                         if (gi == 1) {
                             issue_x(j + 3);
                             issue_e(j + 2);
                         }
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -561,9 +533,6 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_w2x(Wgrad2Args a) {
         __syncthreads();                                  // (the next segment's warm-up overwrites the rings)
     }
 
-#if PULPO_ABLX & 8
-    if (acc[0][0][0] + acc[1][1][3] + acc[0][2][7] + acc[1][0][9] + acc[0][1][11] + acc[1][2][15] != 12345.678f) return;      // (no flush)
-#endif
     // ---- flush: dw[dz][ky][kx] = sum_py sum_px G[py][ky] G[px][kx] M[py][px][dz], G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]].  The px sum
     // is in-lane (this wave's two px), the (py, px-half) sum meets in LDS, one dz at a time: X[wave][kx][r][lane] (8 x 3 x 1024 floats = 96 KB)
     __syncthreads();
@@ -619,9 +588,6 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_w2x(Wgrad2Args a) {
 constexpr int W3G_EX = 4 * 4 * W2G_ESLOT;                          // [px][4 slots][32 co][36]
 constexpr size_t W3G_LDS = (size_t)(W2G_VX + W3G_EX) * sizeof(float);     // 163,840 bytes
 
-#ifndef PULPO_WG3_SKEW
-#define PULPO_WG3_SKEW 1         // 1: the two waves of a SIMD (w, w + 4) stage their planes behind DIFFERENT groups of a half step (see the kernel below)
-#endif
 
 // SG: the group of a half step behind whose first MFMAs a wave starts transforming / writing the fetched planes (groups SG, SG + 1; the next planes'
 // loads are issued in group SG + 1)
@@ -699,7 +665,6 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
         for (int t4 = 0; t4 < 4; ++t4) {
             const int gx = x0 - 1 + 2 * x_xb + t4;
             x_off[t4] = (xrow && (unsigned)gx < (unsigned)a.W) ? (unsigned)((long)((ci0 + 4 * x_q) >> 3) * a.in_kb + (gy * a.W + gx) * (int)a.in_ps + ((4 * x_q) & 7)) * 4u : OOB;
-            if ((PULPO_ABLX & 32) && x_off[t4] != OOB) x_off[t4] &= 0xFFF0u;       // (diagnostic: every input tap from one 64 KB window - cache hits)
         }
         const int ey = y0 + e_y;
         const bool erow = e_item && e_cok && ey < a.H;
@@ -707,7 +672,6 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
         for (int t2 = 0; t2 < 2; ++t2) {
             const int gx = x0 + 2 * e_xb + t2;
             e_off[t2] = (erow && gx < a.W) ? (unsigned)((long)((co0 + 4 * e_q) >> 3) * a.go_kb + (ey * a.W + gx) * (int)a.go_ps + ((4 * e_q) & 7)) * 4u : OOB;
-            if ((PULPO_ABLX & 64) && e_off[t2] != OOB) e_off[t2] &= 0xFFF0u;       // (diagnostic: the same for the gradient operand)
         }
     };
     const unsigned x_plane = (unsigned)((long)a.H * a.W * a.in_ps * 4), e_plane = (unsigned)((long)a.H * a.W * a.go_ps * 4);
@@ -715,14 +679,14 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
     float4 xr[4], er[2];                                  // raw registers of the plane being fetched
     auto issue_x = [&](int zp) {                          // input plane zp (zeros outside the volume)
         const unsigned zmask = (unsigned)zp < (unsigned)a.D ? 0u : OOB;          // (wave-uniform)
-        const unsigned zo = (zmask | (unsigned)(PULPO_ABLX & 32)) ? 0u : (unsigned)zp * x_plane;
+        const unsigned zo = zmask ? 0u : (unsigned)zp * x_plane;
 #pragma unroll
         for (int t4 = 0; t4 < 4; ++t4)
             xr[t4] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, (int)(x_off[t4] | zmask), (int)zo, 0));
     };
     auto issue_e = [&](int zp) {                          // output-gradient plane zp
         const unsigned zmask = (unsigned)zp < (unsigned)a.D ? 0u : OOB;
-        const unsigned zo = (zmask | (unsigned)(PULPO_ABLX & 64)) ? 0u : (unsigned)zp * e_plane;
+        const unsigned zo = zmask ? 0u : (unsigned)zp * e_plane;
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2)
             er[t2] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(e_rs, (int)(e_off[t2] | zmask), (int)zo, 0));
@@ -777,10 +741,6 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
     const float* vb = VX + irow * W2G_VROW + (2 * kk + tb) * 4;
     const float* ea = EX + irow * W2G_EROW + (2 * kk) * 4;
 
-#ifndef PULPO_W3_SETPRIO
-#define PULPO_W3_SETPRIO 0       // 1: waves 4-7 raised for good, 2: the partners of a SIMD (w, w + 4) alternate per group (conv3d_wino3.hip)
-#endif
-    if (PULPO_W3_SETPRIO == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);       // (the second-dispatched half loses every issue arbitration otherwise: MI355X_MICROARCH.md)
     // ---- main loop: column segments of pair steps [Js, Je) of this split's range, i.e. half steps h = 2 Js .. 2 Je - 1, each segment entered
     // through three warm-up half steps (stage only).  Half step h: barrier; its 32 MFMAs; the registers (input plane h + 2, gradient plane
     // h + 2) are transformed and written into the free slots; the loads of planes h + 3 are issued.
@@ -810,16 +770,13 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
         auto half_step = [&](int h, auto hm_tag) {
             constexpr int HM = decltype(hm_tag)::value;
             constexpr bool HB = (HM & 1) != 0;
-#if !(PULPO_ABLX & 1)
             __syncthreads();                              // staged planes visible; everybody has finished the previous half step's reads
-#endif
             constexpr int xs_slot = (HM + 3) & 3, ew_slot = (HM + 2) & 3;
             constexpr int d0s = (HB ? HM - 1 : HM) & 3, d1s = (HB ? HM : HM + 1) & 3;      // slots of the pair's gradient planes 2 J, 2 J + 1
             float4 av[3], bv[3], e0[2], e1[2];
 #pragma unroll
             for (int gi = 0; gi < 4; ++gi) {
                 const int g = gi >> 1, px = 2 * pxh + (gi & 1), pl = gi & 1;
-                if (PULPO_W3_SETPRIO == 2) { if (((gi + pxh) & 1) != 0) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
                 const float* eb0 = ea + (px * 4 + d0s) * W2G_ESLOT + g * 16;
                 const float* eb1 = ea + (px * 4 + d1s) * W2G_ESLOT + g * 16;
                 e0[0] = *reinterpret_cast<const float4*>(eb0 + 4 * ea_); e1[0] = *reinterpret_cast<const float4*>(eb0 + 4 * eb_);
@@ -859,33 +816,21 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
                 for (int s_ = 0; s_ < 4; ++s_) {
                     acc[pl][PZA] = __builtin_amdgcn_mfma_f32_32x32x2f32(va4[s_], ea4[s_], acc[pl][PZA], 0, 0, 0);
                     acc[pl][PZB] = __builtin_amdgcn_mfma_f32_32x32x2f32(vb4[s_], eb4[s_], acc[pl][PZB], 0, 0, 0);
-#ifndef PULPO_W3_STAGE
-#define PULPO_W3_STAGE 0                                  // 0: two points behind the first MFMAs of groups 0 and 1 (the (y, x) kernel's placement), 1: all four in group 0
-#endif
-                    if (s_ == 0 && gi >= SG && gi < SG + (PULPO_W3_STAGE ? 1 : 2)) {
+                    if (s_ == 0 && gi >= SG && gi < SG + 2) {
                         // the planes fetched during the previous half step are transformed and written behind the group's first MFMAs; their
                         // registers are then free and the next planes are requested.  (All four points in ONE group - 30 instead of 24 of the half
                         // step's 32 MFMAs for the loads to land - measured 1.5 - 2 % SLOWER although a build without any loads is 14 - 18 % faster:
                         // what the loads cost is not their latency.)
                         __builtin_amdgcn_sched_barrier(0);
                         if (gi == SG) touch_raw();
-#if !(PULPO_ABLX & 2)
-                        if (PULPO_W3_STAGE) {
-                            write_x(0, xs_slot); write_x(1, xs_slot); write_x(2, xs_slot); write_x(3, xs_slot);
-                            write_e(0, ew_slot); write_e(1, ew_slot); write_e(2, ew_slot); write_e(3, ew_slot);
-                        } else {
-                            write_x(2 * (gi - SG), xs_slot);
-                            write_x(2 * (gi - SG) + 1, xs_slot);
-                            write_e(2 * (gi - SG), ew_slot);
-                            write_e(2 * (gi - SG) + 1, ew_slot);
-                        }
-#endif
-#if !(PULPO_ABLX & 4)
-                        if (gi == SG + (PULPO_W3_STAGE ? 0 : 1)) {
+                        write_x(2 * (gi - SG), xs_slot);
+                        write_x(2 * (gi - SG) + 1, xs_slot);
+                        write_e(2 * (gi - SG), ew_slot);
+                        write_e(2 * (gi - SG) + 1, ew_slot);
+                        if (gi == SG + 1) {
                             issue_x(h + 3);
                             issue_e(h + 3);
                         }
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -908,9 +853,6 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
         __syncthreads();                                  // (the next segment's warm-up overwrites the rings)
     }
 
-#if PULPO_ABLX & 8
-    if (acc[0][0][0] + acc[1][1][3] + acc[0][2][7] + acc[1][0][9] + acc[0][1][11] + acc[1][2][15] != 12345.678f) return;      // (no flush)
-#endif
     // ---- flush: first the z axis in-lane, M[dz] = sum_pz G[pz][dz] acc[pz] (G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]); then, as in the
     // (y, x) kernel, dw[dz][ky][kx] = sum_py sum_px G[py][ky] G[px][kx] M[py][px][dz]: the px sum in-lane (this wave's two px), the (py, px-half)
     // sum through LDS, one dz at a time: X[wave][kx][r][lane] (8 x 3 x 1024 floats = 96 KB)
@@ -957,7 +899,7 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
 // step, their SIMD partners 4-7 behind groups 2 / 3 - one wave's staging arithmetic and LDS writes fall into the other's matrix instructions.
 template <int DUMMY>
 __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_w3x(Wgrad2Args a) {
-    if (PULPO_WG3_SKEW && __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) != 0) wgrad_w3x_body<2>(a);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 8) != 0) wgrad_w3x_body<2>(a);
     else wgrad_w3x_body<0>(a);
 }
 
@@ -965,12 +907,8 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_w3x(Wgrad2Args a) {
 
 namespace pulpo_conv {
 
-// PULPO_WGRAD_W3=0: the (y, x) kernel for every shape (A/B switch).  Default: the F(2x2x2,3x3x3) kernel where the depth is even
-bool wgrad_w3_depth_ok(int D) {
-    static int w3 = -1;
-    if (w3 < 0) { const char* e = getenv("PULPO_WGRAD_W3"); w3 = e ? atoi(e) : 1; }
-    return w3 && D % 2 == 0 && D >= 4;
-}
+// the F(2x2x2,3x3x3) kernel where the depth is even, else the (y, x) kernel
+bool wgrad_w3_depth_ok(int D) { return D % 2 == 0 && D >= 4; }
 
 // launched by pulpo_conv3d_k3_wgrad (conv3d_wgrad.hip) for channels-last operands on large volumes; scratch must be zeroed by the caller
 int launch_wgrad_w2(const float* in, long in_bs, long in_ps, const float* go, long go_bs, long go_ps, float* scratch, int B, int D, int H, int W,
@@ -1018,23 +956,20 @@ int launch_wgrad_w2(const float* in, long in_bs, long in_ps, const float* go, lo
         }
         // workgroups: one per CU, each with the CU's whole LDS and 2 x 234 of a SIMD's 512 registers - on a CU it holds, no kernel of the main
         // stream that needs LDS (the BatchNorm finalize / column-sum kernels between two data-gradient launches) starts until it retires.
-        // PULPO_WGRAD_W3_WGS (default 256) leaves CUs free for them.
-        static int wgs3 = -1;
-        if (wgs3 < 0) { const char* e = getenv("PULPO_WGRAD_W3_WGS"); wgs3 = e ? atoi(e) : 256; }
+        // 256 workgroups leave CUs free for them.
+        constexpr int WGS3 = 256;
         const long nstep3 = (long)B * a.nty * a.ntx * (D / 2);
-        a.nsplit = (int)std::min<long>(std::max(1, wgs3 / npair), nstep3);
+        a.nsplit = (int)std::min<long>(std::max(1, WGS3 / npair), nstep3);
         if (slabs) a.nsplit = std::min(a.nsplit, nslab);
         if (int rc = use_slabs(a.nsplit)) return rc;
         hipLaunchKernelGGL((conv3d_k3_wgrad_w3x<0>), dim3(npair * a.nsplit), dim3(512), W3G_LDS, st, a);
         return pulpo::check_launch("conv3d_k3_wgrad_w3x");
     }
-    // PULPO_WGRAD_WAVES8=0: the four-wave build (one wave per SIMD, 405 registers).  Default: eight waves, two per SIMD at 2 x 198 registers -
-    // 11 % faster alone (step-weighted 9.24 against 10.26 ms) and 0.6 ms per 160^3 training step (37.5 -> 36.9 ms)
-    static int waves8 = -1;
-    if (waves8 < 0) { const char* e = getenv("PULPO_WGRAD_WAVES8"); waves8 = e ? atoi(e) : 1; }
-    // (the eight-wave kernel addresses its operands with 32-bit buffer offsets: volumes of 2 GiB and more take the four-wave kernel)
+    // eight waves, two per SIMD at 2 x 198 registers, against the four-wave kernel's one per SIMD at 405 registers: 11 % faster alone
+    // (step-weighted 9.24 against 10.26 ms) and 0.6 ms per 160^3 training step (37.5 -> 36.9 ms).  (The eight-wave kernel addresses its
+    // operands with 32-bit buffer offsets: volumes of 2 GiB and more take the four-wave kernel.)
     const bool small = (long)D * H * W * in_ps * 4 < (1L << 31) && (long)D * H * W * go_ps * 4 < (1L << 31);
-    if (waves8 && small) {
+    if (small) {
         static bool attr8 = false;
         if (!attr8) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_k3_wgrad_w2x<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)W2G_LDS);

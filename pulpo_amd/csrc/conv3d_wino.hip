@@ -6,22 +6,6 @@
 #include "conv_shared.h"
 #include "../../include/pulpo_hip.h"
 #include "wino3_pack.h"
-#include <stdlib.h>
-
-
-#ifndef PULPO_ABL
-#define PULPO_ABL 0          // diagnostic builds (scripts/ablate.py): 9 = in-kernel stamps of the (y, x) Winograd kernel
-#endif
-#if PULPO_ABL == 9
-// g_stamps[block][0] = HW_REG_HW_ID, [1] = HW_REG_XCC_ID, [2] = start clock, [3 + 2k] / [4 + 2k] = main-loop end / tile end of the block's k-th tile
-__device__ unsigned long long g_stamps[512 * 80];
-#define STAMP(slot, val) do { if (threadIdx.x == 0 && (slot) < 80) g_stamps[blockIdx.x * 80 + (slot)] = (val); } while (0)
-PULPO_API int pulpo_debug_read_stamps(void* dst, size_t bytes) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define STAMP(slot, val) do {} while (0)
-#endif
 
 namespace {
 
@@ -102,7 +86,7 @@ __device__ __forceinline__ void w2_stage_scalar(float* xs, const float* __restri
 // of the 4x8x8 tile (two MFMA row tiles of 2 z-planes x 4 x 4 blocks).  The x inverse transform is in-lane; the y inverse transform sums
 // over the four waves through LDS, one row tile at a time.
 //
-// What the phase stamps of a diagnostic build showed (scripts/ablate.py, scripts/stamps.py; 32->32 @160^3: 84k clocks per tile of which
+// What the phase stamps of a diagnostic build showed (32->32 @160^3: 84k clocks per tile of which
 // 49k are the two co-resident waves' matrix time), and what this version does about it:
 //   * 2.5 ds_read_b32 per MFMA kept the LDS issue path, not the matrix pipe, busy  -> operand rows of four k-steps by ONE ds_read_b128
 //     (row / plane strides chosen for a conflict-free bank map), 0.63 reads per MFMA;
@@ -211,10 +195,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2_mfma(ConvArgs a) {
         }
     };
 
-    STAMP(0, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));        // HW_REG_HW_ID
-    STAMP(1, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20));       // HW_REG_XCC_ID
-    STAMP(2, __builtin_amdgcn_s_memtime());
-    [[maybe_unused]] int tile_no = 0;
     int work = pulpo::xcd_remap(blockIdx.x, nwg);           // static deal of the tiles: tile = block id + k * grid (remapped: an XCD's workgroups hold neighbouring tiles)
     Tile cur = describe(work);
 #pragma unroll
@@ -323,7 +303,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2_mfma(ConvArgs a) {
             }
         }
 
-        STAMP(3 + 2 * tile_no, __builtin_amdgcn_s_memtime());
         // ---- epilogue: x inverse transform in registers, y inverse transform across the four waves through LDS, one row tile (two z-planes) at
         // a time so that the exchange buffer stays inside the halo image (the next tile's first weight slab is landing in ws meanwhile)
         float* R = smem;                                    // [py][ox][r][lane]
@@ -500,8 +479,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2_mfma(ConvArgs a) {
                 }
             }
         }
-        STAMP(4 + 2 * tile_no, __builtin_amdgcn_s_memtime());
-        ++tile_no;
         if (!has_next) break;
         cur = nxt;
         work = next_work;
@@ -630,34 +607,24 @@ static int launch_wino2(const ConvArgs& a, int nblk, hipStream_t st) {
     return pulpo::check_launch("conv3d_k3_wino2_mfma");
 }
 
-static int wino2_pipe_enabled() {                      // PULPO_W2_PIPE=0 keeps the round-2 kernel for every operand (A/B switch)
-    static int pipe = -1;
-    if (pipe < 0) { const char* e = getenv("PULPO_W2_PIPE"); pipe = e ? atoi(e) : 1; }
-    return pipe;
-}
-
 // 1 when pulpo_conv3d_k3_fwd_wino2 / _dgrad_wino2_bnred run the pipelined kernel (conv3d_k3_wino2p_mfma) for a channels-last, 16-byte
 // aligned operand of K channels with voxel stride in_ps: K a multiple of 8 and the volume below 2^31 bytes.  (Names the kernel in traces.)
 PULPO_API int pulpo_conv3d_k3_wino2_pipelined(int D, int H, int W, int K, int64_t in_ps) {
     ConvArgs a{};
     a.D = D; a.H = H; a.W = W; a.Cin = K; a.Cout = 32; a.in_ps = in_ps;      // (output channel counts up to 1024 qualify)
-    return wino2_pipe_enabled() && wino2p_ok(a);
+    return wino2p_ok(a);
 }
 
 // Small volumes (the 20^3 pyramid level: 45 voxel tiles x 4 - 9 channel tiles for 512 resident workgroups) leave most compute units with one
 // workgroup: the pipelined kernel then splits the reduction channels of every (voxel tile, channel tile) over `ks` work items that store
 // partial slabs, and splitk_reduce_kernel adds the slabs in fixed order (deterministic) while it produces the BatchNorm partial sums.
-// Measured on MI355X (scripts/conv_bench.py, 20^3, PULPO_W2P_KSPLIT = 1 / 2 / 3 / 4 / 8): 192 -> 192 150 / 139 / 136 / 157 / 170 us,
+// Measured on MI355X (scripts/conv_bench.py, 20^3, split 1 / 2 / 3 / 4 / 8): 192 -> 192 150 / 139 / 136 / 157 / 170 us,
 // 288 -> 192 218 / 187 / 180 / 205 / 228 us, 128 -> 192 110 / 111 / 116 / 127 / 149 us, 192 -> 288 (405 items) 149 / 174 / 184 / 193 / 215 us:
 // three splits pay from 192 reduction channels up while the items fill at most about half of the slots, nothing else does.
-// PULPO_W2P_KSPLIT=<n> forces the split (1 = off) for measurements.
 static int wino2p_ksplit(int B, int D, int H, int W, int K, int N) {
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("PULPO_W2P_KSPLIT"); force = e ? atoi(e) : 0; }
-    if (!wino2_pipe_enabled() || K % 8 != 0) return 1;
+    if (K % 8 != 0) return 1;
     const long items = (long)B * pulpo::cdiv(D, 4) * pulpo::cdiv(H, TY) * pulpo::cdiv(W, TX) * pulpo::cdiv(N, 32);
     const int nchunk = K / 8;
-    if (force > 0) return std::min(force, nchunk);
     if (items <= 96 && nchunk >= 8) return std::min(nchunk / 4, 6);          // the 10^3 level: 12 voxel tiles (see wino2_ragged_depth_ok)
     return (items <= 288 && nchunk >= 24) ? 3 : 1;
 }
@@ -667,9 +634,7 @@ static int wino2p_ksplit(int B, int D, int H, int W, int K, int N) {
 // by the volume's extent, so a ragged depth tile costs only its empty rows; statistics then always come from the split-K reduction,
 // whose row count (pulpo_conv3d_k3_stat_tiles) does not depend on the tiling.
 int pulpo_conv::wino2_ragged_depth_ok(int B, int D, int H, int W, int K, int N) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PULPO_W2P_RAGGED_DEPTH"); on = e ? atoi(e) : 1; }      // (A/B switch)
-    return on && D >= 8 && (long)D * H * W >= 1000 && K % 8 == 0 && wino2_pipe_enabled() && wino2p_ksplit(B, D, H, W, K, N) > 1;
+    return D >= 8 && (long)D * H * W >= 1000 && K % 8 == 0 && wino2p_ksplit(B, D, H, W, K, N) > 1;
 }
 
 // floats of scratch pulpo_conv3d_k3_fwd_wino2 needs for the shape (0: none, scratch may be NULL)
@@ -738,16 +703,15 @@ static int fwd_wino2_impl(const float* in, int64_t in_bs, int64_t in_ps, int64_t
     PULPO_REQUIRE(nblk_l < (1L << 31), "conv3d_k3_fwd_wino2: grid too large");
     const bool vec = (in_cs == 1) && (in_ps % 4 == 0) && (in_bs % 4 == 0) && (K % 4 == 0) && (((uintptr_t)in & 15) == 0);
     hipStream_t st = (hipStream_t)stream;
-    // channels-last operands: the pipelined kernel (conv3d_wino2p.hip); PULPO_W2_PIPE=0 keeps the round-2 kernel
-    const int pipe = wino2_pipe_enabled();
+    // channels-last operands: the pipelined kernel (conv3d_wino2p.hip)
     PULPO_REQUIRE(conv_tz(D, H, W) == 4 || (vec && wino2p_ok(a)),
                   "conv3d_k3_fwd_wino2: a volume of depth %d needs a channels-last, 16-byte aligned operand (pipelined kernel, split-K)", D);
     if (bn_y != nullptr) {
         PULPO_REQUIRE(vec, "conv3d_k3_dgrad_wino2_bnred: the gradient operand must be channels-last, 16-byte aligned, with a multiple of 4 channels");
-        if (pipe && wino2p_ok(a)) return launch_wino2p(a, (int)nblk_l, true, st);
+        if (wino2p_ok(a)) return launch_wino2p(a, (int)nblk_l, true, st);
         return launch_wino2<true, true>(a, (int)nblk_l, st);
     }
-    if (vec && pipe && wino2p_ok(a)) {
+    if (vec && wino2p_ok(a)) {
         const int ks = wino2p_ksplit(B, D, H, W, K, N);
         if (ks == 1) return launch_wino2p(a, (int)nblk_l, false, st);
         PULPO_REQUIRE(scratch != nullptr, "conv3d_k3_fwd_wino2: scratch of pulpo_conv3d_k3_fwd_wino2_scratch_floats() floats required");

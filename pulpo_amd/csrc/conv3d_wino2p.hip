@@ -14,27 +14,6 @@
 //   * Image = [channel quad][row] float4s (rows = (hz, px, hy, x-pair), planes of 164 rows): the 16 lanes of every ds_read_b128 lane group
 //     fall on 16 different 16-byte slots without pad floats (rows {0-3, 24-27} of one plane and {8-11, 16-19} of the next, plane stride 4 mod 16).
 #include "conv_shared.h"
-#include <stdlib.h>
-
-#ifndef PULPO_W2P_FMA_BATCH
-#define PULPO_W2P_FMA_BATCH 1
-#endif
-#ifndef PULPO_ABL
-#define PULPO_ABL 0          // diagnostic builds (scripts/ablate.py): timings only, results are garbage.  Bits: 1 no epilogue, 2 no halo staging,
-#endif                       // 4 no weight re-loads, 8 no chunk barrier, 16 no MFMAs (one v_fma each), 32 no operand-row reads inside the loop, 64 phase stamps,
-                             // 128 no output stores (fast path), 256 no y combination (one operand row per row tile, no v_fma: the loop of a 2-D-staged image),
-                             // 512 staging without transform + LDS writes (loads and their waits only), 1024 staging without loads (transform + writes only)
-
-#if PULPO_ABL & 64
-// g_stamps[block][0] = HW_REG_HW_ID, [1] = HW_REG_XCC_ID, [2] = start clock, [3 + 2k] / [4 + 2k] = main-loop end / tile end of the block's k-th tile
-__device__ unsigned long long g_stamps[512 * 80];
-#define STAMP(slot, val) do { if (threadIdx.x == 0 && (slot) < 80) g_stamps[blockIdx.x * 80 + (slot)] = (val); } while (0)
-PULPO_API int pulpo_debug_read_stamps(void* dst, size_t bytes) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define STAMP(slot, val) do {} while (0)
-#endif
 
 namespace {
 
@@ -178,9 +157,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
         return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wl_off, (int)(wofs + px * w_px_stride), 0));
     };
 
-    if (a.stagger > 0 && (int)blockIdx.x >= (nwg >> 1)) {       // start-up offset of the second half of the grid (blocks b and b + nwg / 2 share a CU)
-        for (int s_ = 0; s_ < a.stagger; ++s_) __builtin_amdgcn_s_sleep(127);
-    }
     // ---- per-channel constants of the epilogue (bias | BatchNorm mean, scale, shift), once per workgroup into LDS: the epilogue reads them
     // with ds_read_b128 instead of waiting for global loads at the head of every tile
     float* const tab = smem + 2 * P_IMG;                // [3][ctab]
@@ -196,10 +172,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
         }
         tab[c] = t0; tab[ctab + c] = t1; tab[2 * ctab + c] = t2;
     }
-    STAMP(0, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));        // HW_REG_HW_ID
-    STAMP(1, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20));       // HW_REG_XCC_ID
-    STAMP(2, __builtin_amdgcn_s_memtime());
-    [[maybe_unused]] int tile_no = 0;
     int work = pulpo::xcd_remap(blockIdx.x, nwg);
     Tile cur = describe(work);
     int cb = 0;                                         // image being read
@@ -240,7 +212,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
         int it = 0;
         for (int chunk = cur.c0; chunk < cur.c1; ++chunk) {
             const bool last_chunk = chunk + 1 == cur.c1;
-            constexpr bool stage = !(PULPO_ABL & 2);
             // what is staged underneath this chunk's MFMAs: the tile's next chunk, or chunk 0 of the next tile (after the last tile: the
             // tile's own chunk 0 again, into an image nobody reads - cheaper than a branch around every piece of the side work)
             if (last_chunk) halo_offsets(has_next ? nxt : cur);
@@ -255,9 +226,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                 for (int m = 0; m < 2; ++m) {
                     const int off = ((2 * m + dz) * P_PLROWS + px * P_PL) * 4;
                     ra[slot][m] = *reinterpret_cast<const float4*>(pa + off);
-#if !(PULPO_ABL & 256)
                     rb[slot][m] = *reinterpret_cast<const float4*>(pb + off);
-#endif
                 }
             };
             fetch_a(0, 0, 0);
@@ -266,25 +235,17 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                 const bool tile_end = dz == 2 && last_chunk;
                 // (after the last tile the re-load fetches the tile's own first rows again: no branch around a load inside the loop, so the
                 //  compiler's vmcnt counts stay exact)
-                constexpr bool more_w = !(PULPO_ABL & 4);
                 const unsigned wsrc = tile_end ? (has_next ? nxt.wbase : cur.wbase) : wnext;
 #pragma unroll
                 for (int px = 0; px < 4; ++px) {
                     const int s = dz * 4 + px;
-                    if (!(PULPO_ABL & 32)) {
-                        if (px + 1 < 4) fetch_a(dz, px + 1, (px + 1) & 1);
-                        else if (dz < 2) fetch_a(dz + 1, 0, 0);
-                    }
+                    if (px + 1 < 4) fetch_a(dz, px + 1, (px + 1) & 1);
+                    else if (dz < 2) fetch_a(dz + 1, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     const int sl = px & 1;
                     const float wv[4] = {wr[px].x, wr[px].y, wr[px].z, wr[px].w};
-#if PULPO_W2P_FMA_BATCH
                     // the step's eight y combinations first, then eight MFMAs back to back (no VALU -> MFMA dependency stall between them)
                     float av[4][2];
-#if PULPO_ABL & 256
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) { av[0][m] = ra[sl][m].x; av[1][m] = ra[sl][m].y; av[2][m] = ra[sl][m].z; av[3][m] = ra[sl][m].w; }
-#else
                     // (two-wide vector arithmetic: four v_pk_fma_f32 per step instead of eight v_fma_f32)
 #pragma unroll
                     for (int m = 0; m < 2; ++m) {
@@ -293,47 +254,27 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                         const f32x2 hi = __builtin_elementwise_fma(sav, f32x2{rb[sl][m].z, rb[sl][m].w}, f32x2{ra[sl][m].z, ra[sl][m].w});
                         av[0][m] = lo.x; av[1][m] = lo.y; av[2][m] = hi.x; av[3][m] = hi.y;
                     }
-#endif
                     __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
                     for (int s2 = 0; s2 < 4; ++s2) {
 #pragma unroll
                         for (int m = 0; m < 2; ++m) {
-#if PULPO_W2P_FMA_BATCH
                             const float v_ = av[s2][m];
-#else
-                            const float a_ = s2 == 0 ? ra[sl][m].x : s2 == 1 ? ra[sl][m].y : s2 == 2 ? ra[sl][m].z : ra[sl][m].w;
-                            const float b_ = s2 == 0 ? rb[sl][m].x : s2 == 1 ? rb[sl][m].y : s2 == 2 ? rb[sl][m].z : rb[sl][m].w;
-                            const float v_ = fmaf(sa, b_, a_);
-#endif
-#if PULPO_ABL & 16
-                            acc[m][px][s2] = fmaf(v_, wv[s2], acc[m][px][s2]);
-#else
                             acc[m][px] = __builtin_amdgcn_mfma_f32_32x32x2f32(v_, wv[s2], acc[m][px], 0, 0, 0);
-#endif
                         }
                         if (s2 == 0) {                  // behind the step's first MFMAs: their 128 pipe clocks cover the issue of the side work
                             __builtin_amdgcn_sched_barrier(0);
-                            if (stage) {
-#if !(PULPO_ABL & 1024)
-                                if (s == P_LD0) { load_raw(st_rs, st_c0, 0, 0); load_raw(st_rs, st_c0, 0, 1); }
-                                if (s == P_LD0 + 1) { load_raw(st_rs, st_c0, 0, 2); load_raw(st_rs, st_c0, 0, 3); }
-                                if (s == P_LD1) { load_raw(st_rs, st_c0, 1, 0); load_raw(st_rs, st_c0, 1, 1); }
-                                if (s == P_LD1 + 1) { load_raw(st_rs, st_c0, 1, 2); load_raw(st_rs, st_c0, 1, 3); }
-#endif
-#if PULPO_ABL & 512
-                                if (s == P_XF0 || s == P_XF1) asm volatile("" : : "v"(raw[0].x), "v"(raw[1].x), "v"(raw[2].x), "v"(raw[3].x));      // (wait only)
-#else
-                                if (s == P_XF0) store_item(img_w, 0);
-                                if (s == P_XF1) store_item(img_w, 1);
-#endif
-                            }
+                            if (s == P_LD0) { load_raw(st_rs, st_c0, 0, 0); load_raw(st_rs, st_c0, 0, 1); }
+                            if (s == P_LD0 + 1) { load_raw(st_rs, st_c0, 0, 2); load_raw(st_rs, st_c0, 0, 3); }
+                            if (s == P_LD1) { load_raw(st_rs, st_c0, 1, 0); load_raw(st_rs, st_c0, 1, 1); }
+                            if (s == P_LD1 + 1) { load_raw(st_rs, st_c0, 1, 2); load_raw(st_rs, st_c0, 1, 3); }
+                            if (s == P_XF0) store_item(img_w, 0);
+                            if (s == P_XF1) store_item(img_w, 1);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
                     // the weights of this point are consumed (issued): fetch the same point of the next iteration into the register
-                    if (more_w) wr[px] = load_w(wsrc, px);
+                    wr[px] = load_w(wsrc, px);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 wnext += w_it_stride;
@@ -343,11 +284,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
             // tile back edge; behind an epilogue it would stand for "all but the youngest few" of that tile's output stores.)
 #pragma unroll
             for (int px = 0; px < 3; ++px) asm volatile("" : : "v"(wr[px].x), "v"(wr[px].y), "v"(wr[px].z), "v"(wr[px].w));
-            if (!(PULPO_ABL & 8)) __syncthreads();      // image cb ^ 1 complete and visible; every wave has left image cb
+            __syncthreads();                            // image cb ^ 1 complete and visible; every wave has left image cb
             cb ^= 1;
         }
 
-        STAMP(3 + 6 * tile_no, __builtin_amdgcn_s_memtime());
         // ---- epilogue: x inverse transform in registers, y inverse transform across the four waves through LDS, one row tile (two z-planes) at
         // a time; the exchange buffer is the image the last chunk was read from (the next tile's chunk 0 already sits in the other one)
         float* R = smem + (cb ^ 1) * P_IMG;                 // [py][ox][r][lane]
@@ -386,10 +326,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
         const float4 sh4 = *reinterpret_cast<const float4*>(tab + 2 * ctab + co0 + 4 * q);
         const float bias1 = with_bias ? tab[co0 + ei] : 0.f, fsc1 = tab[ctab + co0 + ei], fsh1 = tab[2 * ctab + co0 + ei];
         const float* bn_b = bnr ? a.bn_y + (long)cur.b * a.bn_y_bs + co0 + 4 * q : nullptr;
-        STAMP(4 + 6 * tile_no, __builtin_amdgcn_s_memtime());
 #pragma unroll
-        for (int m = 0; m < ((PULPO_ABL & 1) ? 0 : 2); ++m) {
-            if (m > 0) { STAMP(6 + 6 * tile_no, __builtin_amdgcn_s_memtime()); __syncthreads(); }                     // every wave has left the exchange buffer (previous row tile)
+        for (int m = 0; m < 2; ++m) {
+            if (m > 0) __syncthreads();                 // every wave has left the exchange buffer (previous row tile)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float m0 = acc[m][0][r], m1 = acc[m][1][r], m2 = acc[m][2][r], m3 = acc[m][3][r];
@@ -410,7 +349,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                 }
             }
             __syncthreads();
-            if (m == 0) STAMP(5 + 6 * tile_no, __builtin_amdgcn_s_memtime());
             if (fast) {
                 float4 tq[2][4];
 #pragma unroll
@@ -461,9 +399,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                         v0 = make_float4(act(v0.x, sc4.x, sh4.x), act(v0.y, sc4.y, sh4.y), act(v0.z, sc4.z, sh4.z), act(v0.w, sc4.w, sh4.w));
                         v1 = make_float4(act(v1.x, sc4.x, sh4.x), act(v1.y, sc4.y, sh4.y), act(v1.z, sc4.z, sh4.z), act(v1.w, sc4.w, sh4.w));
                     }
-#if PULPO_ABL & 128
-                    if (v0.x == 12345.678f && v1.y == 9876.54f)
-#endif
                     {
                         if (in0) *reinterpret_cast<float4*>(obase + vox * o_ps) = v0;
                         if (in1) *reinterpret_cast<float4*>(obase + (vox + a.W) * o_ps) = v1;
@@ -498,7 +433,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                 }
             }
         }
-        STAMP(7 + 6 * tile_no, __builtin_amdgcn_s_memtime());
         // per-tile BatchNorm partial sums: reduce over the lanes that hold the same channel(s), then over the four waves.  The barrier also
         // separates the exchange buffer's last reads from the next tile's staging into the same image, so it is taken without statistics too.
         if (stats != nullptr) {
@@ -530,11 +464,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                 stats[((long)cur.tile_lin * 2 + which) * a.Cout + co0 + c] = tot;
             }
         }
-#if PULPO_ABL & 1
-        if (acc[0][0][0] + acc[1][1][1] + acc[0][2][2] + acc[1][3][3] + acc[0][1][5] + acc[1][0][7] + acc[0][3][9] + acc[1][2][11] == 12345.678f) out_b[tid] = 1.f;
-#endif
-        STAMP(8 + 6 * tile_no, __builtin_amdgcn_s_memtime());
-        ++tile_no;
         if (!has_next) break;
         cur = nxt;
         work = next_work;
@@ -558,19 +487,9 @@ int launch_wino2p(const ConvArgs& a, int nblk, bool bnr, hipStream_t st) {
         if (e != hipSuccess) return pulpo::fail((int)e, "hipFuncSetAttribute(conv3d wino2p): %s", hipGetErrorString(e));
         attr_set[bnr] = true;
     }
-    {
-        static int pct = -1;                            // PULPO_W2P_STAGGER = start-up offset of the second workgroup of a CU, % of a tile's time
-        if (pct < 0) { const char* e = getenv("PULPO_W2P_STAGGER"); pct = e ? atoi(e) : 0; }
-        const long clocks = ((long)((a.Cin + P_CH - 1) / P_CH) * 96 * 64 * 2 + 6000) * pct / 100;
-        const_cast<ConvArgs&>(a).stagger = nblk >= 512 ? (int)(clocks / (64 * 127)) : 0;
-    }
-    {
-        // PULPO_W2P_TILE_ORDER: 1 (default) blocked 4 x 4 x 4 where the tile grid allows (the 160^3 layers), 0 linear (x fastest).  Measured with
-        // rocprofv3 --pmc FETCH_SIZE on 32 -> 32 @ 160^3 / 128 -> 128 @ 40^3: 28 % fewer bytes over the fabric, 1 % less time stand-alone.
-        static int order = -1;
-        if (order < 0) { const char* e = getenv("PULPO_W2P_TILE_ORDER"); order = e ? atoi(e) : 1; }
-        const_cast<ConvArgs&>(a).tile_order = (order == 1 && a.ntx % 4 == 0 && a.nty % 4 == 0 && a.ntz % 4 == 0) ? 1 : 0;
-    }
+    // tiles in 4 x 4 x 4 blocks where the tile grid allows (the 160^3 layers), else in linear order (x fastest).  Measured with rocprofv3 --pmc
+    // FETCH_SIZE on 32 -> 32 @ 160^3 / 128 -> 128 @ 40^3: 28 % fewer bytes over the fabric than linear order, 1 % less time stand-alone.
+    const_cast<ConvArgs&>(a).tile_order = (a.ntx % 4 == 0 && a.nty % 4 == 0 && a.ntz % 4 == 0) ? 1 : 0;
     // persistent workgroups: two per CU
     if (bnr) hipLaunchKernelGGL((conv3d_k3_wino2p_mfma<true>), dim3(std::min(nblk, 512)), dim3(256), P_LDS, st, a);
     else hipLaunchKernelGGL((conv3d_k3_wino2p_mfma<false>), dim3(std::min(nblk, 512)), dim3(256), P_LDS, st, a);

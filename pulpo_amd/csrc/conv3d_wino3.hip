@@ -18,7 +18,7 @@
 //
 // Whole tiles only (D % 4 == 0, H % 8 == 0, W % 8 == 0), channels-last 16-byte aligned operands, Cin % 8 == 0, Cout % 32 == 0, at least 256 work
 // items: every such layer from 16 reduction channels up (pulpo_conv3d_k3_algo = 3; 32 until the end of round 4 - with the leaner tile head and epilogue
-// two chunks per tile pay too: 16 -> 96 at 80^3 0.242 -> 0.213 ms; PULPO_CONV_WINO3=0 / PULPO_CONV_WINO3_MINK=<k> move the policy).
+// two chunks per tile pay too: 16 -> 96 at 80^3 0.242 -> 0.213 ms).
 // What was measured while it was built: an image transformed along x AND z at staging time (two rows per step instead of
 // four) multiplies faster (bare loop 0.31 against 0.34 ms at 64 -> 64 / 80^3) but its staging - eight loads, 32 combinations and a second
 // item for a quarter of the threads - cost 20 - 24 % against 8 - 10 % here; wave-uniform branches around staging loads cost 15 % (every
@@ -26,30 +26,6 @@
 // zeroes out-of-volume planes ignores the scalar offset).
 #include "conv_shared.h"
 #include "wino3_pack.h"
-#include <stdlib.h>
-
-#ifndef PULPO_W3_STAMPS
-#define PULPO_W3_STAMPS 0        // diagnostic build (scripts/stamps_w3.py): s_memtime stamps of one tile's phases per wave, kept in registers until the tile's end
-#endif
-#if PULPO_W3_STAMPS
-__device__ unsigned g_w3_stamps[256 * 8 * 32];
-PULPO_API int pulpo_debug_read_stamps_w3(void* dst, size_t bytes) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_w3_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-#define W3_CLK() ((unsigned)__builtin_amdgcn_s_memtime())                        // (waits for lgkmcnt(0) where it is consumed: the stamps sit where that wait is due anyway)
-// scalar stamps (SGPRs): T = now; the phase accumulators of the tile are wave-uniform sums
-#define W3_NOW(var) do { __builtin_amdgcn_sched_barrier(0); var = W3_CLK(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define W3_STAMP(i) do {} while (0)
-#else
-#define W3_STAMP(i) do {} while (0)
-#endif
-
-#ifndef PULPO_W3_PK
-#define PULPO_W3_PK 1        // the y / z combinations in two-wide vector arithmetic (v_pk_fma_f32); 0: scalar v_fma_f32 - measured 3-4 % slower here (64-clock fp32 MFMAs leave room)
-#endif
-#ifndef PULPO_ABL
-#define PULPO_ABL 0          // diagnostic builds (scripts/ablate.py): timings only, results are garbage.  Bits: 1 no epilogue, 2 no halo staging, 64 every tap from one 64 KB window (cache hits),
-#endif                       // 4 no weight re-loads, 8 no chunk barrier, 32 no operand-row reads inside the loop
 
 namespace {
 
@@ -70,12 +46,6 @@ constexpr int Q_PART = 8 * 64 * 8;               // a wave's per-lane statistics
 constexpr size_t Q_LDS = (size_t)(2 * Q_IMG + Q_TAB + Q_R + Q_RED + Q_PART) * sizeof(float);
 static_assert(Q_LDS <= 160 * 1024, "one workgroup per CU");
 
-#ifndef PULPO_W3_YEARLY
-#define PULPO_W3_YEARLY 1          // BNR epilogue: y requested early (see the epilogue)
-#endif
-#ifndef PULPO_W3_SKEW
-#define PULPO_W3_SKEW 1          // 1: the two waves of a SIMD (w and w + 4) do their halo staging in DIFFERENT pairs of a chunk (see the kernel below)
-#endif
 
 // SP: the pair of a chunk behind whose first MFMAs a wave transforms and stores its staging item (SP) and requests the next taps (SP + 1)
 template <bool BNR, int SP>
@@ -169,7 +139,7 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
         const bool rowok = item && (unsigned)(t.z0 - 1 + hz) < (unsigned)a.D && (unsigned)(t.y0 - 1 + hy) < (unsigned)a.H;
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt)
-            hoff[tt] = (rowok && (unsigned)(t.x0 - 1 + 2 * xb + tt) < (unsigned)a.W) ? ((PULPO_ABL & 64) ? ((origin + roff + tt * ps_bytes) & 0xFFE0u) : origin + roff + tt * ps_bytes) : OOB;
+            hoff[tt] = (rowok && (unsigned)(t.x0 - 1 + 2 * xb + tt) < (unsigned)a.W) ? origin + roff + tt * ps_bytes : OOB;
     };
     auto in_rsrc = [&](int b) {
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in + (long)b * a.in_bs), 0, in_bytes, 0x00020000);
@@ -229,10 +199,6 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
     for (int pp = 0; pp < 2; ++pp) { wr[pp][0] = load_w(cur.wbase, pp); wr[pp][1] = load_w(cur.wbase, 4 + pp); }
     __syncthreads();
 
-#ifndef PULPO_W3_SETPRIO
-#define PULPO_W3_SETPRIO 2       // 0: equal priorities, 1: waves 4-7 raised for good (no gain), 2: the partners of a SIMD alternate per pair (+1.5 %)
-#endif
-    if (PULPO_W3_SETPRIO == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);       // (the second-dispatched half loses every issue arbitration otherwise: MI355X_MICROARCH.md)
     float4 ra[3], rb[3];                                // the operand rows of a PAIR of point steps (pz local 0 / 1 at one px): rows ta / tb of planes U, V, W
 
     // The tile's statistics: the waves' partial sums wait in `red` and are added behind the NEXT barrier every wave passes anyway (the end of the
@@ -249,10 +215,6 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
         }
         pend_tile = -1;
     };
-#if PULPO_W3_STAMPS
-    int tile_no = 0;
-    unsigned w3_tile0 = 0, w3_rows = 0, w3_mfma = 0, w3_bar = 0;
-#endif
     for (;;) {
         // the next tile is known from the start (its description inside the chunk loop, under `chunk + 2 == nchunk`, was if-converted by the
         // compiler: five integer divisions' worth of scalar instructions and a dozen spilled-register reloads in EVERY chunk)
@@ -291,9 +253,9 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
             // Point steps run in PAIRS - the wave's two z points at one px: they share the three planes U, V, W (six rows instead of eight), and
             // their MFMAs alternate between two accumulator tiles, so that no matrix instruction waits for the result of the one in front of
             // it.  The rows of the next pair are requested as soon as the combinations have been formed.
-            // y combination of each plane (Y = A + sa B), then the two z combinations; two-wide vector arithmetic
+            // y combination of each plane (Y = A + sa B), then the two z combinations; two-wide vector arithmetic (v_pk_fma_f32: scalar v_fma_f32
+            // measured 3-4 % slower here - the 64-clock fp32 MFMAs leave room)
             auto combine = [&](float (&av0)[4], float (&av1)[4]) {
-#if PULPO_W3_PK
                 const f32x2 sav = {sa, sa}, m1 = {-1.f, -1.f}, bwv = {bw, bw};
                 f32x2 ylo[3], yhi[3];
 #pragma unroll
@@ -305,59 +267,22 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
                 const f32x2 lo1 = __builtin_elementwise_fma(bwv, ylo[2], ylo[1]), hi1 = __builtin_elementwise_fma(bwv, yhi[2], yhi[1]);
                 av0[0] = lo0.x; av0[1] = lo0.y; av0[2] = hi0.x; av0[3] = hi0.y;
                 av1[0] = lo1.x; av1[1] = lo1.y; av1[2] = hi1.x; av1[3] = hi1.y;
-#else
-                // scalar fmas (the guide prices v_pk_fma_f32 above two v_fma_f32 beside 32-clock bf16 MFMAs; beside these 64-clock fp32 MFMAs the packed form won)
-                float y[3][4];
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    y[p][0] = fmaf(sa, rb[p].x, ra[p].x); y[p][1] = fmaf(sa, rb[p].y, ra[p].y);
-                    y[p][2] = fmaf(sa, rb[p].z, ra[p].z); y[p][3] = fmaf(sa, rb[p].w, ra[p].w);
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    av0[k] = y[0][k] - y[2][k];
-                    av1[k] = fmaf(bw, y[2][k], y[1][k]);
-                }
-#endif
-            };
-#ifndef PULPO_W3_SPREAD
-#define PULPO_W3_SPREAD 0        // 1: the next pair's combinations spread over the gaps behind the fourth, sixth and eighth MFMA instead of one block behind the fourth
-#endif
-            f32x2 sy_lo[3], sy_hi[3];
-            auto comb_y = [&](int p) {
-                const f32x2 sav = {sa, sa};
-                sy_lo[p] = __builtin_elementwise_fma(sav, f32x2{rb[p].x, rb[p].y}, f32x2{ra[p].x, ra[p].y});
-                sy_hi[p] = __builtin_elementwise_fma(sav, f32x2{rb[p].z, rb[p].w}, f32x2{ra[p].z, ra[p].w});
-            };
-            auto comb_z = [&](float (&av0)[4], float (&av1)[4]) {
-                const f32x2 m1 = {-1.f, -1.f}, bwv = {bw, bw};
-                const f32x2 lo0 = __builtin_elementwise_fma(m1, sy_lo[2], sy_lo[0]), hi0 = __builtin_elementwise_fma(m1, sy_hi[2], sy_hi[0]);
-                const f32x2 lo1 = __builtin_elementwise_fma(bwv, sy_lo[2], sy_lo[1]), hi1 = __builtin_elementwise_fma(bwv, sy_hi[2], sy_hi[1]);
-                av0[0] = lo0.x; av0[1] = lo0.y; av0[2] = hi0.x; av0[3] = hi0.y;
-                av1[0] = lo1.x; av1[1] = lo1.y; av1[2] = hi1.x; av1[3] = hi1.y;
             };
             // Software pipeline over the chunk's four pairs: the operand rows of pair pp + 1 are requested in front of pair pp's MFMAs and
             // COMBINED between them (behind the fourth of the eight), the rows of pair pp + 2 requested right after - a wave never stands in a
             // vector-only phase while it has matrix instructions to issue, except in front of a chunk's first pair.
             float avn0[4], avn1[4];                     // the operands of the pair in flight / of the next pair
-#if PULPO_W3_STAMPS
-            unsigned t_a, t_b, t_c, t_d;
-            W3_NOW(t_a);
-            if (chunk == 0) { w3_tile0 = t_a; w3_rows = 0; w3_mfma = 0; w3_bar = 0; }
-#endif
-            if (!(PULPO_ABL & 32)) fetch_a(0);
+            fetch_a(0);
             combine(avn0, avn1);
-#if PULPO_W3_STAMPS
-            W3_NOW(t_b);
-#endif
-            if (!(PULPO_ABL & 32)) fetch_a(1);
+            fetch_a(1);
 #pragma unroll
             for (int pp = 0; pp < 4; ++pp) {
                 const int s0 = pp, s1 = 4 + pp;         // point steps (pz local 0, px = pp) and (pz local 1, px = pp)
-                // PULPO_W3_SETPRIO = 2: the two waves of a SIMD (w and w + 4: pzh 0 / 1) take the higher issue priority in ALTERNATING pairs.  At
-                // equal priority the older wave wins every arbitration: it runs its 32 MFMAs of a chunk in 3 350 clocks, the younger one gets
-                // the leftover slots and finishes alone 1 300 clocks later (scripts/stamps_w3.py), with the pipe idle in its gaps.
-                if (PULPO_W3_SETPRIO == 2) { if (((pp + pzh) & 1) != 0) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+                // The two waves of a SIMD (w and w + 4: pzh 0 / 1) take the higher issue priority in ALTERNATING pairs (+1.5 %; waves 4-7 raised
+                // for good gained nothing).  At equal priority the older wave wins every arbitration: it runs its 32 MFMAs of a chunk in 3 350
+                // clocks, the younger one gets the leftover slots and finishes alone 1 300 clocks later (in-kernel clock stamps), with the pipe
+                // idle in its gaps.
+                if (((pp + pzh) & 1) != 0) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
                 const float av0[4] = {avn0[0], avn0[1], avn0[2], avn0[3]}, av1[4] = {avn1[0], avn1[1], avn1[2], avn1[3]};
                 const float wv0[4] = {wr[pp & 1][0].x, wr[pp & 1][0].y, wr[pp & 1][0].z, wr[pp & 1][0].w};
                 const float wv1[4] = {wr[pp & 1][1].x, wr[pp & 1][1].y, wr[pp & 1][1].z, wr[pp & 1][1].w};
@@ -368,47 +293,29 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
                     acc[s1 >> 2][s1 & 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s2], wv1[s2], acc[s1 >> 2][s1 & 3], 0, 0, 0);
                     if (s2 == 0) {                      // behind the pair's first MFMAs: the staging work of the pair
                         __builtin_amdgcn_sched_barrier(0);
-                        if (!(PULPO_ABL & 2)) {
-                            if (pp == SP) {
-                                store_item(img_w);
-                                if (chunk + 2 == nchunk) halo_offsets(has_next ? nxt : cur);
-                            }
-                            if (pp == SP + 1) { load_raw(st_rs, st_c0, 0); load_raw(st_rs, st_c0, 1); load_raw(st_rs, st_c0, 2); load_raw(st_rs, st_c0, 3); }
+                        if (pp == SP) {
+                            store_item(img_w);
+                            if (chunk + 2 == nchunk) halo_offsets(has_next ? nxt : cur);
                         }
+                        if (pp == SP + 1) { load_raw(st_rs, st_c0, 0); load_raw(st_rs, st_c0, 1); load_raw(st_rs, st_c0, 2); load_raw(st_rs, st_c0, 3); }
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (!PULPO_W3_SPREAD && s2 == 1 && pp + 1 < 4) {        // behind the fourth MFMA: the next pair's combinations, then the request for the pair after it
+                    if (s2 == 1 && pp + 1 < 4) {        // behind the fourth MFMA: the next pair's combinations, then the request for the pair after it
                         __builtin_amdgcn_sched_barrier(0);
                         combine(avn0, avn1);
                         __builtin_amdgcn_sched_barrier(0);
-                        if (!(PULPO_ABL & 32) && pp + 2 < 4) fetch_a(pp + 2);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    if (PULPO_W3_SPREAD && pp + 1 < 4 && s2 >= 1) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (s2 == 1) { comb_y(0); comb_y(1); }
-                        if (s2 == 2) { comb_y(2); comb_z(avn0, avn1); }
-                        if (s2 == 3 && !(PULPO_ABL & 32) && pp + 2 < 4) fetch_a(pp + 2);
+                        if (pp + 2 < 4) fetch_a(pp + 2);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
                 // the pair's weights are consumed: a ring of two pairs - the rows take the points of the pair two on (the same chunk's, or the
                 // next chunk's first two)
-                if (!(PULPO_ABL & 4)) {
-                    wr[pp & 1][0] = pp < 2 ? load_w(wcur, s0 + 2) : load_w(wnext, s0 - 2);
-                    wr[pp & 1][1] = pp < 2 ? load_w(wcur, s1 + 2) : load_w(wnext, s1 - 2);
-                }
+                wr[pp & 1][0] = pp < 2 ? load_w(wcur, s0 + 2) : load_w(wnext, s0 - 2);
+                wr[pp & 1][1] = pp < 2 ? load_w(wcur, s1 + 2) : load_w(wnext, s1 - 2);
                 __builtin_amdgcn_sched_barrier(0);
             }
             wcur += w_chunk_stride;
-#if PULPO_W3_STAMPS
-            W3_NOW(t_c);
-#endif
-            if (!(PULPO_ABL & 8)) __syncthreads();      // image cb ^ 1 complete and visible; every wave has left image cb
-#if PULPO_W3_STAMPS
-            W3_NOW(t_d);
-            w3_rows += t_b - t_a; w3_mfma += t_c - t_b; w3_bar += t_d - t_c;
-#endif
+            __syncthreads();                            // image cb ^ 1 complete and visible; every wave has left image cb
             cb ^= 1;
             if (chunk == 0) flush_stats();              // (the previous tile's, see above)
         }
@@ -432,14 +339,10 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
         const int ox = combo >> 4, rr = combo & 15;
         const int row = (rr & 3) + 8 * (rr >> 2) + 4 * kh;          // = MFMA row = block (zb, yb, xb)
         const int vzb = row >> 4, vyb = (row >> 2) & 3, vxb = row & 3;
-#if PULPO_W3_STAMPS
-        unsigned t_e0, t_e1 = 0, t_e2 = 0, t_e3;
-        W3_NOW(t_e0);
-#endif
         // x inverse transform (4 px -> 2 ox), once and in place: acc[p][0] <- out x0 = q0 + q1 + q2, acc[p][1] <- out x1 = q1 - q2 - q3
         // BNR: the pre-norm values of this lane's two output voxels of a parity are requested EARLY - parity 0 in front of the x inverse transform,
         // parity 1 as soon as parity 0's have been used - so that a miss (y is read once per step: HBM) lands under the transform and the exchange
-        // instead of in front of the sums that need it (PULPO_W3_YEARLY=0: requested right in front of the exchange barrier of their parity)
+        // instead of in front of the sums that need it
         float4 yv0 = zero4, yv1 = zero4;
         const bool qok = co0 + 4 * q < a.Cout;         // (a partly empty cout tile: channel quads beyond the tensor are neither read nor stored)
         auto load_y = [&](int oz_) {
@@ -449,27 +352,26 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
                 yv1 = *reinterpret_cast<const float4*>(bn_b + (vox_ + a.W) * a.bn_y_ps);
             }
         };
-        if (PULPO_W3_YEARLY) { load_y(0); __builtin_amdgcn_sched_barrier(0); }
+        load_y(0);
+        __builtin_amdgcn_sched_barrier(0);
         // a - b below is fma(m1, b, a) with m1 = -1 the compiler cannot see through: exact (the product is), and it stays ONE two-wide instruction
         // (v_pk_fma_f32) - a two-wide subtraction is expanded into two scalar ones by the backend
         f32x2 m1 = {-1.f, -1.f};
         asm volatile("" : "+s"(m1));
         // (two-wide: the accumulator registers of rows r, r + 1 are an aligned pair - v_pk_add_f32 with the association of the scalar form,
         //  (a0 + a1) + a2 and (a1 - a2) - a3: 64 instead of 128 vector instructions per wave, which the SIMD's two waves issue at the same time)
-        if (!(PULPO_ABL & 1)) {
 #pragma unroll
-            for (int p = 0; p < 2; ++p)
+        for (int p = 0; p < 2; ++p)
 #pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const f32x2 a0 = {acc[p][0][r], acc[p][0][r + 1]}, a1 = {acc[p][1][r], acc[p][1][r + 1]};
-                    const f32x2 a2 = {acc[p][2][r], acc[p][2][r + 1]}, a3 = {acc[p][3][r], acc[p][3][r + 1]};
-                    const f32x2 o0 = (a0 + a1) + a2, o1 = __builtin_elementwise_fma(m1, a3, __builtin_elementwise_fma(m1, a2, a1));
-                    acc[p][0][r] = o0.x; acc[p][0][r + 1] = o0.y;
-                    acc[p][1][r] = o1.x; acc[p][1][r + 1] = o1.y;
-                }
-        }
+            for (int r = 0; r < 16; r += 2) {
+                const f32x2 a0 = {acc[p][0][r], acc[p][0][r + 1]}, a1 = {acc[p][1][r], acc[p][1][r + 1]};
+                const f32x2 a2 = {acc[p][2][r], acc[p][2][r + 1]}, a3 = {acc[p][3][r], acc[p][3][r + 1]};
+                const f32x2 o0 = (a0 + a1) + a2, o1 = __builtin_elementwise_fma(m1, a3, __builtin_elementwise_fma(m1, a2, a1));
+                acc[p][0][r] = o0.x; acc[p][0][r + 1] = o0.y;
+                acc[p][1][r] = o1.x; acc[p][1][r + 1] = o1.y;
+            }
 #pragma unroll
-        for (int oz = 0; oz < ((PULPO_ABL & 1) ? 0 : 2); ++oz) {
+        for (int oz = 0; oz < 2; ++oz) {
             if (oz > 0) __syncthreads();                // every wave has left the exchange buffer (previous parity)
             // this wave's share of the z inverse transform: out z0 = q0 + q1 + q2, out z1 = q1 - q2 - q3; wave pzh = 0 holds (q0, q1), pzh = 1
             // holds (q2, -q3) (the second accumulator of those waves holds MINUS its point, see the matrix loop).  A branch per wave (pzh is
@@ -495,14 +397,7 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
             }
             const int gz = z0 + 2 * vzb + oz, gy = y0 + 2 * vyb, gx = x0 + 2 * vxb + ox;
             const long vox = (long)(gz * a.H + gy) * a.W + gx;
-            if (BNR && !PULPO_W3_YEARLY && qok) {
-                yv0 = *reinterpret_cast<const float4*>(bn_b + vox * a.bn_y_ps);
-                yv1 = *reinterpret_cast<const float4*>(bn_b + (vox + a.W) * a.bn_y_ps);
-            }
             __syncthreads();
-#if PULPO_W3_STAMPS
-            if (oz == 0) W3_NOW(t_e1);
-#endif
             float4 t[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) {               // point row p: the two z halves summed
@@ -523,7 +418,7 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
                 red1(v0.z, yv0.z, sc4.z, sh4.z, bm4.z, s4.z, q4.z); red1(v0.w, yv0.w, sc4.w, sh4.w, bm4.w, s4.w, q4.w);
                 red1(v1.x, yv1.x, sc4.x, sh4.x, bm4.x, s4.x, q4.x); red1(v1.y, yv1.y, sc4.y, sh4.y, bm4.y, s4.y, q4.y);
                 red1(v1.z, yv1.z, sc4.z, sh4.z, bm4.z, s4.z, q4.z); red1(v1.w, yv1.w, sc4.w, sh4.w, bm4.w, s4.w, q4.w);
-                if (PULPO_W3_YEARLY && oz == 0) { __builtin_amdgcn_sched_barrier(0); load_y(1); __builtin_amdgcn_sched_barrier(0); }
+                if (oz == 0) { __builtin_amdgcn_sched_barrier(0); load_y(1); __builtin_amdgcn_sched_barrier(0); }
             } else {
                 s4.x += v0.x + v1.x; s4.y += v0.y + v1.y; s4.z += v0.z + v1.z; s4.w += v0.w + v1.w;
                 q4.x += v0.x * v0.x + v1.x * v1.x; q4.y += v0.y * v0.y + v1.y * v1.y; q4.z += v0.z * v0.z + v1.z * v1.z; q4.w += v0.w * v0.w + v1.w * v1.w;
@@ -538,9 +433,6 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
                 *reinterpret_cast<float4*>(obase + vox * a.out_ps) = v0;
                 *reinterpret_cast<float4*>(obase + (vox + a.W) * a.out_ps) = v1;
             }
-#if PULPO_W3_STAMPS
-            if (oz == 0) W3_NOW(t_e2);
-#endif
         }
         // per-tile BatchNorm partial sums: over the lanes that hold the same channels, then over the eight waves
         // (through the wave's own LDS rows - DS operations of one wave execute in order, no barrier - instead of three rounds of cross-lane
@@ -557,25 +449,6 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
             red[(wave * 2 + wh_) * NT + c_] = t_;
         }
         pend_tile = cur.tile_lin; pend_co0 = co0;
-#if PULPO_W3_STAMPS
-        W3_NOW(t_e3);
-        if (tile_no == 1 && lane == 0) {
-            unsigned* o_ = g_w3_stamps + (blockIdx.x * 8 + wave) * 32;
-            o_[0] = w3_rows; o_[1] = w3_mfma; o_[2] = w3_bar; o_[3] = t_e0 - w3_tile0; o_[4] = t_e1 - t_e0; o_[5] = t_e2 - t_e1; o_[6] = t_e3 - t_e2;
-            o_[7] = t_e3 - w3_tile0;
-        }
-        ++tile_no;
-#endif
-#if PULPO_ABL & 1
-        {
-            float t_ = 0.f;
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int x = 0; x < 4; ++x) t_ += acc[p][x][(p * 4 + x) & 15];
-            if (t_ == 12345.678f) out_b[tid] = 1.f;
-        }
-#endif
         if (!has_next) break;
         cur = nxt;
         work = next_work;
@@ -591,7 +464,7 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
 // branch around the tap loads makes every vmcnt behind it a worst-case guess (measured in round 4: -15 %).  Both copies pass the same barriers.
 template <bool BNR>
 __global__ __launch_bounds__(512, 1) void conv3d_k3_wino3_mfma(ConvArgs a) {
-    if (PULPO_W3_SKEW && __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) != 0) wino3_body<BNR, 2>(a);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 8) != 0) wino3_body<BNR, 2>(a);
     else wino3_body<BNR, 0>(a);
 }
 
@@ -600,16 +473,9 @@ __global__ void pack_weight_wino3_kernel(const float* __restrict__ w, float* __r
         pulpo_conv::pack_wino3_one(w, wp, Cin, Cout, NPad, dgrad, e);
 }
 
-int wino3_enabled() {                                   // PULPO_CONV_WINO3=0: the (y, x) kernel everywhere (A/B switch)
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PULPO_CONV_WINO3"); on = e ? atoi(e) : 1; }
-    return on;
-}
-int wino3_min_k() {                                     // PULPO_CONV_WINO3_MINK: smallest reduction-channel count that takes this kernel
-    static int k = -1;
-    if (k < 0) { const char* e = getenv("PULPO_CONV_WINO3_MINK"); k = e ? atoi(e) : 16; }
-    return k < 16 ? 16 : k;                             // (at least two chunks per tile: the statistics' deferred flush counts on a second chunk barrier)
-}
+// smallest reduction-channel count that takes this kernel (at least two chunks per tile: the statistics' deferred flush counts on a second
+// chunk barrier)
+constexpr int WINO3_MIN_K = 16;
 
 }  // namespace
 
@@ -620,7 +486,7 @@ int wino3_shape_ok(int B, int D, int H, int W, int K, int N) {
     // (output channels: a multiple of 4; a cout tile of 32 may be partly empty - the 16-channel data gradient of the feedback layer runs at half
     //  the tile's columns here as it did in the (y, x) kernel, on 1.5x fewer matrix instructions)
     const int ncot = (N + Q_NT - 1) / Q_NT;
-    if (!wino3_enabled() || K < wino3_min_k() || K % Q_CH != 0 || N % 4 != 0 || (N % Q_NT != 0 && N < 16) || 3 * ncot * Q_NT > Q_TAB) return 0;
+    if (K < WINO3_MIN_K || K % Q_CH != 0 || N % 4 != 0 || (N % Q_NT != 0 && N < 16) || 3 * ncot * Q_NT > Q_TAB) return 0;
     if (D % 4 != 0 || H % TY != 0 || W % TX != 0) return 0;
     // the BatchNorm statistics rows are counted by pulpo_conv3d_k3_stat_tiles(), i.e. with conv_tz(): this kernel writes one row per 4-deep tile
     if (conv_tz(D, H, W) != 4) return 0;

@@ -8,7 +8,6 @@
 // served by L1/L2; the backward scatters with float atomics (memory-side adds, MI355X_MICROARCH.md).
 #include "common.h"
 #include "sampling.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -439,10 +438,10 @@ PULPO_API int pulpo_vecint_fwd(const float* v, float* work, int B, int D, int H,
     hipStream_t st = (hipStream_t)stream;
     const long n = (long)B * 3 * D * H * W, total = (long)B * D * H * W;
     // the one-launch form: ONE workgroup per batch element does every gather of every step - 16.6 us at 10^3 against 36 for seven launches, but 76 us
-    // at 20^3 against 38 (scripts/vecint_probe.py): up to 2048 voxels by default (PULPO_VECINT_LDS_MAXV moves it; it fits up to 8192)
-    static long lds_maxv = -1;
-    if (lds_maxv < 0) { const char* e = getenv("PULPO_VECINT_LDS_MAXV"); lds_maxv = e ? atol(e) : 2048; }
-    if (total / B <= std::min<long>(VI_MAXV, lds_maxv) && nsteps > 0) {
+    // at 20^3 against 38 (scripts/vecint_probe.py): up to 2048 voxels (it fits up to VI_MAXV)
+    constexpr long VECINT_LDS_MAXV = 2048;
+    static_assert(VECINT_LDS_MAXV <= VI_MAXV, "the one-launch form holds the whole field in LDS");
+    if (total / B <= VECINT_LDS_MAXV && nsteps > 0) {
         const size_t lds = sizeof(float) * 3 * (size_t)(total / B);
         static bool attr_set = false;
         if (!attr_set) {
@@ -467,11 +466,10 @@ PULPO_API int pulpo_vecint_fwd(const float* v, float* work, int B, int D, int H,
 }
 
 // fields the LDS-boxed backward step takes.  Round 5: from 8^3 up (16^3 before) - the 10^3 level of the metric's pyramid ran the plain scatter with a
-// device copy in front of every squaring step (14 launches of ~5 + ~10 us); PULPO_VECINT_TILED_MIN moves the threshold (A/B switch)
+// device copy in front of every squaring step (14 launches of ~5 + ~10 us)
 static bool vecint_bwd_tiled(int D, int H, int W) {
-    static int lo = -1;
-    if (lo < 0) { const char* e = getenv("PULPO_VECINT_TILED_MIN"); lo = e ? atoi(e) : 8; }
-    return D >= lo && H >= lo && W >= lo && D >= 2;
+    constexpr int TILED_MIN = 8;
+    return D >= TILED_MIN && H >= TILED_MIN && W >= TILED_MIN;
 }
 
 // floats of scratch pulpo_vecint_bwd needs: one buffer per step for the tiled scatter (zeroed by one fill), two for the plain scatter.
@@ -504,11 +502,8 @@ PULPO_API int pulpo_vecint_bwd(const float* work, const float* gout, float* gin,
             gp = tmp + (long)k * n;
             const int ntz = pulpo::cdiv(D, 4), nty = pulpo::cdiv(H, 8), ntx = pulpo::cdiv(W, 8);
             // the LAST squaring steps move by the largest fraction of the field (v / 2 at k = nsteps - 1): a box with a two-voxel rim keeps their
-            // corners in LDS where the one-voxel rim sent them to memory atomics (80^3: 88 against ~40 us for the other steps).
-            // PULPO_VECINT_R2_STEPS: how many of the last steps take the wider box (default 1; 0 = none, A/B switch)
-            static int r2 = -1;
-            if (r2 < 0) { const char* e = getenv("PULPO_VECINT_R2_STEPS"); r2 = e ? atoi(e) : 1; }
-            if (k >= nsteps - r2 && (long)D * H * W >= 64L * 64 * 64)     // (below 64^3 the wider box costs more than the fallbacks it saves: 14 against 12 us)
+            // corners in LDS where the one-voxel rim sent them to memory atomics (80^3: 88 against ~40 us for the other steps); the last step only.
+            if (k == nsteps - 1 && (long)D * H * W >= 64L * 64 * 64)     // (below 64^3 the wider box costs more than the fallbacks it saves: 14 against 12 us)
                 hipLaunchKernelGGL(vecint_bwd_tile_kernel<2>, dim3((unsigned)((long)B * ntz * nty * ntx)), dim3(256), 0, st, cur, g, gp, B, D, H, W, ntz, nty, ntx);
             else
                 hipLaunchKernelGGL(vecint_bwd_tile_kernel<1>, dim3((unsigned)((long)B * ntz * nty * ntx)), dim3(256), 0, st, cur, g, gp, B, D, H, W, ntz, nty, ntx);
