@@ -87,6 +87,12 @@ def new_cl(B: int, C: int, D: int, H: int, W: int, device, dtype=torch.float32) 
     return torch.empty((B, C, D, H, W), device=device, dtype=dtype, memory_format=CL)
 
 
+def _packed_cl(t: torch.Tensor) -> torch.Tensor:
+    """a packed channels-last copy (voxel stride = channel count, 16-byte aligned for C % 4 == 0).  to_cl() hands a channel slice of a wider
+    channels-last buffer back as it is - at an unaligned channel offset that is no operand of the vector-load kernels"""
+    return torch.empty(t.shape, device=t.device, dtype=t.dtype, memory_format=CL).copy_(t)
+
+
 def planar(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
@@ -418,7 +424,7 @@ def _conv_raw(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], o
     if algo == "wino3":
         # F(2x2x2,3x3x3): channels-last, 16-byte aligned operand and result (the deep layers' tensors are; anything else is copied into that form)
         if not vec_ok:
-            x = to_cl(x)
+            x = _packed_cl(x)
             xb, xp, xc = grid_strides(x)
         if oc != 1 or op % 4 or ob % 4 or out.data_ptr() % 16:
             raise PulpoHipError("conv3d (F(2x2x2,3x3x3) kernel): the result must be channels-last and 16-byte aligned")
@@ -429,7 +435,7 @@ def _conv_raw(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], o
         return
     if algo == "wino2":
         if (D % 4 or D * H * W < 8000) and not vec_ok:     # (volumes below 20^3 - the 10^3 level - run on the pipelined kernel only: channels-last operand)
-            x = to_cl(x)
+            x = _packed_cl(x)
             xb, xp, xc = grid_strides(x)
             vec_ok = True
         nscr = lib.query("pulpo_conv3d_k3_fwd_wino2_scratch_floats", B, D, H, W, K, N)

@@ -1,7 +1,7 @@
-"""float64 references of the training step's head, loss and field operators, written with plain torch ops (einsum, softplus, cumsum,
-index_select, grid_sample) so that they also run on the GPU at the pyramid's sizes, and the element-wise comparison the pyramid tests use.
-tests/test_oracle_golden.py pins every helper to oracle/pulpo_oracle.py at small shapes; tests/test_gpu_pyramid_ops.py holds the HIP kernels
-to them."""
+"""float64 references of the training step's head, loss, field and ConvUnit operators, written with plain torch ops (matmul, einsum,
+softplus, cumsum, index_select, grid_sample) so that they also run on the GPU at the pyramid's sizes, and the element-wise comparison the
+pyramid tests use.  tests/test_oracle_golden.py pins every helper to oracle/pulpo_oracle.py and torch.nn.functional at small shapes;
+tests/test_gpu_pyramid_ops.py and tests/test_gpu_pyramid_convunit.py hold the HIP kernels to them."""
 from typing import Optional, Sequence
 
 import torch
@@ -143,6 +143,119 @@ def resize_ref(x, size: Sequence[int], steps: Optional[Sequence[float]] = None):
         step = steps[k] if steps is not None else x.shape[d] / size[k]
         x = lin1(x, d, int(size[k]), float(step))
     return x
+
+
+# ------------------------------------------------------------------------------------------------ 3x3x3 convolution (ConvUnit)
+def _taps(x):
+    """the 27 shifted windows of the zero-padded volume, channels last: yields (kd, kh, kw, (B, D, H, W, C) view)"""
+    B, C, D, H, W = x.shape
+    xp = F.pad(x, (1, 1, 1, 1, 1, 1)).permute(0, 2, 3, 4, 1)
+    for kd in range(3):
+        for kh in range(3):
+            for kw in range(3):
+                yield kd, kh, kw, xp[:, kd:kd + D, kh:kh + H, kw:kw + W]
+
+
+def conv3_ref(x, w, b=None):
+    """Conv3d(kernel 3, padding 1) in x's dtype: out[b, o, v] = bias[o] + sum over taps and channels of x[b, c, v + tap - 1] w[o, c, tap], one
+    matmul over the channels per tap, accumulated in tap order (no F.conv3d: it runs in double on any device)"""
+    B, C, D, H, W = x.shape
+    out = None
+    for kd, kh, kw, xs in _taps(x):
+        t = torch.matmul(xs.reshape(-1, C), w[:, :, kd, kh, kw].t())
+        out = t if out is None else out.add_(t)
+    if b is not None:
+        out = out + b
+    return out.reshape(B, D, H, W, w.shape[0]).permute(0, 4, 1, 2, 3)
+
+
+def conv3_dgrad_ref(dy, w):
+    """gradient of conv3_ref with respect to x: the same convolution of dy with the transposed, tap-flipped weights"""
+    return conv3_ref(dy, w.transpose(0, 1).flip(2, 3, 4))
+
+
+def conv3_wgrad_ref(x, dy):
+    """gradient of conv3_ref with respect to w: dw[o, c, tap] = sum over batch and voxels of x[b, c, v + tap - 1] dy[b, o, v]"""
+    B, C, D, H, W = x.shape
+    N = dy.shape[1]
+    g = dy.permute(0, 2, 3, 4, 1).reshape(-1, N)
+    dw = x.new_empty(N, C, 3, 3, 3)
+    for kd, kh, kw, xs in _taps(x):
+        dw[:, :, kd, kh, kw] = torch.matmul(g.t(), xs.reshape(-1, C))
+    return dw
+
+
+def conv3_mag(x, w, b=None):
+    """A = |bias| + sum |x| |w| per output element: the magnitude sum a rounding-error bound of the convolution is proportional to"""
+    return conv3_ref(x.abs(), w.abs(), None if b is None else b.abs())
+
+
+def conv3_dgrad_mag(dy, w):
+    return conv3_dgrad_ref(dy.abs(), w.abs())
+
+
+def conv3_wgrad_mag(x, dy, random_walk: bool = False):
+    """sum |x| |dy| per weight; random_walk: sqrt(sum x^2 dy^2), the size a sum of that many independently rounded terms drifts by"""
+    if random_walk:
+        return conv3_wgrad_ref(x * x, dy * dy).sqrt()
+    return conv3_wgrad_ref(x.abs(), dy.abs())
+
+
+# ------------------------------------------------------------------------------------------------ BatchNorm3d + LeakyReLU (ConvUnit)
+def bn_train_ref(y, gamma, beta, eps: float = 1e-5, momentum: float = 0.1, running_mean=None, running_var=None, slope: float = 0.2):
+    """training-mode BatchNorm3d + LeakyReLU of a (B, C, D, H, W) tensor in its dtype.  Returns a dict: mean, var (biased), rstd,
+    scale = gamma rstd, shift = beta - mean scale, bn = y scale + shift, z = leaky_relu(bn), and - with running statistics given - their
+    update (1 - momentum) old + momentum new, the variance unbiased (n / (n - 1)), as nn.BatchNorm3d does"""
+    n = y.numel() // y.shape[1]
+    v = lambda t: t.reshape(1, -1, 1, 1, 1)
+    mean = y.mean(dim=(0, 2, 3, 4))
+    var = ((y - v(mean)) ** 2).mean(dim=(0, 2, 3, 4))
+    rstd = (var + eps).rsqrt()
+    scale = gamma * rstd
+    shift = beta - mean * scale
+    bn = y * v(scale) + v(shift)
+    r = dict(mean=mean, var=var, rstd=rstd, scale=scale, shift=shift, bn=bn, z=torch.where(bn > 0, bn, slope * bn))
+    if running_mean is not None:
+        r["running_mean"] = (1 - momentum) * running_mean + momentum * mean
+        r["running_var"] = (1 - momentum) * running_var + momentum * var * (n / max(n - 1, 1))
+    return r
+
+
+def bn_lrelu_bwd_ref(dz, y, mean, rstd, scale, shift, slope: float = 0.2):
+    """backward of bn_train_ref's z with respect to y, gamma and beta.  dbn = dz lrelu'(y scale + shift) (slope at bn <= 0, as
+    aten::leaky_relu_backward), sum_dbn and sum_dbn_c = sum dbn (y - mean) per channel, dbeta = sum_dbn, dgamma = rstd sum_dbn_c,
+    dy = scale (dbn - sum_dbn / n - (y - mean) rstd^2 sum_dbn_c / n).  Returns a dict with those names"""
+    n = y.numel() // y.shape[1]
+    v = lambda t: t.reshape(1, -1, 1, 1, 1)
+    bn = y * v(scale) + v(shift)
+    dbn = torch.where(bn > 0, dz, slope * dz)
+    yc = y - v(mean)
+    s1 = dbn.sum(dim=(0, 2, 3, 4))
+    s2 = (dbn * yc).sum(dim=(0, 2, 3, 4))
+    dy = v(scale) * (dbn - v(s1) / n - yc * v(rstd * rstd * s2) / n)
+    return dict(dbn=dbn, sum_dbn=s1, sum_dbn_c=s2, dbeta=s1, dgamma=rstd * s2, dy=dy)
+
+
+# ------------------------------------------------------------------------------------------------ pooling, x2 up-sampling + cat
+def avgpool2_ref(x):
+    """AvgPool3d(2, 2, ceil_mode=True): windows that hang over the far faces are averaged over the voxels they hold (ATen's divisor without
+    padding: 8, 4, 2 or 1 voxels), as zero-padded window sums over the window's voxel count"""
+    D, H, W = x.shape[2:]
+    xp = F.pad(x, (0, W % 2, 0, H % 2, 0, D % 2))
+    B, C, Dp, Hp, Wp = xp.shape
+    s = xp.reshape(B, C, Dp // 2, 2, Hp // 2, 2, Wp // 2, 2).sum(dim=(3, 5, 7))
+
+    def cnt(n):
+        c = torch.full(((n + 1) // 2,), 2.0, dtype=x.dtype, device=x.device)
+        if n % 2:
+            c[-1] = 1.0
+        return c
+    return s / (cnt(D).reshape(-1, 1, 1) * cnt(H).reshape(-1, 1) * cnt(W))
+
+
+def up2_cat_ref(srcs):
+    """cat([F.interpolate(s, scale_factor=2, trilinear, align_corners=False) for s in srcs], dim=1)"""
+    return torch.cat([resize_ref(s, [2 * n for n in s.shape[2:]]) for s in srcs], dim=1)
 
 
 # ------------------------------------------------------------------------------------------------ element-wise comparison

@@ -502,3 +502,96 @@ def test_pyramid_comparison_rejects_a_one_element_error():
     bad = got.clone()
     bad[-1, -1, -1, -1, -1] = float("nan")
     assert R.ratio(bad, ref, tol) == float("inf")
+
+
+CONVUNIT_PIN_SHAPES = [(1, 5, 7, (6, 5, 7)), (2, 3, 4, (5, 4, 3)), (2, 8, 6, (1, 6, 5)), (1, 2, 32, (4, 8, 8)), (1, 16, 3, (3, 1, 9))]
+
+
+@pytest.mark.parametrize("B,Cin,Cout,size", CONVUNIT_PIN_SHAPES)
+def test_pyramid_conv_references_match_conv3d(B, Cin, Cout, size):
+    """conv3_ref / conv3_dgrad_ref / conv3_wgrad_ref (27 shifted matmuls) against the oracle's convolution and autograd through F.conv3d in
+    double - odd sizes, B = 2, depth 1 and a single row - and the magnitude sums against the same operators on absolute values"""
+    import pyramid_ref as R
+    import torch.nn.functional as F
+    gen = torch.Generator().manual_seed(B * 100 + Cin * 10 + Cout)
+    dbl = dict(dtype=torch.float64)
+    x = torch.randn(B, Cin, *size, generator=gen, **dbl).requires_grad_(True)
+    w = torch.randn(Cout, Cin, 3, 3, 3, generator=gen, **dbl).requires_grad_(True)
+    b = torch.randn(Cout, generator=gen, **dbl)
+    dy = torch.randn(B, Cout, *size, generator=gen, **dbl)
+    want = O.conv3_k3(x, w, b)
+    gx, gw = torch.autograd.grad((want * dy).sum(), [x, w])
+    xd, wd = x.detach(), w.detach()
+    for got, ref in ((R.conv3_ref(xd, wd, b), want.detach()), (R.conv3_ref(xd, wd), F.conv3d(xd, wd, None, padding=1)),
+                     (R.conv3_dgrad_ref(dy, wd), gx), (R.conv3_wgrad_ref(xd, dy), gw),
+                     (R.conv3_mag(xd, wd, b), F.conv3d(xd.abs(), wd.abs(), b.abs(), padding=1)),
+                     (R.conv3_dgrad_mag(dy, wd), F.conv_transpose3d(dy.abs(), wd.abs(), None, padding=1))):
+        assert got.shape == ref.shape and float((got - ref).abs().max()) < 1e-12 * max(1.0, float(ref.abs().max()))
+    xa, da = xd.abs().requires_grad_(True), dy.abs()
+    wz = torch.zeros_like(wd).requires_grad_(True)
+    ga, = torch.autograd.grad((F.conv3d(xa, wz, None, padding=1) * da).sum(), [wz])
+    assert float((R.conv3_wgrad_mag(xd, dy) - ga).abs().max()) < 1e-12 * float(ga.abs().max())
+    g2, = torch.autograd.grad((F.conv3d(xd * xd, wz, None, padding=1) * (dy * dy)).sum(), [wz])
+    assert float((R.conv3_wgrad_mag(xd, dy, random_walk=True) - g2.sqrt()).abs().max()) < 1e-12 * float(g2.sqrt().max())
+    assert bool((R.conv3_wgrad_mag(xd, dy, random_walk=True) <= R.conv3_wgrad_mag(xd, dy) * (1 + 1e-12)).all())
+
+
+@pytest.mark.parametrize("B,C,size", [(1, 5, (6, 5, 7)), (2, 4, (5, 4, 3)), (2, 3, (1, 6, 5)), (1, 8, (4, 8, 8))])
+def test_pyramid_batchnorm_references_match_the_oracle(B, C, size):
+    """bn_train_ref / bn_lrelu_bwd_ref against F.batch_norm + F.leaky_relu (the oracle's conv_unit tail) and autograd through them in double:
+    z, the running-statistics update, dy, dgamma, dbeta; with an activation that is exactly zero after the normalisation's affine map"""
+    import pyramid_ref as R
+    import torch.nn.functional as F
+    gen = torch.Generator().manual_seed(B * 10 + C)
+    dbl = dict(dtype=torch.float64)
+    y = (torch.randn(B, C, *size, generator=gen, **dbl) * 2 + 0.5).requires_grad_(True)
+    gamma = (torch.rand(C, generator=gen, **dbl) + 0.5).requires_grad_(True)
+    beta = (torch.randn(C, generator=gen, **dbl) * 0.3).requires_grad_(True)
+    rm, rv = torch.randn(C, generator=gen, **dbl), torch.rand(C, generator=gen, **dbl) + 0.5
+    dz = torch.randn(B, C, *size, generator=gen, **dbl)
+    rm_t, rv_t = rm.clone(), rv.clone()
+    z = F.leaky_relu(F.batch_norm(y, rm_t, rv_t, gamma, beta, training=True, momentum=0.1, eps=1e-5), 0.2)
+    gy, gg, gb = torch.autograd.grad((z * dz).sum(), [y, gamma, beta])
+    yd = y.detach()
+    r = R.bn_train_ref(yd, gamma.detach(), beta.detach(), 1e-5, 0.1, rm, rv)
+    close = lambda a, b: float((a - b).abs().max()) < 1e-11 * max(1.0, float(b.abs().max()))
+    assert close(r["z"], z.detach()) and close(r["running_mean"], rm_t) and close(r["running_var"], rv_t)
+    assert close(r["mean"], yd.mean(dim=(0, 2, 3, 4))) and close(r["var"], yd.transpose(0, 1).reshape(C, -1).var(dim=1, unbiased=False))
+    assert close(r["rstd"], (r["var"] + 1e-5).rsqrt()) and close(r["scale"], gamma.detach() * r["rstd"])
+    assert close(r["shift"], beta.detach() - r["mean"] * r["scale"])
+    bw = R.bn_lrelu_bwd_ref(dz, yd, r["mean"], r["rstd"], r["scale"], r["shift"])
+    assert close(bw["dy"], gy) and close(bw["dgamma"], gg) and close(bw["dbeta"], gb)
+    assert close(bw["dbn"], torch.where(r["bn"] > 0, dz, 0.2 * dz)) and close(bw["sum_dbn"], bw["dbn"].sum(dim=(0, 2, 3, 4)))
+    assert close(bw["sum_dbn_c"], (bw["dbn"] * (yd - r["mean"].reshape(1, -1, 1, 1, 1))).sum(dim=(0, 2, 3, 4)))
+    # bn exactly 0 (scale 1, shift 0, y 0): z = 0 and the gradient takes the slope, as aten::leaky_relu_backward does
+    one, zero = torch.ones(1, **dbl), torch.zeros(1, **dbl)
+    y0 = torch.tensor([0.0, 1.0, -1.0], **dbl).reshape(1, 1, 1, 1, 3)
+    bw0 = R.bn_lrelu_bwd_ref(torch.ones_like(y0), y0, zero, one, one, zero)
+    y0g = y0.clone().requires_grad_(True)
+    g0, = torch.autograd.grad(F.leaky_relu(y0g, 0.2).sum(), [y0g])
+    assert torch.equal(bw0["dbn"], g0) and float(g0[0, 0, 0, 0, 0]) == 0.2
+
+
+@pytest.mark.parametrize("B,C,size", [(1, 3, (6, 7, 5)), (2, 4, (5, 4, 3)), (2, 2, (3, 6, 5)), (1, 1, (8, 8, 8)), (1, 5, (2, 2, 2)), (1, 2, (3, 2, 9))])
+def test_pyramid_pool_and_up2_references_match_torch(B, C, size):
+    """avgpool2_ref against the oracle's AvgPool3d(2, 2, ceil_mode=True) (divisors 8, 4, 2, 1 at ragged edges) and up2_cat_ref against
+    F.interpolate(scale_factor=2) + cat, forward and through autograd, in double (torch's pooling refuses an extent of 1: none here)"""
+    import pyramid_ref as R
+    import torch.nn.functional as F
+    gen = torch.Generator().manual_seed(sum(size) + B + C)
+    dbl = dict(dtype=torch.float64)
+    x = torch.randn(B, C, *size, generator=gen, **dbl).requires_grad_(True)
+    want = O.pool2(x)
+    up = torch.randn(want.shape, generator=gen, **dbl)
+    gw, = torch.autograd.grad((want * up).sum(), [x])
+    got = R.avgpool2_ref(x)
+    gg, = torch.autograd.grad((got * up).sum(), [x])
+    assert got.shape == want.shape and float((got - want).detach().abs().max()) < 1e-13 and float((gg - gw).abs().max()) < 1e-13
+    srcs = [torch.randn(B, c, *size, generator=gen, **dbl).requires_grad_(True) for c in (C, 3, 1)]
+    want = torch.cat([F.interpolate(s, scale_factor=2, mode="trilinear", align_corners=False) for s in srcs], dim=1)
+    up = torch.randn(want.shape, generator=gen, **dbl)
+    gw = torch.autograd.grad((want * up).sum(), srcs)
+    got = R.up2_cat_ref(srcs)
+    gg = torch.autograd.grad((got * up).sum(), srcs)
+    assert got.shape == want.shape and float((got - want).detach().abs().max()) < 1e-13
+    assert all(float((a - b).abs().max()) < 1e-13 for a, b in zip(gg, gw))
