@@ -459,6 +459,25 @@ size_t pulpo_vecint_bwd_det_ws_bytes(int B, int D, int H, int W, int nsteps);
 int pulpo_vecint_bwd_det(const float* work, const float* gout, float* gin, void* ws /*nullable if the query is 0*/, int B, int D, int H, int W,
                          int nsteps, void* stream);
 
+/* ------------------------------------------------------------------------- weight gradient under a WORKGROUP BUDGET (added within ABI 5: nothing else changed)
+ * pulpo_conv3d_k3_wgrad / _det / _kb with one more argument.  The Winograd weight-gradient kernels (pulpo_conv3d_k3_wgrad_algo >= 2) run one
+ * workgroup per CU and hold it whole; max_workgroups > 0 launches at most that many - never fewer than one per (32-channel ci tile, co tile) pair,
+ * and a multiple of 8 where the pair count allows, so that the grid lies evenly on the eight XCDs - which leaves the other CUs to the kernels of
+ * another stream (the coarse pyramid levels of the backward pass).  max_workgroups = 0 is the entry point without the suffix;
+ * the direct and the input-layer kernels ignore the budget.  Deterministic form: the slab count follows the split count, so results are
+ * bit-identical run to run for ONE budget, not across budgets.  pulpo_conv3d_k3_wgrad_grid: the workgroups such a launch takes for vectorisable
+ * operands (0: the shape runs no Winograd kernel). */
+int pulpo_conv3d_k3_wgrad_grid(int B, int D, int H, int W, int Cin, int Cout, int max_workgroups);
+int pulpo_conv3d_k3_wgrad_wg(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* dy, int64_t dy_bs, int64_t dy_ps,
+                             int64_t dy_cs, float* dw, int accumulate, float* scratch, int B, int D, int H, int W, int Cin, int Cout, void* stream,
+                             int max_workgroups);
+int pulpo_conv3d_k3_wgrad_det_wg(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* dy, int64_t dy_bs, int64_t dy_ps,
+                                 int64_t dy_cs, float* dw, int accumulate, float* scratch, float* slabs, int nslab, int B, int D, int H, int W,
+                                 int Cin, int Cout, void* stream, int max_workgroups);
+int pulpo_conv3d_k3_wgrad_kb_wg(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_kb, const float* dy, int64_t dy_bs, int64_t dy_ps, int64_t dy_kb,
+                                float* dw, int accumulate, float* scratch, float* slabs /*nullable*/, int nslab, int B, int D, int H, int W, int Cin, int Cout,
+                                void* stream, int max_workgroups);
+
 #ifdef __cplusplus
 }
 #endif

@@ -545,7 +545,8 @@ PULPO_API int pulpo_conv3d_k3_wgrad_algo(int B, int D, int H, int W, int Cin, in
 // scratch: pulpo_conv3d_k3_wgrad_scratch_floats floats.
 static int wgrad_impl(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* dy, int64_t dy_bs,
                       int64_t dy_ps, int64_t dy_cs, float* dw, int accumulate, float* scratch, float* slabs, int nslab, int B, int D, int H, int W,
-                      int Cin, int Cout, void* stream, const WgradArgs* bnf = nullptr, int64_t dy_kb = 8, int64_t in_kb = 8) {
+                      int Cin, int Cout, void* stream, const WgradArgs* bnf = nullptr, int64_t dy_kb = 8, int64_t in_kb = 8, int max_workgroups = 0) {
+    PULPO_REQUIRE(max_workgroups >= 0, "conv3d_k3_wgrad: negative workgroup budget");
     PULPO_REQUIRE(in && dy && scratch && (dw || accumulate == 2), "conv3d_k3_wgrad: null pointer");
     PULPO_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3d_k3_wgrad: bad dims");
     hipStream_t st = (hipStream_t)stream;
@@ -618,7 +619,8 @@ static int wgrad_impl(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_
     if (algo >= 2) {
         // F(2x2,3x3) in (y, x) / F(2x2x2,3x3x3), register-staged transposed operand images, z-streaming workgroups (conv3d_wgrad_w2.hip)
         // (its launcher picks its own split count: it zeroes the copies it will use and reports how many)
-        rc = pulpo_conv::launch_wgrad_w2(in, in_bs, in_ps, dy, dy_bs, dy_ps, scratch, B, D, H, W, Cin, Cout, st, slabs, nslab, &used, (long)dy_kb, (long)in_kb);
+        rc = pulpo_conv::launch_wgrad_w2(in, in_bs, in_ps, dy, dy_bs, dy_ps, scratch, B, D, H, W, Cin, Cout, st, slabs, nslab, &used, (long)dy_kb, (long)in_kb,
+                                         max_workgroups);
         return finish(rc);
     }
     PULPO_REQUIRE(dy_kb == 8 && in_kb == 8, "conv3d_k3_wgrad_kb: %dx%dx%d, %d -> %d channels does not run the F(2x2x2,3x3x3) kernel (pulpo_conv3d_k3_wgrad_algo != 3), the only reader of channel-blocked operands", D, H, W, Cin, Cout);
@@ -744,6 +746,43 @@ PULPO_API int pulpo_conv3d_k3_wgrad_kb(const float* in, int64_t in_bs, int64_t i
     PULPO_REQUIRE(dy_kb >= 8 && dy_kb % 4 == 0 && in_kb >= 8 && in_kb % 4 == 0 && (slabs == nullptr || nslab >= 1), "conv3d_k3_wgrad_kb: bad block stride / slab count");
     PULPO_REQUIRE((in_kb == 8 || Cin % 8 == 0) && (dy_kb == 8 || Cout % 8 == 0), "conv3d_k3_wgrad_kb: a channel-blocked operand has whole 8-channel blocks");
     return wgrad_impl(in, in_bs, in_ps, 1, dy, dy_bs, dy_ps, 1, dw, accumulate, scratch, slabs, slabs ? nslab : 0, B, D, H, W, Cin, Cout, stream, nullptr, dy_kb, in_kb);
+}
+
+// ---- the same three entry points with a WORKGROUP BUDGET for the Winograd kernels (pulpo_conv3d_k3_wgrad_algo >= 2): a launch of at most
+// max_workgroups workgroups (never fewer than one per (ci tile, co tile) pair, a multiple of 8 where the pair count allows) spread evenly over the
+// XCDs, so that the kernel - one workgroup holds a CU whole - can run on a second stream BESIDE kernels that cannot fill the machine.
+// max_workgroups = 0: exactly the entry point without the suffix.  The other weight-gradient kernels ignore the budget.  In the deterministic form
+// the slab count follows the split count, so the summation order (and the last bits) depend on the budget.
+PULPO_API int pulpo_conv3d_k3_wgrad_grid(int B, int D, int H, int W, int Cin, int Cout, int max_workgroups) {
+    // workgroups of that launch for 16-byte-vectorisable operands below 2 GiB (0: the shape does not run a Winograd kernel)
+    if (max_workgroups < 0 || pulpo_conv3d_k3_wgrad_algo(B, D, H, W, Cin, Cout, 1) < 2) return 0;
+    const int npair = pulpo::cdiv(Cin, 32) * pulpo::cdiv(Cout, 32);
+    const long nstep = (long)B * pulpo::cdiv(H, 8) * pulpo::cdiv(W, 8) * (pulpo_conv::wgrad_w3_depth_ok(D) ? D / 2 : D);
+    return npair * pulpo_conv::wgrad_w2_splits(npair, nstep, max_workgroups);
+}
+
+PULPO_API int pulpo_conv3d_k3_wgrad_wg(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* dy, int64_t dy_bs,
+                                       int64_t dy_ps, int64_t dy_cs, float* dw, int accumulate, float* scratch, int B, int D, int H, int W,
+                                       int Cin, int Cout, void* stream, int max_workgroups) {
+    return wgrad_impl(in, in_bs, in_ps, in_cs, dy, dy_bs, dy_ps, dy_cs, dw, accumulate, scratch, nullptr, 0, B, D, H, W, Cin, Cout, stream, nullptr, 8, 8,
+                      max_workgroups);
+}
+
+PULPO_API int pulpo_conv3d_k3_wgrad_det_wg(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* dy, int64_t dy_bs,
+                                           int64_t dy_ps, int64_t dy_cs, float* dw, int accumulate, float* scratch, float* slabs, int nslab, int B,
+                                           int D, int H, int W, int Cin, int Cout, void* stream, int max_workgroups) {
+    PULPO_REQUIRE(slabs && nslab >= 1, "conv3d_k3_wgrad_det: slabs of nslab >= 1 copies of the packed scratch required");
+    return wgrad_impl(in, in_bs, in_ps, in_cs, dy, dy_bs, dy_ps, dy_cs, dw, accumulate, scratch, slabs, nslab, B, D, H, W, Cin, Cout, stream, nullptr, 8, 8,
+                      max_workgroups);
+}
+
+PULPO_API int pulpo_conv3d_k3_wgrad_kb_wg(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_kb, const float* dy, int64_t dy_bs, int64_t dy_ps,
+                                          int64_t dy_kb, float* dw, int accumulate, float* scratch, float* slabs, int nslab, int B, int D, int H, int W,
+                                          int Cin, int Cout, void* stream, int max_workgroups) {
+    PULPO_REQUIRE(dy_kb >= 8 && dy_kb % 4 == 0 && in_kb >= 8 && in_kb % 4 == 0 && (slabs == nullptr || nslab >= 1), "conv3d_k3_wgrad_kb: bad block stride / slab count");
+    PULPO_REQUIRE((in_kb == 8 || Cin % 8 == 0) && (dy_kb == 8 || Cout % 8 == 0), "conv3d_k3_wgrad_kb: a channel-blocked operand has whole 8-channel blocks");
+    return wgrad_impl(in, in_bs, in_ps, 1, dy, dy_bs, dy_ps, 1, dw, accumulate, scratch, slabs, slabs ? nslab : 0, B, D, H, W, Cin, Cout, stream, nullptr, dy_kb, in_kb,
+                      max_workgroups);
 }
 
 namespace {

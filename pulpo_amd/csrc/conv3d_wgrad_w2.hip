@@ -910,9 +910,22 @@ namespace pulpo_conv {
 // the F(2x2x2,3x3x3) kernel where the depth is even, else the (y, x) kernel
 bool wgrad_w3_depth_ok(int D) { return D % 2 == 0 && D >= 4; }
 
+// Spatial splits of the nstep streaming steps per (ci tile, co tile) pair.  max_workgroups == 0: one workgroup per CU (256 / npair).  Else the
+// grid npair * nsplit stays within the budget (a budget below npair still takes npair workgroups, one per pair) and, where it can, is a multiple
+// of 8: the dispatcher deals workgroups round-robin over the eight XCDs and xcd_remap() is bijective for any grid size, so a 128-workgroup launch
+// occupies 16 CUs of every XCD and leaves the other 16 of each to the kernels of another stream.
+int wgrad_w2_splits(int npair, long nstep, int max_workgroups) {
+    if (max_workgroups <= 0) return (int)std::min<long>(std::max(1, 256 / npair), nstep);
+    int nsplit = (int)std::min<long>(std::max(1, max_workgroups / npair), nstep);
+    int m = 8;                                             // nsplit % m == 0  <=>  (npair * nsplit) % 8 == 0
+    for (int g = npair; g % 2 == 0 && m > 1; g /= 2) m /= 2;
+    if (nsplit >= m) nsplit -= nsplit % m;
+    return nsplit;
+}
+
 // launched by pulpo_conv3d_k3_wgrad (conv3d_wgrad.hip) for channels-last operands on large volumes; scratch must be zeroed by the caller
 int launch_wgrad_w2(const float* in, long in_bs, long in_ps, const float* go, long go_bs, long go_ps, float* scratch, int B, int D, int H, int W,
-                    int Cin, int Cout, hipStream_t st, float* slabs, int nslab, int* used_slabs, long go_kb, long in_kb) {
+                    int Cin, int Cout, hipStream_t st, float* slabs, int nslab, int* used_slabs, long go_kb, long in_kb, int max_workgroups) {
     Wgrad2Args a;
     a.split_stride = 0;
     a.go_kb = go_kb; a.in_kb = in_kb;
@@ -933,8 +946,7 @@ int launch_wgrad_w2(const float* in, long in_bs, long in_ps, const float* go, lo
     a.ncit = pulpo::cdiv(Cin, 32); a.ncot = pulpo::cdiv(Cout, 32);
     const int npair = a.ncit * a.ncot;
     const long nstep = (long)B * a.nty * a.ntx * D;
-    int nsplit = std::max(1, 256 / npair);                 // one workgroup per CU
-    nsplit = (int)std::min<long>(nsplit, nstep);
+    int nsplit = wgrad_w2_splits(npair, nstep, max_workgroups);       // (default: one workgroup per CU)
     if (slabs) nsplit = std::min(nsplit, nslab);
     a.nsplit = nsplit;
     static bool attr = false;
@@ -956,10 +968,9 @@ int launch_wgrad_w2(const float* in, long in_bs, long in_ps, const float* go, lo
         }
         // workgroups: one per CU, each with the CU's whole LDS and 2 x 234 of a SIMD's 512 registers - on a CU it holds, no kernel of the main
         // stream that needs LDS (the BatchNorm finalize / column-sum kernels between two data-gradient launches) starts until it retires.
-        // 256 workgroups leave CUs free for them.
-        constexpr int WGS3 = 256;
+        // 256 workgroups leave CUs free for them (a caller's max_workgroups leaves more: wgrad_w2_splits).
         const long nstep3 = (long)B * a.nty * a.ntx * (D / 2);
-        a.nsplit = (int)std::min<long>(std::max(1, WGS3 / npair), nstep3);
+        a.nsplit = wgrad_w2_splits(npair, nstep3, max_workgroups);
         if (slabs) a.nsplit = std::min(a.nsplit, nslab);
         if (int rc = use_slabs(a.nsplit)) return rc;
         hipLaunchKernelGGL((conv3d_k3_wgrad_w3x<0>), dim3(npair * a.nsplit), dim3(512), W3G_LDS, st, a);

@@ -32,8 +32,11 @@ int launch_unpack_wgrad(const float* packed, float* dw, int Cin, int Cout, int a
 // weight gradient, Winograd F(2x2,3x3) form (conv3d_wgrad_w2.hip): channels-last operands, accumulates into the zeroed packed scratch
 // slabs / nslab (deterministic mode, see pulpo_conv3d_k3_wgrad_det): non-null -> split s of the grid accumulates into its own zeroed copy
 // slabs + s * 27 * Cin * npad(Cout) of the packed sums instead of `scratch` (the caller adds the copies up in fixed order), at most nslab splits
+// max_workgroups > 0: a workgroup budget for the launch (wgrad_w2_splits), 0: one workgroup per CU
 int launch_wgrad_w2(const float* in, long in_bs, long in_ps, const float* go, long go_bs, long go_ps, float* scratch, int B, int D, int H, int W,
-                    int Cin, int Cout, hipStream_t st, float* slabs = nullptr, int nslab = 0, int* used_slabs = nullptr, long go_kb = 8, long in_kb = 8);
+                    int Cin, int Cout, hipStream_t st, float* slabs = nullptr, int nslab = 0, int* used_slabs = nullptr, long go_kb = 8, long in_kb = 8,
+                    int max_workgroups = 0);
+int wgrad_w2_splits(int npair, long nstep, int max_workgroups);     // spatial splits per (ci tile, co tile) pair under that budget
 // scratch[e] += slabs[0][e] + slabs[1][e] + ... (fixed order, e < n): the ordered second stage of the deterministic weight gradient
 int launch_wgrad_slab_reduce(float* scratch, const float* slabs, int nslab, long n, hipStream_t st, int npad_ = 64, int cols = 64);
 bool wgrad_w3_depth_ok(int D);                      // the F(2x2x2,3x3x3) weight-gradient kernel takes this depth (even, at least 4)

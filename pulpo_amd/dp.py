@@ -209,6 +209,15 @@ def _gradient_buckets(model: nn.Module):
     return params, ranges, triggers
 
 
+# Defaults of the coarse window (ops.CoarseWindow; DataParallelStepper's constructor arguments of the same names), as measured at 160^3 / T5 / L4
+# (profiles/r6_window_ab.txt).
+COARSE_WINDOW = True                 # fp32, non-deterministic steps with a side stream
+COARSE_VOXELS = 20 ** 3              # levels of at most this many voxels per batch element are "coarse"
+COARSE_MAX_WORKGROUPS = 192          # workgroup budget of every weight gradient on the window's side stream (128: slower than in line)
+COARSE_DEFER_FLOP = 1.0e12           # weight-gradient FLOP (54 Cin Cout B V per job) held back above the window for it (160^3: all 0.85e12)
+COARSE_EXIT_WAIT = False             # the main stream does not wait where the window closes: the overrun competes on its capped grid
+
+
 class DataParallelStepper:
     """forward + backward + gradient all-reduce + Adam for one batch of volume pairs per rank (weak scaling).
 
@@ -218,7 +227,9 @@ class DataParallelStepper:
     the compute stream, and the Adam step waits for all buckets."""
 
     def __init__(self, model: nn.Module, lr: Optional[float] = None, overlap: bool = True, async_wgrad: bool = True,
-                 freeze_gc: Optional[bool] = None, graph: Optional[bool] = None):
+                 freeze_gc: Optional[bool] = None, graph: Optional[bool] = None, coarse_window: Optional[bool] = None,
+                 coarse_voxels: Optional[int] = None, max_workgroups: Optional[int] = None, defer_flop: Optional[float] = None,
+                 exit_wait: Optional[bool] = None):
         self.model = model
         # graph: zero_grad + forward + backward + gradient finishing are captured into ONE HIP graph on the third step and replayed from then on
         # (step() only; the gradient exchange, the fused Adam update - its step count is a kernel argument - and the weight re-pack stay eager).
@@ -234,6 +245,14 @@ class DataParallelStepper:
         dev0 = next(model.parameters()).device
         self.async_wgrad = bool(async_wgrad) and dev0.type == "cuda" and os.environ.get("PULPO_ASYNC_WGRAD", "1") != "0"
         self._side = torch.cuda.Stream(device=dev0) if self.async_wgrad else None
+        # the coarse window: weight gradients beside the coarse pyramid levels of the backward pass, on a capped grid (ops.CoarseWindow).
+        # coarse_window None = the module default; the other four are its tunables (None = COARSE_* above).
+        from . import ops
+        self._want_window = bool(COARSE_WINDOW if coarse_window is None else coarse_window)
+        self._window = ops.CoarseWindow(self._side, COARSE_VOXELS if coarse_voxels is None else coarse_voxels,
+                                        COARSE_MAX_WORKGROUPS if max_workgroups is None else max_workgroups,
+                                        COARSE_DEFER_FLOP if defer_flop is None else defer_flop,
+                                        COARSE_EXIT_WAIT if exit_wait is None else exit_wait) if self._side is not None else None
         self._one = None
         params, ranges, triggers = _gradient_buckets(model)
         self.arena = FlatArena(model, params)
@@ -298,6 +317,9 @@ class DataParallelStepper:
         ops._BN_TILE_PARTS.clear()                 # (BatchNorm-backward sums a data-gradient kernel left for a unit whose backward never ran)
         ops.DIRECT_PARAM_GRADS = bool(direct)      # conv / BN backward kernels add straight into the arena's .grad views
         ops.ASYNC_WGRAD_STREAM = self._side if (self.wgrad_on_side_stream() and direct) else None
+        ops.COARSE_WINDOW = self._window if (self.coarse_window() and direct) else None
+        if ops.COARSE_WINDOW is not None:
+            self._window.begin()
         self._in_backward = True
         try:
             if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
@@ -305,6 +327,8 @@ class DataParallelStepper:
             loss.backward(self._one)
         except BaseException:
             ops.reset_param_grad_buffers(self.model)        # deferred gradient sums of an interrupted backward pass are void
+            if self._window is not None:
+                self._window.held = []                      # (and so are the weight gradients still held back for the coarse window)
             raise
         finally:
             self._in_backward = False
@@ -312,6 +336,9 @@ class DataParallelStepper:
             ops.DIRECT_PARAM_GRADS = False
             ops.join_async_wgrad()             # (also finishes the deferred weight / bias gradients in one launch)
             ops.ASYNC_WGRAD_STREAM = None
+            if ops.COARSE_WINDOW is not None:
+                self._window.begin()           # (an interrupted pass: no operand stays referenced)
+            ops.COARSE_WINDOW = None
 
     def reduce_and_update(self, reduced_elsewhere: bool = False) -> None:
         """gradient exchange (what is left of it) + fused Adam.  reduced_elsewhere: a DistributedDataParallel wrapper has already averaged
@@ -431,9 +458,21 @@ class DataParallelStepper:
         from . import ops
         return ops.CONV_PRECISION == "bf16"
 
+    def coarse_window(self) -> bool:
+        """whether this step's backward pass runs the coarse window (ops.CoarseWindow): the weight gradients of the coarse pyramid levels, and the
+        last ones produced above them, on the side stream under a workgroup budget.  fp32, non-deterministic steps only: the bf16 configurations
+        keep all their weight gradients on the side stream (wgrad_on_side_stream), and a budget changes the split count - the summation order -
+        that deterministic mode pins."""
+        from . import ops
+        return bool(self._want_window and self._window is not None and not self.wgrad_on_side_stream() and not ops.DETERMINISTIC
+                    and ops.CONV_PRECISION == "fp32")
+
     def describe(self) -> dict:
+        w = self._window
         return {"overlap": bool(self.overlap and world() > 1), "async_wgrad": bool(self.async_wgrad), "wgrad_side_stream": self.wgrad_on_side_stream(),
-                "buckets": len(self.buckets)}
+                "buckets": len(self.buckets), "coarse_window": self.coarse_window(),
+                "coarse_window_settings": None if w is None else {"coarse_voxels": w.coarse_voxels, "max_workgroups": w.max_workgroups,
+                                                                  "defer_flop": w.defer_flop, "exit_wait": w.exit_wait, "deferred_last_step": w.deferred_last}}
 
 
 class ArenaAdam(torch.optim.Adam):

@@ -648,9 +648,10 @@ def _blocked_dy_ok(x, y, weight, wpt, need_dx: bool, need_dw: bool) -> bool:
 
 
 def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Optional[torch.Tensor] = None,
-               owner: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+               owner: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> Optional[torch.Tensor]:
     """weight gradient; `into` -> accumulated into that (Cout,Cin,3,3,3) tensor in place, returns None.  With `owner` (the weight parameter,
-    data-parallel stepper) the accumulation is DEFERRED to flush_param_grads(): the packed sums stay in the parameter's persistent scratch."""
+    data-parallel stepper) the accumulation is DEFERRED to flush_param_grads(): the packed sums stay in the parameter's persistent scratch.
+    max_workgroups > 0: the fp32 Winograd kernels launch at most that many workgroups (pulpo_conv3d_k3_wgrad_wg; the other kernels ignore it)."""
     B, _, D, H, W = _dims5(x)
     if is_blocked(x) and (_use_bf16(Cin) or lib.query("pulpo_conv3d_k3_wgrad_algo", B, D, H, W, Cin, Cout, 1) != 3):
         x = blocked_to_cl(x)                         # (a blocked operand outside the F(2x2x2,3x3x3) kernel's shapes: a copy - BLOCKED_Z switched between passes)
@@ -667,6 +668,7 @@ def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Opt
     db, dp, dc = (dy.bs, dy.ps, 1) if isinstance(dy, _BlockedGrad) else grid_strides(dy)
     t0 = _trace_begin()
     sfx = "_bf16" if _use_bf16(Cin) else ""
+    wg, wga = ("_wg", (int(max_workgroups),)) if max_workgroups else ("", ())
     det = ()
     if DETERMINISTIC:
         # one zero-initialised copy of the packed sums per spatial split of the grid (<= ~110 MB, transient), added up in fixed order
@@ -676,8 +678,8 @@ def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Opt
     if blocked:
         # (_blocked_dy_ok has checked: fp32 operands, channels-last x, the F(2x2x2,3x3x3) weight-gradient kernel takes the shape)
         dyt, _, _, dkb, _ = _opnd(dy)
-        lib.call("pulpo_conv3d_k3_wgrad_kb", _ptr(xt), xb, xp, xkb, _ptr(dyt), db, dp, dkb, _ptr(dw), 2 if deferred else int(into is not None), _ptr(scratch),
-                 *(det if det else (None, 0)), B, D, H, W, Cin, Cout, _stream())
+        lib.call("pulpo_conv3d_k3_wgrad_kb" + wg, _ptr(xt), xb, xp, xkb, _ptr(dyt), db, dp, dkb, _ptr(dw), 2 if deferred else int(into is not None), _ptr(scratch),
+                 *(det if det else (None, 0)), B, D, H, W, Cin, Cout, _stream(), *wga)
     elif sfx:
         if x.dtype != dy.dtype:                      # (one storage type per launch; a mixed pair - a user's fp32 input to a bf16-storage unit - is rare)
             x, dy = x.float(), dy.float()
@@ -690,8 +692,8 @@ def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Opt
             x, dy = x.float(), dy.float()
             xb, xp, xc = grid_strides(x)
             db, dp, dc = grid_strides(dy)
-        lib.call("pulpo_conv3d_k3_wgrad_det" if det else "pulpo_conv3d_k3_wgrad", _ptr(x), xb, xp, xc, _ptr(dy), db, dp, dc, _ptr(dw),
-                 2 if deferred else int(into is not None), _ptr(scratch), *det, B, D, H, W, Cin, Cout, _stream())
+        lib.call(("pulpo_conv3d_k3_wgrad_det" if det else "pulpo_conv3d_k3_wgrad") + wg, _ptr(x), xb, xp, xc, _ptr(dy), db, dp, dc, _ptr(dw),
+                 2 if deferred else int(into is not None), _ptr(scratch), *det, B, D, H, W, Cin, Cout, _stream(), *wga)
     if deferred and not _pending_src(scratch):
         # (ONE finishing job per scratch: a unit applied twice in a step - shared weights, two forward passes - has accumulated both weight
         #  gradients into the same packed sums by the time the job runs)
@@ -731,7 +733,109 @@ def join_async_wgrad():
     """make the current stream wait for every weight gradient queued on the side stream, then finish the deferred parameter gradients"""
     if ASYNC_WGRAD_STREAM is not None:
         torch.cuda.current_stream().wait_stream(ASYNC_WGRAD_STREAM)
+    if COARSE_WINDOW is not None:
+        COARSE_WINDOW.join()
     flush_param_grads()
+
+
+# ---- The coarse window (round 6).  In the backward pass of a pyramid the levels of at most `coarse_voxels` voxels (20^3 and 10^3 at 160^3: the
+# latent levels 3 and 4, then DownPath's two coarsest blocks) are a stretch of ~2.5 ms in which no kernel of the main stream can fill the machine:
+# a hundred 5 - 12 us kernels on a few workgroups, data gradients of 270 work items, weight gradients whose split count is capped by their step
+# count.  Weight gradients are leaves - nothing reads them before the gradient exchange / Adam - so
+#   * the window's own weight gradients go to the side stream instead of in line, and
+#   * the last weight gradients produced ABOVE the window (the 40^3 / 80^3 latent levels), as many as fit `defer_flop`, are HELD BACK and queued
+#     on the side stream when the window opens,
+# all under a workgroup budget (`max_workgroups`, pulpo_conv3d_k3_wgrad_wg): a full-grid F(2x2x2,3x3x3) weight gradient holds every CU whole and
+# can only time-slice with the main stream (why "everything on the side stream" lost for fp32, DESIGN.md section 3), a 192-workgroup one holds 24
+# CUs per XCD and leaves the other 8 to the main stream's small kernels (measured: 192 is the best budget, 128 loses to in-line launches, and
+# the side stream may overrun the window - profiles/r6_window_ab.txt).  Which jobs to hold is learnt from the previous backward pass (the
+# sequence of weight gradients seen above the window; its last entries within the FLOP budget), so the first pass of a model holds nothing.
+# Set by dp.DataParallelStepper.backward (fp32, non-deterministic, direct parameter gradients); None = off (plain autograd use).
+COARSE_WINDOW = None
+
+
+class CoarseWindow:
+    ABOVE, INSIDE, BELOW = 0, 1, 2
+
+    def __init__(self, stream, coarse_voxels: int, max_workgroups: int, defer_flop: float, exit_wait: bool):
+        self.stream, self.coarse_voxels, self.max_workgroups = stream, int(coarse_voxels), int(max_workgroups)
+        self.defer_flop, self.exit_wait = float(defer_flop), bool(exit_wait)
+        self._plan_sig, self._plan = None, frozenset()
+        self.deferred_last = 0                   # weight gradients held back in the last backward pass (tests / describe())
+        self.begin()
+
+    def begin(self) -> None:
+        """a backward pass starts"""
+        self.state, self.held, self.seen, self.used = self.ABOVE, [], [], False
+        self.keep = []                           # operands of launches queued on the side stream the main stream has not waited for yet
+
+    def _budgeted(self, x, dy, Cin, Cout) -> bool:
+        """does this weight gradient run a kernel that takes the workgroup budget?"""
+        B, _, D, H, W = _dims5(x)
+        return (not _use_bf16(Cin) and x.dtype == torch.float32 and dy.dtype == torch.float32
+                and lib.query("pulpo_conv3d_k3_wgrad_grid", B, D, H, W, Cin, Cout, self.max_workgroups) > 0)
+
+    def _to_side(self, jobs) -> None:
+        side = self.stream
+        side.wait_stream(torch.cuda.current_stream())        # after everything queued so far (the operands' producers)
+        with torch.cuda.stream(side):
+            for x, dy, Cin, Cout, slot_w, owner in jobs:
+                _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=owner, max_workgroups=self.max_workgroups)
+        # The operands stay referenced until the main stream - the stream they were allocated on - has waited for the side stream (the window's
+        # exit, or join()): from then on everything the main stream does is ordered behind these launches and the allocator may hand the memory
+        # out again.  (Not record_stream(): a block it has marked returns to the pool whenever its event happens to have completed, so which block
+        # the next tensors get, and with it the allocator's rounding, would vary from step to step.)
+        self.keep.extend(t for x, dy, *_ in jobs for t in (x, dy))
+        self.used = True
+
+    def visit(self, voxels: int) -> None:
+        """a convolution's backward on a volume of `voxels` voxels per batch element begins: opens / closes the window"""
+        if voxels <= self.coarse_voxels:
+            if self.state != self.INSIDE:
+                if self.state == self.ABOVE:     # the plan of the next pass: the last jobs seen above the window that fit the FLOP budget
+                    sig = tuple(self.seen)
+                    if sig != self._plan_sig:
+                        plan, total = set(), 0.0
+                        for key, flop in reversed(sig):
+                            if total + flop > self.defer_flop:
+                                break
+                            plan.add(key)
+                            total += flop
+                        self._plan_sig, self._plan = sig, frozenset(plan)
+                self.deferred_last = len(self.held)
+                if self.held:
+                    self._to_side(self.held)
+                    self.held = []
+                self.state = self.INSIDE
+        elif self.state == self.INSIDE:
+            self.state = self.BELOW
+            if self.exit_wait and self.used:     # the full-grid levels that follow do not share the machine with an overrun of the side stream
+                torch.cuda.current_stream().wait_stream(self.stream)
+                self.keep = []
+
+    def wgrad(self, x, dy, Cin, Cout, slot_w, owner) -> None:
+        """the weight gradient of the unit whose backward visit() has just seen"""
+        job = (x, dy, Cin, Cout, slot_w, owner)
+        if self.state == self.INSIDE:
+            self._to_side([job])
+            return
+        if self.state == self.ABOVE and self._budgeted(x, dy, Cin, Cout):
+            B, _, D, H, W = _dims5(x)
+            key = id(owner)
+            self.seen.append((key, 54.0 * Cin * Cout * B * D * H * W))
+            if key in self._plan:
+                self.held.append(job)
+                return
+        _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=owner)
+
+    def join(self) -> None:
+        """launch what is still held (a pass without a coarse level, a gradient bucket that leaves early) in line and wait for the side stream"""
+        for x, dy, Cin, Cout, slot_w, owner in self.held:
+            _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=owner)
+        self.held = []
+        if self.used:
+            torch.cuda.current_stream().wait_stream(self.stream)
+        self.keep = []
 
 
 # ---- BatchNorm-backward reduction inside the data-gradient convolution.  In a ConvSequence unit u consumes z = lrelu(bn(y)) of unit u-1,
@@ -996,6 +1100,9 @@ class _ConvBNLReLU(torch.autograd.Function):
                      _ptr(part), _stream())
             _hbm_end(t0, "bn_lrelu_bwd_reduce", (_esize(dz) + _esize(y)) * Cout * npix)                # read dz, y
         w_p, b_p, g_p, be_p = ctx.params
+        win = COARSE_WINDOW
+        if win is not None:
+            win.visit(D * H * W)
         slot_w, slot_b, slot_g, slot_be = (_grad_slot(t) if need else None
                                            for t, need in zip((w_p, b_p, g_p, be_p), ctx.needs_input_grad[1:5]))
         direct_bn = slot_g is not None and slot_be is not None
@@ -1055,7 +1162,11 @@ class _ConvBNLReLU(torch.autograd.Function):
             _PENDING_KEEPALIVE.append(part2)
         dbias = _colsum(part2, nblk, Cout, into=slot_b) if (ctx.needs_input_grad[2] and not defer_b) else None
         dbeta, dgamma = (None, None) if direct_bn else (tot[:Cout], tot[Cout:])
-        dw = _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=w_p if slot_w is not None else None) if (ctx.needs_input_grad[1] and not defer_w) else None
+        if win is not None and ctx.needs_input_grad[1] and slot_w is not None and not defer_w:
+            win.wgrad(x, dy, Cin, Cout, slot_w, w_p)             # in line, held back for the coarse window, or on its side stream
+            dw = None
+        else:
+            dw = _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=w_p if slot_w is not None else None) if (ctx.needs_input_grad[1] and not defer_w) else None
         dx = None
         if ctx.needs_input_grad[0]:
             # (the bf16-operand kernel takes operand and result in one storage type; every other kernel is fp32)

@@ -85,3 +85,32 @@ if covered:
         else: cm.append([s, e])
     cov = sum(in_holes(s, e) for s, e in cm)
 print(f"  nothing running at all inside the holes: {hole_ms - cov/1e6:.2f} ms")
+# ---- the second queue burst by burst (the coarse window of the backward pass: weight gradients on a capped grid beside the coarse levels' kernels):
+# what the main queue runs during a burst, and what it runs while the burst's LAST kernel is still going (an overrun into the full-grid levels)
+side = sorted((s, e, n) for q, v in queues.items() if q != main for s, e, n in v)
+if side:
+    bursts = [[side[0]]]
+    for k in side[1:]:
+        if k[0] - max(x[1] for x in bursts[-1]) > 1_000_000: bursts.append([k])       # more than 1 ms apart: another burst
+        else: bursts[-1].append(k)
+    mq = sorted(queues[main])
+    print(f"second queue(s): {len(side)} kernels in {len(bursts)} bursts; the last {min(4, len(bursts))}:")
+    for b in bursts[-4:]:
+        bs, be = b[0][0], max(x[1] for x in b)
+        busy = union([(s, e) for s, e, n in b])
+        names = collections.Counter(n for s, e, n in b)
+        print(f" burst at +{(bs - t0)/1e6:.2f} ms: {len(b)} kernels over {(be - bs)/1e3:.0f} us, busy {busy/1e3:.0f} us: " + ", ".join(f"{c} x {n}" for n, c in names.most_common(4)))
+        print("   first kernels: " + ", ".join(f"{n} {(e - s)/1e3:.0f} us" for s, e, n in b[:6]))
+        inside = [(s, e, n) for s, e, n in mq if e > bs and s < be]
+        ia = collections.defaultdict(lambda: [0, 0])
+        for s, e, n in inside:
+            ia[n][0] += 1; ia[n][1] += min(e, be) - max(s, bs)
+        print(f"   main queue meanwhile: {len(inside)} kernels, busy {union([(max(s, bs), min(e, be)) for s, e, n in inside])/1e3:.0f} us" if inside else "   main queue meanwhile: nothing")
+        for n, (c, d) in sorted(ia.items(), key=lambda kv: -kv[1][1])[:8]:
+            print(f"     {n:50s} {c:4d} {d/1e3:8.0f} us")
+        ls, le, ln = max(b, key=lambda x: x[1])
+        tail = [(s, e, n) for s, e, n in mq if e > ls and s < le and n.startswith(MATRIX)]
+        print(f"   last kernel {ln} {(le - ls)/1e3:.0f} us; main-queue matrix kernels beside it: " + (", ".join(f"{n} {(e - s)/1e3:.0f} us (shared {(min(e, le) - max(s, ls))/1e3:.0f} us)" for s, e, n in tail) or "none"))
+        nxt = [(s, e, n) for s, e, n in mq if s >= be][:1]
+        if nxt:
+            print(f"   main queue's next kernel after the burst: {nxt[0][2]} {(nxt[0][1] - nxt[0][0])/1e3:.0f} us, starting {(nxt[0][0] - be)/1e3:.1f} us after it")
