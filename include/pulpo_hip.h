@@ -478,6 +478,30 @@ int pulpo_conv3d_k3_wgrad_kb_wg(const float* in, int64_t in_bs, int64_t in_ps, i
                                 float* dw, int accumulate, float* scratch, float* slabs /*nullable*/, int nslab, int B, int D, int H, int W, int Cin, int Cout,
                                 void* stream, int max_workgroups);
 
+/* ------------------------------------------------------------------------- 1x1x1 heads on the PRE-NORM tensor of the ConvUnit in front of them (added within ABI 5: nothing else changed)
+ * The last ConvUnit before a head (src/components/pulpo.py:254 sample_merge_block -> mu_sigma; src/network_blocks.py:77-81 VelocityField's last unit -> its
+ * 1x1x1 convolution) produces an activation z = leaky_relu(scale * y + shift) that only the head reads, and the gradient dz the head returns is read only by
+ * that unit's batch_norm_backward.  These entry points form both per element, so neither tensor exists:
+ *  - pulpo_heads_fwd_bn_t: pulpo_heads_fwd on (y, coef, slope) - coef is the block pulpo_bn_fwd_finalize wrote; fp32 results bit-identical to
+ *    pulpo_bn_lrelu_apply followed by pulpo_heads_fwd (one shared expression, csrc/head_bn.h).
+ *  - pulpo_heads_bwd_bn_t: pulpo_heads_bwd (partial: the same rows, pulpo_heads_bwd_blocks of them) AND pulpo_bn_lrelu_bwd_reduce in one pass: bnpart =
+ *    [pulpo_heads_bwd_blocks][2][C] rows for pulpo_bn_bwd_finalize.  Nothing of C channels is written.
+ *  - pulpo_bn_lrelu_bwd_apply_heads_t / _kb_t: pulpo_bn_lrelu_bwd_apply_t / _kb_t with dz formed from the head's planar operands (g0 for nout 3; g0, g1, g2,
+ *    eps, sigma for nout 6, as pulpo_heads_bwd takes them); partial2: pulpo_bn_bwd_blocks(B * V, C) rows of C floats.
+ * fp32 activations only (bf16 activation storage keeps the separate passes).  Groups of four channels where C % 4 == 0 and the operands are 16-byte
+ * aligned, single channels otherwise (C <= 256: e.g. a channel slice at an odd offset of a wider buffer).  Run-to-run deterministic. */
+int pulpo_heads_fwd_bn_t(const float* y, int64_t ps, const float* coef, float slope, const float* Wt, const float* bias, const float* eps /*nullable*/,
+                         float* o0, float* o1, float* o2, int nout, int B, int64_t V, int C, void* stream);
+int pulpo_heads_bwd_bn_t(const float* y, int64_t ps, const float* coef, float slope, const float* Wt, const float* g0, const float* g1, const float* g2,
+                         const float* eps, const float* sigma, float* partial /*[blocks][nout*C+nout]*/, float* bnpart /*[blocks][2][C]*/, int nout, int B,
+                         int64_t V, int C, void* stream);
+int pulpo_bn_lrelu_bwd_apply_heads_t(const float* y, int64_t yps, const float* coef, const double* totd, float slope, const float* Wt, const float* g0,
+                                     const float* g1, const float* g2, const float* eps, const float* sigma, float* dy, int64_t dyps, float* partial2,
+                                     int nout, int B, int64_t V, int C, void* stream);
+int pulpo_bn_lrelu_bwd_apply_heads_kb_t(const float* y, int64_t yps, const float* coef, const double* totd, float slope, const float* Wt, const float* g0,
+                                        const float* g1, const float* g2, const float* eps, const float* sigma, float* dy, int64_t dyps, int64_t dykb,
+                                        float* partial2, int nout, int B, int64_t V, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

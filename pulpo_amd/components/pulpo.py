@@ -100,9 +100,18 @@ class PULPoEncoder(nn.Module):
 
     def forward(self, down_activation: torch.Tensor, feedback: Optional[torch.Tensor] = None):
         h = down_activation
-        if feedback is not None:
-            h = self.sample_merge_block(ops.cat_channels(feedback, down_activation))     # (the buffer itself where both were produced into it)
         sampler = self.sampler
+        if feedback is not None:
+            h = ops.cat_channels(feedback, down_activation)                              # (the buffer itself where both were produced into it)
+            blk = self.sample_merge_block
+            # the block's output has one reader, the mu / sigma head: it runs on the last unit's pre-norm tensor (ConvUnit.forward), the activation
+            # and its gradient are never written.  Not with a user-supplied sampler, hooks on the block, eval mode, slices or zdim != 3.
+            # (down_activation itself - the coarsest level's case - is a skip tensor with other readers and keeps the separate passes)
+            if (sampler is gauss_sampler or isinstance(sampler, FixedNoiseSampler)) and self.mu_sigma.zdim == 3 and blk.head_ready(h, self.zdim):
+                eps = sampler.fixed_eps if isinstance(sampler, FixedNoiseSampler) else torch.randn(
+                    (h.shape[0], self.zdim) + tuple(h.shape[2:]), device=h.device, dtype=torch.float32)
+                return blk(h, head=("mu_sigma", self.mu_sigma, eps))
+            h = blk(h)
         if sampler is gauss_sampler:                         # fused: noise drawn once, sample formed in the head kernel
             eps = torch.randn((h.shape[0], self.zdim) + tuple(h.shape[2:]), device=h.device, dtype=torch.float32)
             return self.mu_sigma.sample(h, eps)

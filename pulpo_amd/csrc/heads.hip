@@ -6,6 +6,7 @@
 // HBM-bound (reads C floats, writes 3-9 per voxel): 8 lanes share one voxel, each lane streams float4 channel
 // slices (one 128-byte line per voxel per step), partial dot products are combined with wave shuffles.
 #include "act_io.h"
+#include "head_bn.h"
 
 namespace {
 
@@ -129,13 +130,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const TH* __restrict__ h
             if (live) {
                 const float* sv = sc[it * RB + row];
                 float dpre[6];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const float gz = sv[6 + j];
-                    dpre[j] = sv[j] + gz;                                      // dmu = g0 + g2
-                    const float gs = sv[3 + j] + gz * sv[9 + j];               // dsigma = g1 + g2 * eps (eps absent: stored as 0)
-                    dpre[3 + j] = gs * (1.f - expf(-sv[12 + j]));
-                }
+                pulpo::head_dpre6(sv, dpre);                                   // dmu = g0 + g2 ; dsigma = g1 + g2 * eps (eps absent: stored as 0)
                 float o[VEC];
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) o[k] = 0.f;
@@ -143,7 +138,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const TH* __restrict__ h
                 for (int j = 0; j < NOUT; ++j) {
                     db[j] += dpre[j];
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) { o[k] += dpre[j] * w[j][k]; dw[j][k] += dpre[j] * x[k]; }
+                    for (int k = 0; k < VEC; ++k) { o[k] += dpre[j] * w[j][k]; dw[j][k] = fmaf(dpre[j], x[k], dw[j][k]); }    // (fmaf spelled out: heads_bwd_bn_kernel adds the same bits)
                 }
                 pulpo::stv<VEC>(dh + p * dps + c, o);
             }
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const TH* __restrict__ h
             for (int j = 0; j < NOUT; ++j) {
                 db[j] += dpre[j];
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) { o[k] += dpre[j] * w[j][k]; dw[j][k] += dpre[j] * x[k]; }
+                for (int k = 0; k < VEC; ++k) { o[k] += dpre[j] * w[j][k]; dw[j][k] = fmaf(dpre[j], x[k], dw[j][k]); }    // (fmaf spelled out: heads_bwd_bn_kernel adds the same bits)
             }
             pulpo::stv<VEC>(dh + p * dps + c, o);
         }
@@ -181,6 +176,282 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const TH* __restrict__ h
         float t = 0.f;
         for (int r = 0; r < RB; ++r) t += red[r * ROWLEN + j];
         partial[(long)blockIdx.x * ROWLEN + j] = t;
+    }
+}
+
+// ---- the head on the PRE-NORM tensor of the ConvUnit in front of it (PULPoEncoder.sample_merge_block -> mu_sigma, VelocityField's last unit -> its
+// 1x1x1 convolution).  That unit's output z = lrelu(scale * y + shift) has no reader but the head, and the gradient dz the head sends back none but
+// the unit's BatchNorm backward: both are formed where they are used (z: three operations per element in kernels that wait for memory; dz: 3 - 6
+// products per element from planar values the kernels hold anyway), so the chain reads y three times and writes dy once instead of ten passes.
+// fp32 activations.  coef: the unit's coefficient block (pulpo_bn_fwd_finalize).
+template <int NOUT, bool VEC>
+__global__ __launch_bounds__(256) void heads_fwd_bn_kernel(const float* __restrict__ y, long ps, const float* __restrict__ coef, float slope,
+                                                             const float* __restrict__ Wt, const float* __restrict__ bias, const float* __restrict__ eps,
+                                                             float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2, int B, long V, int C) {
+    extern __shared__ float wl[];              // [NOUT][C] weights | [C] scale | [C] shift
+    float* scl = wl + NOUT * C;
+    float* shl = scl + C;
+    for (int j = threadIdx.x; j < NOUT * C; j += blockDim.x) wl[j] = Wt[j];
+    for (int j = threadIdx.x; j < C; j += blockDim.x) { scl[j] = coef[2 * C + j]; shl[j] = coef[3 * C + j]; }
+    __syncthreads();
+    const int g = threadIdx.x & (G - 1);
+    const long npix = (long)B * V;
+    const long pstep = (long)gridDim.x * (blockDim.x / G);
+    for (long p0 = (long)blockIdx.x * (blockDim.x / G); p0 < npix; p0 += pstep) {   // uniform trip count per block
+        const long p = p0 + threadIdx.x / G;
+        const bool live = p < npix;
+        float acc[NOUT];
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) acc[j] = 0.f;
+        if (live) {
+            const float* hp = y + p * ps;
+            if constexpr (VEC) {
+                for (int c = 4 * g; c < C; c += 4 * G) {
+                    float x[4];
+                    pulpo::ldv<4>(hp + c, x);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) x[k] = pulpo::bn_lrelu(x[k], scl[c + k], shl[c + k], slope);
+#pragma unroll
+                    for (int j = 0; j < NOUT; ++j) {
+                        const float* w = wl + j * C + c;
+                        acc[j] += x[0] * w[0] + x[1] * w[1] + x[2] * w[2] + x[3] * w[3];
+                    }
+                }
+            } else {
+                for (int c = g; c < C; c += G) {
+                    const float x = pulpo::bn_lrelu(hp[c], scl[c], shl[c], slope);
+#pragma unroll
+                    for (int j = 0; j < NOUT; ++j) acc[j] += x * wl[j * C + c];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) acc[j] = group_sum(acc[j]);
+        if (live && g < 3) {                   // (as heads_fwd_kernel: lane g < 3 finishes output component g)
+            const long b = p / V, v = p - b * V;
+            const long at = b * 3 * V + v + g * V;
+            const float a_lo = g == 0 ? acc[0] : g == 1 ? acc[1] : acc[2];
+            if constexpr (NOUT == 3) {
+                o0[at] = a_lo + bias[g];
+            } else {
+                const float a_hi = g == 0 ? acc[3] : g == 1 ? acc[4] : acc[5];
+                const float mu = a_lo + bias[g];
+                const float sg = softplus_f(a_hi + bias[3 + g]);
+                o0[at] = mu;
+                o1[at] = sg;
+                o2[at] = eps != nullptr ? mu + sg * eps[at] : mu;
+            }
+        }
+    }
+}
+
+// backward of the head AND the first pass of the unit's BatchNorm / LeakyReLU backward (heads_bwd_kernel + bn_lrelu_bwd_reduce_kernel): a thread
+// owns VEC channels and walks the block's pixels as in heads_bwd_kernel; it reads y, forms z for dW and dz = sum_j dpre[j] * W[j][c] for
+//   dbn = dz * lrelu'(scale * y + shift);   bnpart[blk][0][c] = sum dbn,  bnpart[blk][1][c] = sum dbn * (y - m32)
+// (the reduce kernel's arithmetic, m32 = the fp32-rounded batch mean; rows as pulpo_bn_bwd_finalize reads them) and stores neither.
+// partial[blk][NOUT*C + NOUT] as heads_bwd_kernel writes it.  Fixed block partition, fixed summation order: the same bits on every run.
+template <int NOUT, int VEC>
+__global__ __launch_bounds__(256) void heads_bwd_bn_kernel(const float* __restrict__ y, long ps, const float* __restrict__ coef, float slope,
+                                                             const float* __restrict__ Wt, const float* __restrict__ g0, const float* __restrict__ g1,
+                                                             const float* __restrict__ g2, const float* __restrict__ eps, const float* __restrict__ sigma,
+                                                             float* __restrict__ partial, float* __restrict__ bnpart, int B, long V, int C) {
+    extern __shared__ float red[];             // [RB][NOUT*C + NOUT + 2*C]
+    const int CV = C / VEC, RB = blockDim.x / CV;
+    const int col = threadIdx.x % CV, row = threadIdx.x / CV;
+    const int c = col * VEC;
+    const int ROWLEN = NOUT * C + NOUT, ROWLEN2 = ROWLEN + 2 * C;
+    const long npix = (long)B * V;
+    const bool mine = row < RB;
+    float dw[NOUT][VEC], db[NOUT], w[NOUT][VEC], sc[VEC], sh[VEC], m32[VEC], s0[VEC], s1[VEC];
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) {
+        db[j] = 0.f;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) { dw[j][k] = 0.f; w[j][k] = mine ? Wt[j * C + c + k] : 0.f; }
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        s0[k] = s1[k] = 0.f;
+        sc[k] = mine ? coef[2 * C + c + k] : 0.f;
+        sh[k] = mine ? coef[3 * C + c + k] : 0.f;
+        m32[k] = mine ? coef[c + k] : 0.f;
+    }
+    // one pixel: v = y, dpre = the head's pre-activation gradients
+    auto pixel = [&](const float (&v)[VEC], const float (&dpre)[NOUT]) {
+        float x[VEC], o[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) { x[k] = pulpo::bn_lrelu(v[k], sc[k], sh[k], slope); o[k] = 0.f; }
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) {
+            db[j] += dpre[j];
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) { o[k] = fmaf(dpre[j], w[j][k], o[k]); dw[j][k] = fmaf(dpre[j], x[k], dw[j][k]); }
+        }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const float bn = v[k] * sc[k] + sh[k];
+            const float d = bn > 0.f ? o[k] : o[k] * slope;
+            s0[k] += d;
+            s1[k] = fmaf(d, v[k] - m32[k], s1[k]);
+        }
+    };
+    if constexpr (NOUT == 6) {
+        // (the 15 planar values of a pixel: fetched once per row and shared through LDS, two buffers by trip parity - see heads_bwd_kernel)
+        float (*sv16)[16] = reinterpret_cast<float (*)[16]>(red + (size_t)RB * ROWLEN2);       // [2 * RB][16]
+        int it = 0;
+        for (long pb = (long)blockIdx.x * RB; pb < npix; pb += (long)gridDim.x * RB, it ^= 1) {
+            const long p = pb + row;
+            const bool live = mine && p < npix;
+            const long pc = live ? p : 0;
+            const long b = pc / V, v_ = pc - b * V;
+            const long base = b * 3 * V + v_;
+            if (live)
+                for (int q = col; q < 15; q += CV) {
+                    const int arr = q / 3, j = q - 3 * arr;
+                    const float* src = arr == 0 ? g0 : arr == 1 ? g1 : arr == 2 ? g2 : arr == 3 ? eps : sigma;
+                    sv16[it * RB + row][q] = src != nullptr ? src[base + j * V] : 0.f;
+                }
+            float v[VEC];
+            if (live) pulpo::ldv<VEC>(y + p * ps + c, v);
+            __syncthreads();
+            if (live) {
+                float dpre[6];
+                pulpo::head_dpre6(sv16[it * RB + row], dpre);
+                pixel(v, dpre);
+            }
+        }
+    } else if (mine) {
+        for (long p = (long)blockIdx.x * RB + row; p < npix; p += (long)gridDim.x * RB) {
+            const long b = p / V, v_ = p - b * V;
+            const long base = b * 3 * V + v_;
+            float dpre[NOUT], v[VEC];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dpre[j] = g0[base + j * V];
+            pulpo::ldv<VEC>(y + p * ps + c, v);
+            pixel(v, dpre);
+        }
+    }
+    if (mine) {
+        float* r = red + (size_t)row * ROWLEN2;
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) r[j * C + c + k] = dw[j][k];
+            if (col == 0) r[NOUT * C + j] = db[j];
+        }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) { r[ROWLEN + c + k] = s0[k]; r[ROWLEN + C + c + k] = s1[k]; }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < ROWLEN2; j += blockDim.x) {
+        float t = 0.f;
+        for (int r = 0; r < RB; ++r) t += red[(size_t)r * ROWLEN2 + j];
+        if (j < ROWLEN) partial[(long)blockIdx.x * ROWLEN + j] = t;
+        else bnpart[(long)blockIdx.x * 2 * C + (j - ROWLEN)] = t;
+    }
+}
+
+// second pass of that BatchNorm backward (bn_lrelu_bwd_apply_kernel) with dz formed per element from the head's planar operands:
+//   dy = A * dbn + B * (y - m32) + C  with the constants of pulpo::bn_bwd_constants in LDS;  partial2[blk][c] = sum dy (conv-bias gradient).
+// dy: channel c of pixel p at (c / 8) * dykb + p * dyps + c % 8 (dykb = 8: channels-last; else the channel-blocked layout, see pulpo_bn_lrelu_bwd_apply_kb_t)
+template <int NOUT, int VEC>
+__global__ __launch_bounds__(256) void bn_lrelu_bwd_apply_heads_kernel(const float* __restrict__ y, long yps, const float* __restrict__ coef,
+                                                                         const double* __restrict__ totd, float slope, const float* __restrict__ Wt,
+                                                                         const float* __restrict__ g0, const float* __restrict__ g1, const float* __restrict__ g2,
+                                                                         const float* __restrict__ eps, const float* __restrict__ sigma, float* __restrict__ dy,
+                                                                         long dyps, long dykb, float* __restrict__ partial2, int B, long V, int C) {
+    extern __shared__ float red[];             // [RB][C] sums of dy | [6][C] constants | [NOUT][C] head weights | (NOUT 6) [2 * RB][16] planar operands
+    const int CV = C / VEC, RB = blockDim.x / CV;
+    const int col = threadIdx.x % CV, row = threadIdx.x / CV;
+    const int c = col * VEC;
+    const long npix = (long)B * V;
+    const bool mine = row < RB;
+    float* kst = red + RB * C;
+    float* wl = kst + 6 * C;
+    float (*sv16)[16] = reinterpret_cast<float (*)[16]>(wl + NOUT * C);
+    pulpo::bn_bwd_constants(kst, coef, totd, C);
+    for (int j = threadIdx.x; j < NOUT * C; j += blockDim.x) wl[j] = Wt[j];
+    __syncthreads();
+    float s0[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) s0[k] = 0.f;
+    const long cdst = (long)(c >> 3) * dykb + (c & 7);
+    int it = 0;
+    for (long pb = (long)blockIdx.x * RB; pb < npix; pb += (long)gridDim.x * RB, it ^= 1) {     // uniform trip count per block (NOUT 6: one barrier per trip)
+        const long p = pb + row;
+        const bool live = mine && p < npix;
+        const long pc = live ? p : 0;
+        const long b = pc / V, v_ = pc - b * V;
+        const long base = b * 3 * V + v_;
+        float dpre[NOUT], v[VEC], g[VEC], o[VEC];
+        if constexpr (NOUT == 6) {
+            if (live)
+                for (int q = col; q < 15; q += CV) {
+                    const int arr = q / 3, j = q - 3 * arr;
+                    const float* src = arr == 0 ? g0 : arr == 1 ? g1 : arr == 2 ? g2 : arr == 3 ? eps : sigma;
+                    sv16[it * RB + row][q] = src != nullptr ? src[base + j * V] : 0.f;
+                }
+            if (live) pulpo::ldv<VEC>(y + p * yps + c, v);
+            __syncthreads();
+            if (live) pulpo::head_dpre6(sv16[it * RB + row], dpre);
+        } else if (live) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dpre[j] = g0[base + j * V];
+            pulpo::ldv<VEC>(y + p * yps + c, v);
+        }
+        if (!live) continue;
+        int cl = c;                                 // (opaque: the constants are READ here every time, not kept in registers - see bn_lrelu_bwd_apply_kernel)
+        asm volatile("" : "+v"(cl));
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) g[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) {            // dz, the expression of heads_bwd_bn_kernel
+            float wj[VEC];
+            pulpo::ldv<VEC>(wl + j * C + cl, wj);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) g[k] = fmaf(dpre[j], wj[k], g[k]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            float sh[VEC], sc[VEC];
+            pulpo::ldv<VEC>(kst + 0 * C + cl, sc);
+            pulpo::ldv<VEC>(kst + 1 * C + cl, sh);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const float bn = v[k] * sc[k] + sh[k];
+                g[k] = sc[k] * (bn > 0.f ? g[k] : g[k] * slope);          // scale * dbn
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            float m32[VEC], cb[VEC], chi[VEC];
+            pulpo::ldv<VEC>(kst + 2 * C + cl, m32);
+            pulpo::ldv<VEC>(kst + 3 * C + cl, cb);
+            pulpo::ldv<VEC>(kst + 4 * C + cl, chi);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) v[k] = fmaf(cb[k], v[k] - m32[k], chi[k]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            float clo[VEC];
+            pulpo::ldv<VEC>(kst + 5 * C + cl, clo);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                o[k] = (g[k] + v[k]) + clo[k];
+                s0[k] += o[k];
+            }
+        }
+        pulpo::stv<VEC>(dy + p * dyps + cdst, o);
+    }
+    if (mine) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) red[row * C + c + k] = s0[k];
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < C; j += blockDim.x) {
+        float t = 0.f;
+        for (int r = 0; r < RB; ++r) t += red[r * C + j];
+        partial2[(long)blockIdx.x * C + j] = t;
     }
 }
 
@@ -257,4 +528,97 @@ PULPO_API int pulpo_heads_bwd_t(const void* h, int h_dt, int64_t ps, const float
 PULPO_API int pulpo_heads_bwd(const float* h, int64_t ps, const float* Wt, const float* g0, const float* g1, const float* g2, const float* eps,
                               const float* sigma, float* dh, int64_t dps, float* partial, int nout, int B, int64_t V, int C, void* stream) {
     return pulpo_heads_bwd_t(h, 0, ps, Wt, g0, g1, g2, eps, sigma, dh, dps, partial, nout, B, V, C, stream);
+}
+
+// ---- the same heads on the pre-norm tensor y of the ConvUnit in front of them (fp32, strides in elements; coef: that unit's coefficient block,
+// slope: its LeakyReLU).  Channel groups of four where C % 4 == 0 and everything is 16-byte aligned, else single channels (C <= 256).
+PULPO_API int pulpo_heads_fwd_bn_t(const float* y, int64_t ps, const float* coef, float slope, const float* Wt, const float* bias, const float* eps,
+                                   float* o0, float* o1, float* o2, int nout, int B, int64_t V, int C, void* stream) {
+    PULPO_REQUIRE(y && coef && Wt && bias && o0 && B > 0 && V > 0 && C > 0, "heads_fwd_bn: bad arguments");
+    PULPO_REQUIRE(nout == 3 || (nout == 6 && o1 && o2), "heads_fwd_bn: nout must be 3 or 6");
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = C % 4 == 0 && ps % 4 == 0 && (((uintptr_t)y) % 16) == 0;
+    const int nblk = heads_blocks((long)B * V);
+    const size_t lds = (size_t)(nout + 2) * C * sizeof(float);
+    PULPO_REQUIRE(lds <= 64 * 1024, "heads_fwd_bn: LDS budget exceeded");
+    if (nout == 3) {
+        if (vec) hipLaunchKernelGGL((heads_fwd_bn_kernel<3, true>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
+        else hipLaunchKernelGGL((heads_fwd_bn_kernel<3, false>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
+    } else {
+        if (vec) hipLaunchKernelGGL((heads_fwd_bn_kernel<6, true>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
+        else hipLaunchKernelGGL((heads_fwd_bn_kernel<6, false>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
+    }
+    return pulpo::check_launch("heads_fwd_bn");
+}
+
+// partial: [pulpo_heads_bwd_blocks][nout*C + nout] as pulpo_heads_bwd_t; bnpart: [pulpo_heads_bwd_blocks][2][C], the rows pulpo_bn_bwd_finalize takes
+// (nrow = pulpo_heads_bwd_blocks).  The gradient of the unit's output is not written: pulpo_bn_lrelu_bwd_apply_heads_t forms it again.
+PULPO_API int pulpo_heads_bwd_bn_t(const float* y, int64_t ps, const float* coef, float slope, const float* Wt, const float* g0, const float* g1,
+                                   const float* g2, const float* eps, const float* sigma, float* partial, float* bnpart, int nout, int B, int64_t V, int C,
+                                   void* stream) {
+    PULPO_REQUIRE(y && coef && Wt && partial && bnpart && B > 0 && V > 0 && C > 0, "heads_bwd_bn: bad arguments");
+    PULPO_REQUIRE((nout == 3 && g0) || (nout == 6 && sigma), "heads_bwd_bn: nout must be 3 (with g0) or 6 (with sigma)");
+    hipStream_t st = (hipStream_t)stream;
+    const bool v4 = C % 4 == 0 && ps % 4 == 0 && (((uintptr_t)y) % 16) == 0;
+    PULPO_REQUIRE(C / (v4 ? 4 : 1) <= 256, "heads_bwd_bn: too many channels (%d%s)", C, v4 || C % 4 != 0 ? "" : ", unaligned operands");
+    const int nblk = pulpo_heads_bwd_blocks(B, V, C);
+    const int CV = C / (v4 ? 4 : 1);
+    int RB = std::max(1, 256 / CV);
+    auto lds_of = [&](int rb) { return ((size_t)rb * (nout * C + nout + 2 * C) + (nout == 6 ? (size_t)2 * rb * 16 : 0)) * sizeof(float); };
+    // (a handful of channels: 256 pixel rows of sums and planar operands pass 64 KB - fewer rows per workgroup, i.e. fewer threads; the kernel takes its
+    //  row count from the launch and walks the pixels in grid strides)
+    while (RB > 1 && lds_of(RB) > 64 * 1024) RB /= 2;
+    const size_t lds = lds_of(RB);
+    PULPO_REQUIRE(lds <= 64 * 1024, "heads_bwd_bn: LDS budget exceeded");
+    const int nthr = RB == std::max(1, 256 / CV) ? 256 : RB * CV;          // (the kernel's row count is blockDim.x / CV)
+    if (nout == 3) {
+        if (v4) hipLaunchKernelGGL((heads_bwd_bn_kernel<3, 4>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, partial, bnpart, B, V, C);
+        else hipLaunchKernelGGL((heads_bwd_bn_kernel<3, 1>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, partial, bnpart, B, V, C);
+    } else {
+        if (v4) hipLaunchKernelGGL((heads_bwd_bn_kernel<6, 4>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, partial, bnpart, B, V, C);
+        else hipLaunchKernelGGL((heads_bwd_bn_kernel<6, 1>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, partial, bnpart, B, V, C);
+    }
+    return pulpo::check_launch("heads_bwd_bn");
+}
+
+PULPO_API int pulpo_bn_bwd_blocks(int64_t npix, int C);      // (norm_act.hip)
+
+namespace {
+int apply_heads(const float* y, long yps, const float* coef, const double* totd, float slope, const float* Wt, const float* g0, const float* g1, const float* g2,
+                const float* eps, const float* sigma, float* dy, long dyps, long dykb, float* partial2, int nout, int B, long V, int C, hipStream_t st) {
+    const bool v4 = C % 4 == 0 && yps % 4 == 0 && dyps % 4 == 0 && dykb % 4 == 0 && ((((uintptr_t)y) | ((uintptr_t)dy)) % 16) == 0;
+    if (C / (v4 ? 4 : 1) > 256) return pulpo::fail(-1, "bn_lrelu_bwd_apply_heads: too many channels (%d%s)", C, v4 || C % 4 != 0 ? "" : ", unaligned operands");
+    const int nblk = pulpo_bn_bwd_blocks((long)B * V, C);
+    const int RB = std::max(1, 256 / (C / (v4 ? 4 : 1)));
+    const size_t lds = ((size_t)(RB + 6 + nout) * C + (nout == 6 ? (size_t)2 * RB * 16 : 0)) * sizeof(float);
+    if (lds > 64 * 1024) return pulpo::fail(-1, "bn_lrelu_bwd_apply_heads: LDS budget exceeded");
+    if (nout == 3) {
+        if (v4) hipLaunchKernelGGL((bn_lrelu_bwd_apply_heads_kernel<3, 4>), dim3(nblk), dim3(256), lds, st, y, yps, coef, totd, slope, Wt, g0, g1, g2, eps, sigma, dy, dyps, dykb, partial2, B, V, C);
+        else hipLaunchKernelGGL((bn_lrelu_bwd_apply_heads_kernel<3, 1>), dim3(nblk), dim3(256), lds, st, y, yps, coef, totd, slope, Wt, g0, g1, g2, eps, sigma, dy, dyps, dykb, partial2, B, V, C);
+    } else {
+        if (v4) hipLaunchKernelGGL((bn_lrelu_bwd_apply_heads_kernel<6, 4>), dim3(nblk), dim3(256), lds, st, y, yps, coef, totd, slope, Wt, g0, g1, g2, eps, sigma, dy, dyps, dykb, partial2, B, V, C);
+        else hipLaunchKernelGGL((bn_lrelu_bwd_apply_heads_kernel<6, 1>), dim3(nblk), dim3(256), lds, st, y, yps, coef, totd, slope, Wt, g0, g1, g2, eps, sigma, dy, dyps, dykb, partial2, B, V, C);
+    }
+    return pulpo::check_launch("bn_lrelu_bwd_apply_heads");
+}
+}  // namespace
+
+// the second BatchNorm-backward pass of that unit: totd from pulpo_bn_bwd_finalize over bnpart; partial2: [pulpo_bn_bwd_blocks(B * V, C)][C] as
+// pulpo_bn_lrelu_bwd_apply_t.  The head's operands as pulpo_heads_bwd_bn_t took them.
+PULPO_API int pulpo_bn_lrelu_bwd_apply_heads_t(const float* y, int64_t yps, const float* coef, const double* totd, float slope, const float* Wt, const float* g0,
+                                               const float* g1, const float* g2, const float* eps, const float* sigma, float* dy, int64_t dyps, float* partial2,
+                                               int nout, int B, int64_t V, int C, void* stream) {
+    PULPO_REQUIRE(y && coef && totd && Wt && dy && partial2 && B > 0 && V > 0 && C > 0, "bn_lrelu_bwd_apply_heads: bad arguments");
+    PULPO_REQUIRE((nout == 3 && g0) || (nout == 6 && sigma), "bn_lrelu_bwd_apply_heads: nout must be 3 (with g0) or 6 (with sigma)");
+    return apply_heads(y, (long)yps, coef, totd, slope, Wt, g0, g1, g2, eps, sigma, dy, (long)dyps, 8, partial2, nout, B, (long)V, C, (hipStream_t)stream);
+}
+
+// ... with dy in the channel-blocked layout [C / 8][pixels][8] (dyps = 8, dykb = pixels * 8; C % 8 == 0), as pulpo_bn_lrelu_bwd_apply_kb_t
+PULPO_API int pulpo_bn_lrelu_bwd_apply_heads_kb_t(const float* y, int64_t yps, const float* coef, const double* totd, float slope, const float* Wt,
+                                                  const float* g0, const float* g1, const float* g2, const float* eps, const float* sigma, float* dy,
+                                                  int64_t dyps, int64_t dykb, float* partial2, int nout, int B, int64_t V, int C, void* stream) {
+    PULPO_REQUIRE(y && coef && totd && Wt && dy && partial2 && B > 0 && V > 0 && C > 0, "bn_lrelu_bwd_apply_heads_kb: bad arguments");
+    PULPO_REQUIRE((nout == 3 && g0) || (nout == 6 && sigma), "bn_lrelu_bwd_apply_heads_kb: nout must be 3 (with g0) or 6 (with sigma)");
+    PULPO_REQUIRE(C % 8 == 0 && dyps % 4 == 0 && dyps >= 8 && dykb % 4 == 0 && dykb >= 8, "bn_lrelu_bwd_apply_heads_kb: C %% 8 == 0, strides in whole four-channel groups");
+    return apply_heads(y, (long)yps, coef, totd, slope, Wt, g0, g1, g2, eps, sigma, dy, (long)dyps, (long)dykb, partial2, nout, B, (long)V, C, (hipStream_t)stream);
 }

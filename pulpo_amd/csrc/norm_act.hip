@@ -4,6 +4,7 @@
 // so a channel slice of a concatenation buffer is a valid operand).  Reductions are two-stage and deterministic:
 // per-block fp32 partials, then a double-precision column sum.
 #include "act_io.h"
+#include "head_bn.h"
 
 namespace {
 
@@ -155,10 +156,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_apply_kernel(const TY* __restric
         Vec<VEC>::ld(scale + c, sc);
         Vec<VEC>::ld(shift + c, sh);
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            const float t = v[k] * sc[k] + sh[k];
-            v[k] = t > 0.f ? t : t * slope;
-        }
+        for (int k = 0; k < VEC; ++k) v[k] = pulpo::bn_lrelu(v[k], sc[k], sh[k], slope);      // (head_bn.h: the head kernels form z with the same expression)
         pulpo::stv<VEC>(z + (long)(c >> 3) * zkb + p * zps + (c & 7), v);      // (zkb = 8: channels-last, c; else the channel-blocked layout [C / 8][pixels][8])
     }
 }
@@ -308,20 +306,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_bwd_apply_kernel(const TG* __res
     const int col = threadIdx.x % CV, row = threadIdx.x / CV;
     const int c = col * VEC;
     float* kst = red + RB * C;
-    for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
-        const double* cd = reinterpret_cast<const double*>(coef + 4 * C);
-        const float sc_ = coef[2 * C + ch], m32_ = coef[ch];
-        const double mean = cd[ch], rstd = cd[C + ch], c1 = totd[ch], c2 = totd[C + ch];
-        const double b = -(double)sc_ * c2 * rstd;
-        const double cc = -(double)sc_ * (c1 + c2 * rstd * ((double)m32_ - mean));
-        const float chi_ = (float)cc;
-        kst[0 * C + ch] = sc_;
-        kst[1 * C + ch] = coef[3 * C + ch];
-        kst[2 * C + ch] = m32_;
-        kst[3 * C + ch] = (float)b;
-        kst[4 * C + ch] = chi_;
-        kst[5 * C + ch] = (float)(cc - (double)chi_);
-    }
+    pulpo::bn_bwd_constants(kst, coef, totd, C);
     __syncthreads();
     float s0[VEC];
 #pragma unroll

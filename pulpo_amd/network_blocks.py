@@ -39,6 +39,14 @@ def _ndims(input_size: Sequence[int], who: str) -> int:
     return nd
 
 
+def _hooked(*modules: nn.Module) -> bool:
+    """does a forward (pre-)hook watch one of the modules (or every module)?  Such a hook sees the module's output tensor: a second reader"""
+    from torch.nn.modules import module as _m
+    if _m._global_forward_hooks or _m._global_forward_pre_hooks:
+        return True
+    return any(m._forward_hooks or m._forward_pre_hooks for m in modules)
+
+
 class ConvUnit(nn.Module):
     """Conv3d(3x3x3, pad 1) -> BatchNorm3d -> LeakyReLU(0.2): one fused HIP pipeline (src/network_blocks.py:11-29)"""
 
@@ -53,10 +61,24 @@ class ConvUnit(nn.Module):
             nn.LeakyReLU(negative_slope=0.2, inplace=True),
         )
 
-    def forward(self, x: torch.Tensor, pool_after: bool = False, out=None, pool_only: bool = False, blocked_out: bool = False):
+    def head_ready(self, x, zdim: int = 3) -> bool:
+        """may forward(x, head=...) run?  The head must be the ONLY reader of this unit's activation - the caller answers for the data flow, this for the
+        hooks on the unit, its BatchNorm and its LeakyReLU - and the unit in training mode on a volume (ops.head_bn_ok)"""
+        return self.training and not _hooked(self, self._op, *self._op) and ops.head_bn_ok(x, True, zdim)
+
+    def forward(self, x: torch.Tensor, pool_after: bool = False, out=None, pool_only: bool = False, blocked_out: bool = False, head=None):
         """out: (buffer, first channel), pool_only: the caller reads only AvgPool(result) -> (result or None, pooled or None); blocked_out: the result in the
-        channel-blocked form (C / 8, B, D, H, W, 8) for the next unit of a ConvSequence; see ops.conv_bn_lrelu"""
+        channel-blocked form (C / 8, B, D, H, W, 8) for the next unit of a ConvSequence; see ops.conv_bn_lrelu.
+        head (after head_ready()): ("mu_sigma", MuSigmaBlock, noise or None) -> (mu, sigma, sample), or ("to3", 1x1x1 Conv3d, None) -> its output: the head
+        runs on this unit's pre-norm tensor and the activation between them is never written (ops.conv_bn_lrelu_mu_sigma / _to3)"""
         conv, bn = self._op[0], self._op[1]
+        if head is not None:
+            kind, mod, noise = head
+            unit_args = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+            if kind == "mu_sigma":
+                cs = mod._conv_sigma[0]
+                return ops.conv_bn_lrelu_mu_sigma(x, unit_args, bn.momentum, bn.eps, mod._conv_mu.weight, mod._conv_mu.bias, cs.weight, cs.bias, noise)
+            return ops.conv_bn_lrelu_to3(x, unit_args, bn.momentum, bn.eps, mod.weight, mod.bias)
         use_batch_stats = self.training or bn.running_mean is None
         # running statistics and num_batches_tracked are updated inside the BatchNorm finalize kernel
         return ops.conv_bn_lrelu(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
@@ -74,15 +96,22 @@ class ConvSequence(nn.Module):
         units += [ConvUnit(input_size, out_channels) for _ in range(depth - 1)]
         self._op = nn.Sequential(*units)
 
-    def forward(self, x: torch.Tensor, pool_after: bool = False, out=None, pool_only: bool = False):
+    def head_ready(self, x, zdim: int = 3) -> bool:
+        """may forward(x, head=...) run (ConvUnit.head_ready for the last unit; no hook on the sequence either)?"""
+        return not _hooked(self, self._op) and self._op[-1].head_ready(x, zdim)
+
+    def forward(self, x: torch.Tensor, pool_after: bool = False, out=None, pool_only: bool = False, head=None):
         """pool_after: the caller pools the result next (DownPath) - the last unit then writes AvgPool(result) along with it;
         out: (buffer, first channel) - the last unit writes its result into that channel range of a wider buffer (ops.conv_bn_lrelu);
-        pool_only (with pool_after): the caller reads ONLY the pooled result -> returns (result or None, pooled or None)"""
-        if not pool_after and out is None and not ops.BLOCKED_Z:
+        pool_only (with pool_after): the caller reads ONLY the pooled result -> returns (result or None, pooled or None);
+        head (after head_ready()): the caller reads ONLY a 1x1x1 head of the result -> returns the head's outputs (ConvUnit.forward)"""
+        if not pool_after and out is None and not ops.BLOCKED_Z and head is None:
             return self._op(x)                       # (the reference's own call: hooks on the Sequential fire)
         n = len(self._op)
         for k, unit in enumerate(self._op):
             last = k + 1 == n
+            if last and head is not None:
+                return unit(x, head=head)
             if last and pool_only:
                 return unit(x, pool_after=pool_after, out=out, pool_only=True)
             # an activation between two units has no reader but the next unit's convolution and weight gradient: where those run the F(2x2x2,3x3x3)
@@ -141,9 +170,12 @@ class VelocityField(nn.Module):
             conv = self._op[0]
             full = ops.conv3d_k3(x, conv.weight, conv.bias)         # 'valid' conv = interior of the zero-padded one
             return (full[:, :, 1:-1, 1:-1, 1:-1] if full.dim() == 5 else full[:, :, 1:-1, 1:-1]).contiguous()
-        for unit in list(self._op)[:-1]:
+        units, last = list(self._op)[:-1], self._op[-1]
+        for k, unit in enumerate(units):
+            # the last unit's activation is read by the 1x1x1 convolution alone: that head runs on the unit's pre-norm tensor (ConvUnit.forward)
+            if k + 1 == len(units) and last.out_channels == 3 and not _hooked(self._op, last) and unit.head_ready(x):
+                return unit(x, head=("to3", last, None))
             x = unit(x)
-        last = self._op[-1]
         return ops.conv1x1_to3(x, last.weight, last.bias)
 
 

@@ -951,10 +951,14 @@ class _ConvBNLReLU(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, num_batches_tracked, training: bool, momentum: float, eps: float,
-                bn_src=None, pool_after: bool = False, pool_only: bool = False, blocked_out: bool = False):
+                bn_src=None, pool_after: bool = False, pool_only: bool = False, blocked_out: bool = False, head_w=None, head_b=None, head_eps=None,
+                head_nout: int = 0, head_params=None):
+        """head_nout = 3 / 6 (conv_bn_lrelu_heads): the unit's activation is read by a 1x1x1 head (head_w [nout][Cout], head_b [nout], head_eps) and by
+        nothing else - the node returns the head's outputs, and neither the activation nor its gradient is written"""
         _require_gpu(x, act=True)
         _require_gpu(weight, bias, gamma, beta)
         ctx.bn_src = bn_src
+        ctx.head = None
         # x: (B, C, D, H, W), or the blocked output (C / 8, B, D, H, W, 8) of the previous ConvUnit of the sequence (is_blocked)
         ctx.dx_blocked = is_blocked(x)
         if not ctx.dx_blocked:
@@ -992,6 +996,23 @@ class _ConvBNLReLU(torch.autograd.Function):
                 _conv_raw(x, wp, bias, y, Cin, Cout, None, coef=coef)
                 return y
             _conv_raw(x, wp, bias, y, Cin, Cout, None)
+        if head_nout:
+            # (conv_bn_lrelu_heads has checked: training statistics, fp32 storage, no pooling, no output slot)
+            _require_gpu(head_w, head_b, head_eps)
+            V = D * H * W
+            outs = [torch.empty((B, 3, D, H, W), device=dev, dtype=torch.float32) for _ in range(1 if head_nout == 3 else 3)]
+            epsc = planar(head_eps) if head_eps is not None else None
+            t0 = _hbm_begin("heads_fwd_bn")
+            lib.call("pulpo_heads_fwd_bn_t", _ptr(y), y.stride(4), _ptr(coef), LRELU_SLOPE, _ptr(head_w), _ptr(head_b), _ptr(epsc), _ptr(outs[0]),
+                     _ptr(outs[1]) if head_nout == 6 else None, _ptr(outs[2]) if head_nout == 6 else None, head_nout, B, V, Cout, _stream())
+            _hbm_end(t0, "heads_fwd_bn", B * V * (4.0 * Cout + 4.0 * (12 if head_nout == 6 else 3)))       # read y (+ eps), write mu / sigma / z (or the field)
+            ctx.save_for_backward(x, weight, y, coef, head_w, epsc, outs[1] if head_nout == 6 else None)
+            ctx.training = training
+            ctx.params = (weight, bias, gamma, beta)
+            ctx.head = (head_nout, head_params)
+            ctx.pooled_out = ctx.pool_only = False
+            _TLS.produced = None
+            return outs[0] if head_nout == 3 else tuple(outs)
         # pool_only: nobody reads the un-pooled activation (DownPath levels above the first latent level: only AvgPool(z) goes on) - it is not written
         pool_only = bool(pool_only and pool_after and lib.query("pulpo_bn_lrelu_apply_pool2_ok", Cout, y.stride(4), Cout, Cout))
         blocked_out = bool(blocked_out and training and not pool_after and not pool_only and zdt == torch.float32 and ydt == torch.float32 and Cout % 8 == 0)
@@ -1038,16 +1059,19 @@ class _ConvBNLReLU(torch.autograd.Function):
         return z
 
     @staticmethod
-    def backward(ctx, dz, dpool=None):
-        if ctx.pool_only:                            # (the node's only output is the pooled tensor)
+    def backward(ctx, dz, dpool=None, dsample=None):
+        head = ctx.head
+        if head is not None:                         # (the node's outputs are the head's: the field, or mu / sigma / sample)
+            head_g, dz, dpool = (dz, dpool, dsample), None, None
+        elif ctx.pool_only:                          # (the node's only output is the pooled tensor)
             dz, dpool = None, dz
-        x, weight, y, coef = ctx.saved_tensors
+        x, weight, y, coef = ctx.saved_tensors[:4]
         B, Cin, D, H, W = _dims5(x)
         Cout = weight.shape[0]
         dev = x.device
         npix = B * D * H * W
         nblk = lib.query("pulpo_bn_bwd_blocks", npix, Cout)
-        NG = 15                                      # inputs of forward()
+        NG = 20                                      # inputs of forward()
         dz_blk = is_blocked(dz)                      # the gradient of a blocked activation arrives blocked (the next unit's data-gradient kernel wrote it so)
         if dz_blk and (dz.dtype != torch.float32 or not dz.is_contiguous() or tuple(blocked_shape(dz)) != (B, Cout, D, H, W)):
             dz, dz_blk = blocked_to_cl(dz.float()), False
@@ -1074,7 +1098,7 @@ class _ConvBNLReLU(torch.autograd.Function):
                     if gz is not None:
                         gin = gin + gz
                 dz = gin
-        elif dz is None:
+        elif dz is None and head is None:
             return (None,) * NG
         tiles = None
         if pooled_src is not None:
@@ -1085,7 +1109,7 @@ class _ConvBNLReLU(torch.autograd.Function):
                      y.stride(4), _ptr(coef), LRELU_SLOPE, _ptr(part), B, D, H, W, Cout, _stream())
             # read the pooled gradient, the skip gradient and y (the summed gradient is not written)
             _hbm_end(t0, "avgpool2_bwd_bnred", Cout * (_esize(gp) * (gp.numel() // Cout + (npix if gz is not None else 0)) + _esize(y) * npix))
-        else:
+        elif head is None:
             if not dz_blk:
                 dz = to_cl(dz)
             # first pass (sum dbn, sum dbn * xhat): already done by the epilogue of the data-gradient convolution that PRODUCED dz, if that was
@@ -1093,6 +1117,25 @@ class _ConvBNLReLU(torch.autograd.Function):
             tiles = _take_bn_tile_parts(y, coef, dz)
             if tiles is None and dz_blk:             # (the separate reduction pass reads channels-last: autograd summed several gradients of z - a copy)
                 dz, dz_blk = blocked_to_cl(dz), False
+        heads_src, head_dw, head_db = None, None, None
+        if head is not None:
+            # the head's backward and this unit's first BatchNorm-backward pass in one kernel over y: dz = W^T dpre is formed per element for the sums
+            # (and again by the second pass below) and never written
+            nout, hparams = head
+            hw, heps, hsigma = ctx.saved_tensors[4:7]
+            V = D * H * W
+            g = [planar(t) if t is not None else None for t in head_g]
+            if nout == 3 and g[0] is None:
+                g[0] = torch.zeros((B, 3, D, H, W), device=dev)
+            hblk = lib.query("pulpo_heads_bwd_blocks", B, V, Cout)
+            hpart, hslots = _heads_part_rows(hparams, ctx.needs_input_grad[15] and ctx.needs_input_grad[16], hblk, nout, Cout, dev)
+            part = torch.empty(hblk * 2 * Cout, device=dev, dtype=torch.float32)
+            heads_src = (_ptr(hw), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(heps), _ptr(hsigma))
+            t0 = _hbm_begin("heads_bwd_bn")
+            lib.call("pulpo_heads_bwd_bn_t", _ptr(y), y.stride(4), _ptr(coef), LRELU_SLOPE, *heads_src, _ptr(hpart), _ptr(part), nout, B, V, Cout, _stream())
+            _hbm_end(t0, "heads_bwd_bn", B * V * (4.0 * Cout + 4.0 * (15 if nout == 6 else 3)))       # read y and the output gradients (+ eps, sigma)
+            head_dw, head_db = _heads_finish_rows(hpart, hslots, hparams, hblk, nout, Cout)
+            tiles = (part, hblk)
         if tiles is None and pooled_src is None:
             part = torch.empty(nblk * 2 * Cout, device=dev, dtype=torch.float32)
             t0 = _hbm_begin("bn_lrelu_bwd_reduce")
@@ -1117,13 +1160,13 @@ class _ConvBNLReLU(torch.autograd.Function):
         # The input layer (image pair -> 32 channels at full resolution): nobody asks for its data gradient, so dy has ONE reader - the weight
         # gradient, which then forms it per element while staging (pulpo_conv3d_k3_wgrad_bn) instead of a pass that reads dz and y and writes dy
         # (0.29 ms at 160^3 x 32 channels).  PULPO_FUSE_INPUT_WGRAD=0: the separate pass (A/B switch).
-        if (FUSE_INPUT_WGRAD and pooled_src is None and Cin <= 2 and not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not DETERMINISTIC and y.dtype == torch.float32
+        if (FUSE_INPUT_WGRAD and pooled_src is None and heads_src is None and Cin <= 2 and not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not DETERMINISTIC and y.dtype == torch.float32
                 and Cout % 4 == 0 and is_cl(y) and (dz_blk or (is_cl(dz) and dz.stride(4) % 4 == 0)) and y.stride(4) % 4 == 0 and x.dtype == torch.float32):
             return _ConvBNLReLU._backward_input_layer(ctx, dz, x, weight, y, coef, totd, tot, direct_bn, (slot_w, slot_b), (w_p, b_p))
         # the data-gradient weights now (cached pack): their kernel family decides dy's layout
         wpt = _pack_weight(weight, dgrad=True, shape=(B, D, H, W)) if ctx.needs_input_grad[0] else None
         blocked = (_blocked_dy_ok(x, y, weight, wpt, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-                   and (pooled_src is not None or dz_blk or (is_cl(dz) and dz.stride(4) % 4 == 0)) and is_cl(y) and y.stride(4) % 4 == 0)
+                   and (pooled_src is not None or heads_src is not None or dz_blk or (is_cl(dz) and dz.stride(4) % 4 == 0)) and is_cl(y) and y.stride(4) % 4 == 0)
         if blocked:
             global BLOCKED_DY_HITS
             BLOCKED_DY_HITS += 1
@@ -1136,8 +1179,16 @@ class _ConvBNLReLU(torch.autograd.Function):
             defer_b = False                          # for flush_param_grads() - this pass takes the immediate path into the same slot
         if not defer_b:
             part2 = torch.empty(nblk * Cout, device=dev, dtype=torch.float32)
-        t0 = _hbm_begin("bn_lrelu_bwd_apply")
-        if pooled_src is not None:
+        t0 = _hbm_begin("bn_lrelu_bwd_apply_heads" if heads_src is not None else "bn_lrelu_bwd_apply")
+        if heads_src is not None:
+            if blocked:
+                lib.call("pulpo_bn_lrelu_bwd_apply_heads_kb_t", _ptr(y), y.stride(4), _ptr(coef), _ptr(totd), LRELU_SLOPE, *heads_src, _ptr(dy.buf), dy.ps, dy.kb,
+                         _ptr(part2), nout, B, V, Cout, _stream())
+            else:
+                lib.call("pulpo_bn_lrelu_bwd_apply_heads_t", _ptr(y), y.stride(4), _ptr(coef), _ptr(totd), LRELU_SLOPE, *heads_src, _ptr(dy), dy.stride(4),
+                         _ptr(part2), nout, B, V, Cout, _stream())
+            _hbm_end(t0, "bn_lrelu_bwd_apply_heads", npix * (8.0 * Cout + 4.0 * (15 if nout == 6 else 3)))      # read y and the head's planar operands; write dy
+        elif pooled_src is not None:
             gp, gz = pooled_src
             if blocked:
                 lib.call("pulpo_bn_lrelu_bwd_apply_pooled_kb_t", _ptr(gp), gp.stride(4), _ptr(gz), grid_strides(gz)[1] if gz is not None else 0, _dt(gp), _ptr(y),
@@ -1184,7 +1235,7 @@ class _ConvBNLReLU(torch.autograd.Function):
                 dx = cl_to_blocked(dx.float())
         if defer_w:
             _wgrad_on_side_stream(x, dy, Cin, Cout, slot_w, w_p)
-        return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None
+        return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, head_dw, head_db, None, None, None
 
 
 def _backward_input_layer(ctx, dz, x, weight, y, coef, totd, tot, direct_bn, slots, params):
@@ -1235,7 +1286,7 @@ def _backward_input_layer(ctx, dz, x, weight, y, coef, totd, tot, direct_bn, slo
         _PENDING_KEEPALIVE.append(part2)
     dbias = _colsum(part2, nrow, Cout, into=slot_b) if (ctx.needs_input_grad[2] and not defer_b) else None
     dbeta, dgamma = (None, None) if direct_bn else (tot[:Cout], tot[Cout:])
-    return None, (None if slot_w is not None else dw), dbias, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None
+    return (None, (None if slot_w is not None else dw), dbias, dgamma, dbeta) + (None,) * 15
 
 
 _ConvBNLReLU._backward_input_layer = staticmethod(_backward_input_layer)
@@ -1265,7 +1316,7 @@ def conv_bn_lrelu(x, weight, bias, gamma, beta, running_mean, running_var, train
     pool_only = bool(pool_only and pool_after and training and torch.is_grad_enabled())
     _TLS.pool_only_done = False
     z = _ConvBNLReLU.apply(x, weight, bias, gamma, beta, running_mean, running_var, num_batches_tracked, bool(training), float(momentum),
-                           float(eps), bn_src, bool(pool_after), pool_only, bool(blocked_out))
+                           float(eps), bn_src, bool(pool_after), pool_only, bool(blocked_out), None, None, None, 0, None)
     pooled_out = None
     if isinstance(z, tuple):
         z, pooled_out = z
@@ -1284,6 +1335,46 @@ def conv_bn_lrelu(x, weight, bias, gamma, beta, running_mean, running_var, train
     if out is not None and z.dim() == 5 and z.data_ptr() == out[0].data_ptr() + out[0].element_size() * out[1] and z.stride() == out[0].stride():
         z._pulpo_cat = (out[0], out[1])
     return (z, None) if want_tuple else z
+
+
+# ---- ConvUnit + 1x1x1 head in one node.  The last ConvUnit in front of a head (PULPoEncoder.sample_merge_block -> mu_sigma, VelocityField's last
+# unit -> its 1x1x1 convolution) produces an activation that only the head reads, and the head returns a gradient that only this unit's BatchNorm
+# backward reads: the head kernels take the pre-norm tensor and the coefficient block and form both per element (pulpo_heads_fwd_bn_t,
+# pulpo_heads_bwd_bn_t, pulpo_bn_lrelu_bwd_apply_heads_t) - ten passes over a C-channel tensor become four, two tensors and two launches per head go.
+# PULPO_FUSE_HEAD_BN=0: the separate passes (A/B switch).
+FUSE_HEAD_BN = os.environ.get("PULPO_FUSE_HEAD_BN", "1") != "0"
+HEAD_BN_HITS = 0                 # heads that ran on the pre-norm tensor so far (tests look at it)
+
+
+def head_bn_ok(x, training: bool, zdim: int = 3) -> bool:
+    """may a ConvUnit applied to x hand (pre-norm tensor, coefficients) to a three-component head instead of its activation?  Training-mode
+    statistics, volumes, fp32 activation storage; the CALLER answers for the activation having no other reader (hooks included)"""
+    return bool(FUSE_HEAD_BN and training and zdim == 3 and not ACT_BF16 and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() in (5, 6))
+
+
+def _conv_bn_lrelu_heads(x, unit_args, momentum, eps, Wt, hbias, heps, nout, hparams):
+    global HEAD_BN_HITS
+    HEAD_BN_HITS += 1
+    weight, bias, gamma, beta, running_mean, running_var, num_batches_tracked = unit_args
+    _TLS.out_slot = None
+    src = getattr(x, "_pulpo_bn_src", None)
+    bn_src = src[:2] if (src is not None and src[2] == x._version and torch.is_grad_enabled()) else None
+    return _ConvBNLReLU.apply(x, weight, bias, gamma, beta, running_mean, running_var, num_batches_tracked, True, float(momentum), float(eps), bn_src,
+                              False, False, False, Wt, hbias, heps, nout, hparams)
+
+
+def conv_bn_lrelu_mu_sigma(x, unit_args, momentum, eps, w_mu, b_mu, w_sigma, b_sigma, noise):
+    """mu_sigma_sample(conv_bn_lrelu(x, ...), ...) for zdim == 3 where head_bn_ok(): (mu, sigma, z).  unit_args: (weight, bias, gamma, beta,
+    running_mean, running_var, num_batches_tracked) of the ConvUnit, in training mode"""
+    C = w_mu.shape[1]
+    Wt = torch.cat([w_mu.reshape(3, C), w_sigma.reshape(3, C)], dim=0)
+    hbias = torch.cat([b_mu, b_sigma], dim=0)
+    return _conv_bn_lrelu_heads(x, unit_args, momentum, eps, Wt, hbias, noise, 6, (((w_mu, 0, 3), (w_sigma, 3, 3)), ((b_mu, 0, 3), (b_sigma, 3, 3))))
+
+
+def conv_bn_lrelu_to3(x, unit_args, momentum, eps, w, b):
+    """conv1x1_to3(conv_bn_lrelu(x, ...), w, b) where head_bn_ok()"""
+    return _conv_bn_lrelu_heads(x, unit_args, momentum, eps, w.reshape(3, w.shape[1]), b, None, 3, (((w, 0, 3),), ((b, 0, 3),)))
 
 
 class _Conv3dK3(torch.autograd.Function):
@@ -1359,32 +1450,45 @@ class _Heads(torch.autograd.Function):
             g[0] = torch.zeros((B, 3, D, H, W), device=dev)
         dh = new_cl(B, C, D, H, W, dev, h.dtype)
         nblk = lib.query("pulpo_heads_bwd_blocks", B, V, C)
-        rowlen = nout * C + nout
-        # inside the stepper: the partial rows go to a persistent buffer (stable address: the finishing launch's job table is cached) and
-        # flush_param_grads() adds their column sums to the parameters' .grad; a head applied twice in a step takes the immediate path
-        slots = None
-        if ctx.params is not None and DIRECT_PARAM_GRADS and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
-            wparts, bparts = ctx.params
-            slots = [(_grad_slot(t), off, n) for t, off, n in wparts] + [(_grad_slot(t), off, n) for t, off, n in bparts]
-            if not all(sl is not None for sl, _, _ in slots):
-                slots = None
-        part = _persistent_buffer(ctx.params[0][0][0], "_pulpo_heads_part", nblk * rowlen, zero=False) if slots is not None else None
-        if part is None or _pending_src(part):
-            slots = None
-            part = torch.empty(nblk * rowlen, device=dev, dtype=torch.float32)
+        part, slots = _heads_part_rows(ctx.params, ctx.needs_input_grad[1] and ctx.needs_input_grad[2], nblk, nout, C, dev)
         t0 = _hbm_begin("heads_bwd")
         lib.call("pulpo_heads_bwd_t", _ptr(h), _dt(h), h.stride(4), _ptr(Wt), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(eps), _ptr(sigma), _ptr(dh),
                  dh.stride(4), _ptr(part), nout, B, V, C, _stream())
         _hbm_end(t0, "heads_bwd", B * V * (2 * _esize(h) * C + 4.0 * (15 if nout == 6 else 3)))   # read h, the output gradients (+ eps, sigma), write dh
-        if slots is not None:
-            nw = len(ctx.params[0])
-            for k, (sl, off, n) in enumerate(slots):
-                col0, ncol = (off * C, n * C) if k < nw else (nout * C + off, n)
-                _PENDING_GRAD_JOBS.append((part.data_ptr() + 4 * col0, sl.data_ptr(), 1, nblk, ncol, rowlen))
-            _PENDING_KEEPALIVE.append(part)
-            return dh, None, None, None, None, None
-        tot = _colsum(part, nblk, rowlen)
-        return dh, tot[: nout * C].view(nout, C), tot[nout * C:], None, None, None
+        dW, db = _heads_finish_rows(part, slots, ctx.params, nblk, nout, C)
+        return dh, dW, db, None, None, None
+
+
+def _heads_part_rows(params, need_wb: bool, nblk: int, nout: int, C: int, dev):
+    """(partial rows [nblk][nout * C + nout] for a head's backward kernel, the .grad slots they will be summed into or None).
+    Inside the stepper the rows go to a persistent buffer (stable address: the finishing launch's job table is cached) and flush_param_grads()
+    adds their column sums to the parameters' .grad; a head applied twice in a step takes the immediate path"""
+    rowlen = nout * C + nout
+    slots = None
+    if params is not None and DIRECT_PARAM_GRADS and need_wb:
+        wparts, bparts = params
+        slots = [(_grad_slot(t), off, n) for t, off, n in wparts] + [(_grad_slot(t), off, n) for t, off, n in bparts]
+        if not all(sl is not None for sl, _, _ in slots):
+            slots = None
+    part = _persistent_buffer(params[0][0][0], "_pulpo_heads_part", nblk * rowlen, zero=False) if slots is not None else None
+    if part is None or _pending_src(part):
+        slots = None
+        part = torch.empty(nblk * rowlen, device=dev, dtype=torch.float32)
+    return part, slots
+
+
+def _heads_finish_rows(part, slots, params, nblk: int, nout: int, C: int):
+    """(dW, db) of a head from its partial rows - or (None, None) with the column sums queued for flush_param_grads()"""
+    rowlen = nout * C + nout
+    if slots is not None:
+        nw = len(params[0])
+        for k, (sl, off, n) in enumerate(slots):
+            col0, ncol = (off * C, n * C) if k < nw else (nout * C + off, n)
+            _PENDING_GRAD_JOBS.append((part.data_ptr() + 4 * col0, sl.data_ptr(), 1, nblk, ncol, rowlen))
+        _PENDING_KEEPALIVE.append(part)
+        return None, None
+    tot = _colsum(part, nblk, rowlen)
+    return tot[: nout * C].view(nout, C), tot[nout * C:]
 
 
 def mu_sigma_sample(h, w_mu, b_mu, w_sigma, b_sigma, eps):
