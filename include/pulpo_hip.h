@@ -278,6 +278,14 @@ int pulpo_dsc(const float* inp, const float* tgt, int nplanes, int64_t V, float*
 int pulpo_percent_leq0(const float* x, int64_t n, float* partial /* pulpo_metric_blocks(n) */, float* out, void* stream);
 int pulpo_warp_landmarks(const float* lm /*(nlm,nd)*/, const float* df /*(nsamp,nd,D,H,W)*/, float* out /*(nsamp,nlm,nd)*/, int nlm, int nsamp,
                          int nd, int D, int H, int W, int* flag, void* stream);
+/* pulpo_field_quality: the two field-quality rows of Evaluate.performance (evaluate.py:1440-1449: HierarchicalRegularization(JDetStd) with
+ * lamb = 1, and JDetLeq0) in one pass that reads df (B,3,D,H,W; D == 1: (B,2,1,H,W)) once and writes no determinant map:
+ *   out[0] = mean, out[1] = unbiased std, out[2] = 100 * count(J <= 0) / n of jacobian_det(df) over all n = B*D*H*W voxels,
+ *   J bit for bit the value pulpo_jacdet_fwd stores.  Block partials of sum(J - 1), sum((J - 1)^2) in double and an integer count, added in
+ *   a fixed order: two calls give the same bits.  ws: pulpo_field_quality_ws_bytes(B, D, H, W) bytes. */
+int pulpo_field_quality_blocks(int B, int D, int H, int W);
+size_t pulpo_field_quality_ws_bytes(int B, int D, int H, int W);
+int pulpo_field_quality(const float* df, float* out /* 3 floats */, void* ws, int B, int D, int H, int W, int normalize, void* stream);
 
 /* ------------------------------------------------------------------------------- Monte-Carlo uncertainty statistics
  * evaluate.py:222-251 stacks N sampled volumes / fields per level and takes torch.std(axis=0) (unbiased) then torch.mean over the
@@ -307,6 +315,15 @@ int pulpo_warp_labels(const float* df, const void* labels, int ldt, int C, const
                       void* amax /*nullable*/, float* dice /*nullable iff target is*/, float* mean /*nullable*/, float* m2 /*nullable iff mean is*/,
                       int k, void* ws, int* flag, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, void* stream);
 int pulpo_labels_check(const void* labels, int ldt, int64_t n, int C, int* flag, void* stream);
+/* pulpo_warp_labels_soft_dice: the level Dice of Evaluate.performance (evaluate.py:1427, 1454-1455) without a one-hot tensor:
+ * Soft_dice_loss (src/losses.py:137-145) of SpatialTransformer(df, one_hot(labels)) against F.interpolate(one_hot(target), size = grid,
+ * trilinear, align_corners=False), as HierarchicalReconstructionLoss(["dice"]) resizes it (src/losses.py:279-325).
+ *   df (B,3,Dg,Hg,Wg); labels (B,1,Di,Hi,Wi) and target (B,1,Dt,Ht,Wt) of dtype ldt; depth 1 = the 2-D form.
+ *   dice (B,C): (2 sum(p t) + 1e-6) / (sum(t^2) + sum(p^2) + 1e-6), sums over the grid's voxels; mean: 1 float, their mean over (b, c)
+ *   = 1 - level_dice / num_pixels.  Deterministic (per-voxel products rounded to 64-bit fixed point, integer adds).
+ *   ws: pulpo_warp_labels_ws_bytes(B, C) bytes; *flag = 1 when a gathered label lies outside [0, C) (zeroed here). */
+int pulpo_warp_labels_soft_dice(const float* df, const void* labels, const void* target, int ldt, int C, float* dice, float* mean, void* ws,
+                                int* flag, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, int Dt, int Ht, int Wt, void* stream);
 int pulpo_labels_from_onehot(const float* seg, void* labels, int ldt, int B, int C, int64_t V, void* stream);
 int pulpo_map_ncc_blocks(int64_t n);
 int pulpo_map_ncc(const float* a, const float* b, int64_t n, double* partial, double* out, void* stream);

@@ -172,6 +172,129 @@ __global__ void dice_from_sums_kernel(const unsigned long long* __restrict__ sum
     dice[i] = (float)((2.0 * s0 / V + 1e-6) / (s1 / V + s2 / V + 1e-6));
 }
 
+// The level Dice of Evaluate.performance (evaluate.py:1427, 1454-1455) without a one-hot tensor: Soft_dice_loss (src/losses.py:137-145) of
+// spatial_transform(df, one_hot(labels)) against F.interpolate(one_hot(target), size = grid, trilinear, align_corners=False).
+// Per voxel of the grid, p_c = the sum of the <= 8 corner weights of the warped moving map that carry class c (the coordinates, weight
+// products and corner order of warp_labels_kernel) and t_c = the sum of the <= 8 tap weights of the resize that carry class c, with
+// PyTorch's source index for size= (resample.hip's src_index: scale = map / grid, src = scale (dst + 0.5) - 0.5 clamped at 0).  Only the
+// <= 16 classes met at the voxel have a non-zero p t, p^2 or t^2.  Each per-voxel product is rounded to 64-bit fixed point (units of
+// 2^-32) before the integer adds of the wave, the block (LDS) and the grid (one global add per block and class): the same bits in any order.
+__device__ __forceinline__ void resize_src_index(int dst, float scale, int in_size, int& i0, int& i1, float& lam) {
+    float s = scale * ((float)dst + 0.5f) - 0.5f;
+    s = s < 0.f ? 0.f : s;
+    i0 = (int)s;
+    if (i0 > in_size - 1) i0 = in_size - 1;
+    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+    lam = s - (float)i0;
+}
+
+// grid (nblk, B); sums: (B, C, 3) u64 = (sum p t, sum t^2, sum p^2); labels on (Di, Hi, Wi), target on (Dt, Ht, Wt)
+template <typename LT>
+__global__ __launch_bounds__(256) void warp_labels_soft_dice_kernel(const float* __restrict__ df, const LT* __restrict__ lab, const LT* __restrict__ tgt,
+                                                                      int C, unsigned long long* __restrict__ sums, int* __restrict__ flag, int Dg, int Hg,
+                                                                      int Wg, int Di, int Hi, int Wi, int Dt, int Ht, int Wt) {
+    __shared__ unsigned long long sh[3 * kMaxClasses];
+    const int b = blockIdx.y;
+    const long Vg = (long)Dg * Hg * Wg, Vi = (long)Di * Hi * Wi, Vt = (long)Dt * Ht * Wt;
+    const LT* lb = lab + b * Vi;
+    const LT* tb = tgt + b * Vt;
+    const float sd = (float)Dt / (float)Dg, shh = (float)Ht / (float)Hg, sw = (float)Wt / (float)Wg;
+    for (int j = threadIdx.x; j < 3 * C; j += 256) sh[j] = 0ull;
+    __syncthreads();
+    bool bad = false;
+    // block-uniform trip count: every lane of a wave takes part in the exchange below
+    for (long base = (long)blockIdx.x * 256; base < Vg; base += (long)gridDim.x * 256) {
+        const long v = base + threadIdx.x;
+        int cl[16];          // 0..7 the warp's corners, 8..15 the resize's taps
+        float w[16];
+        unsigned pending = 0u;
+        if (v < Vg) {
+            const int vi = (int)v;
+            const int x = vi % Wg, y = (vi / Wg) % Hg, z = vi / (Wg * Hg);
+            const float* d = df + (long)b * 3 * Vg + v;
+            const Corner cz = sample_coord((float)z, d[0], Dg, Di);
+            const Corner cy = sample_coord((float)y, d[Vg], Hg, Hi);
+            const Corner cx = sample_coord((float)x, d[2 * Vg], Wg, Wi);
+            const long o00 = ((long)cz.i0 * Hi + cy.i0) * Wi, o01 = ((long)cz.i0 * Hi + cy.i1) * Wi;
+            const long o10 = ((long)cz.i1 * Hi + cy.i0) * Wi, o11 = ((long)cz.i1 * Hi + cy.i1) * Wi;
+            const float wz0 = 1.f - cz.f, wy0 = 1.f - cy.f, wx0 = 1.f - cx.f;
+            // corner order and weight products of warp_fwd_kernel
+            w[0] = wz0 * wy0 * wx0; w[1] = wz0 * wy0 * cx.f; w[2] = wz0 * cy.f * wx0; w[3] = wz0 * cy.f * cx.f;
+            w[4] = cz.f * wy0 * wx0; w[5] = cz.f * wy0 * cx.f; w[6] = cz.f * cy.f * wx0; w[7] = cz.f * cy.f * cx.f;
+            cl[0] = load_label(lb, o00 + cx.i0); cl[1] = load_label(lb, o00 + cx.i1);
+            cl[2] = load_label(lb, o01 + cx.i0); cl[3] = load_label(lb, o01 + cx.i1);
+            cl[4] = load_label(lb, o10 + cx.i0); cl[5] = load_label(lb, o10 + cx.i1);
+            cl[6] = load_label(lb, o11 + cx.i0); cl[7] = load_label(lb, o11 + cx.i1);
+            int z0, z1, y0, y1, x0, x1;
+            float lz, ly, lx;
+            resize_src_index(z, sd, Dt, z0, z1, lz);
+            resize_src_index(y, shh, Ht, y0, y1, ly);
+            resize_src_index(x, sw, Wt, x0, x1, lx);
+            const long t00 = ((long)z0 * Ht + y0) * Wt, t01 = ((long)z0 * Ht + y1) * Wt;
+            const long t10 = ((long)z1 * Ht + y0) * Wt, t11 = ((long)z1 * Ht + y1) * Wt;
+            const float uz0 = 1.f - lz, uy0 = 1.f - ly, ux0 = 1.f - lx;
+            w[8] = uz0 * uy0 * ux0; w[9] = uz0 * uy0 * lx; w[10] = uz0 * ly * ux0; w[11] = uz0 * ly * lx;
+            w[12] = lz * uy0 * ux0; w[13] = lz * uy0 * lx; w[14] = lz * ly * ux0; w[15] = lz * ly * lx;
+            cl[8] = load_label(tb, t00 + x0); cl[9] = load_label(tb, t00 + x1);
+            cl[10] = load_label(tb, t01 + x0); cl[11] = load_label(tb, t01 + x1);
+            cl[12] = load_label(tb, t10 + x0); cl[13] = load_label(tb, t10 + x1);
+            cl[14] = load_label(tb, t11 + x0); cl[15] = load_label(tb, t11 + x1);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const bool ok = cl[i] >= 0 && cl[i] < C;
+                bad |= !ok;
+                if (!ok) cl[i] = -1;
+                pending |= (ok && w[i] != 0.f) ? (1u << i) : 0u;        // a zero weight adds nothing to any sum
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { cl[i] = -1; w[i] = 0.f; }
+        }
+        // Per class present in the wave: every lane's p_c and t_c (matching weights added in corner / tap order, starting from 0 like the
+        // warp's sum), three integer wave sums, one LDS add each.  A class is handled once: all its pending bits clear together.
+        while (true) {
+            const unsigned long long act = __ballot(pending != 0u);
+            if (act == 0ull) break;
+            int cand = -1;
+#pragma unroll
+            for (int i = 15; i >= 0; --i) cand = (pending >> i) & 1u ? cl[i] : cand;
+            const int c = __shfl(cand, __ffsll((long long)act) - 1, 64);
+            float pc = 0.f, tc = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                pc += cl[i] == c ? w[i] : 0.f;
+                tc += cl[8 + i] == c ? w[8 + i] : 0.f;
+                pending &= ~((cl[i] == c ? (1u << i) : 0u) | (cl[8 + i] == c ? (1u << (8 + i)) : 0u));
+            }
+            const unsigned long long u0 = wave_sum_u64(to_fix(pc * tc)), u1 = wave_sum_u64(to_fix(tc * tc)), u2 = wave_sum_u64(to_fix(pc * pc));
+            if ((threadIdx.x & 63) == 0) {
+                if (u0) atomicAdd(&sh[3 * c], u0);
+                if (u1) atomicAdd(&sh[3 * c + 1], u1);
+                if (u2) atomicAdd(&sh[3 * c + 2], u2);
+            }
+        }
+    }
+    if (bad) atomicOr(flag, 1);
+    __syncthreads();
+    unsigned long long* dst = sums + (long)b * C * 3;
+    for (int j = threadIdx.x; j < 3 * C; j += 256)
+        if (sh[j]) atomicAdd(dst + j, sh[j]);
+}
+
+// one wave: dice[b][c] = (2 sum(p t) + 1e-6) / (sum(t^2) + sum(p^2) + 1e-6) (sums, not pulpo_dsc's means) and their mean over (b, c),
+// lane t taking planes t, t + 64, ... in that order, then the butterfly
+__global__ void soft_dice_from_sums_kernel(const unsigned long long* __restrict__ sums, int n, float* __restrict__ dice, float* __restrict__ mean) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const double s0 = (double)sums[3 * i] / kFix, s1 = (double)sums[3 * i + 1] / kFix, s2 = (double)sums[3 * i + 2] / kFix;
+        const double d = (2.0 * s0 + 1e-6) / (s1 + s2 + 1e-6);
+        dice[i] = (float)d;
+        acc += d;
+    }
+    acc = pulpo::wave_sum_d(acc);
+    if (threadIdx.x == 0) mean[0] = (float)(acc / n);
+}
+
 template <typename LT>
 __global__ __launch_bounds__(256) void labels_check_kernel(const LT* __restrict__ lab, long n, int C, int* __restrict__ flag) {
     bool bad = false;
@@ -282,6 +405,32 @@ PULPO_API int pulpo_warp_labels(const float* df, const void* labels, int ldt, in
     const int n = B * C;
     hipLaunchKernelGGL(dice_from_sums_kernel, dim3((n + 255) / 256), dim3(256), 0, st, sums, n, (double)Vg, dice);
     return pulpo::check_launch("warp_labels dice");
+}
+
+PULPO_API int pulpo_warp_labels_soft_dice(const float* df, const void* labels, const void* target, int ldt, int C, float* dice, float* mean, void* ws,
+                                          int* flag, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, int Dt, int Ht, int Wt, void* stream) {
+    PULPO_REQUIRE(df && labels && target && dice && mean && ws && flag && B > 0 && (ldt == 0 || ldt == 1) && C >= 1 && C <= kMaxClasses,
+                  "warp_labels_soft_dice: bad arguments (1 <= C <= 256)");
+    PULPO_REQUIRE(Dg >= 1 && Hg > 1 && Wg > 1 && Di > 0 && Hi > 0 && Wi > 0 && Dt > 0 && Ht > 0 && Wt > 0 && (Dg > 1 || (Di == 1 && Dt == 1)),
+                  "warp_labels_soft_dice: grid H, W must be > 1 (depth 1 = 2-D form, with depth-1 label maps)");
+    PULPO_REQUIRE((long)Dg * Hg * Wg < (1L << 31), "warp_labels_soft_dice: grids of 2^31 voxels and more are not supported");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st);
+    if (e == hipSuccess) e = hipMemsetAsync(ws, 0, pulpo_warp_labels_ws_bytes(B, C), st);
+    if (e != hipSuccess) return pulpo::fail((int)e, "warp_labels_soft_dice memset: %s", hipGetErrorString(e));
+    const long Vg = (long)Dg * Hg * Wg;
+    const dim3 grid(eblocks(Vg, std::max(1, 2048 / B)), B);
+    unsigned long long* sums = (unsigned long long*)ws;
+    if (ldt == 0)
+        hipLaunchKernelGGL(warp_labels_soft_dice_kernel<uint8_t>, grid, dim3(256), 0, st, df, (const uint8_t*)labels, (const uint8_t*)target, C, sums,
+                           flag, Dg, Hg, Wg, Di, Hi, Wi, Dt, Ht, Wt);
+    else
+        hipLaunchKernelGGL(warp_labels_soft_dice_kernel<int32_t>, grid, dim3(256), 0, st, df, (const int32_t*)labels, (const int32_t*)target, C, sums,
+                           flag, Dg, Hg, Wg, Di, Hi, Wi, Dt, Ht, Wt);
+    int rc = pulpo::check_launch("warp_labels_soft_dice");
+    if (rc) return rc;
+    hipLaunchKernelGGL(soft_dice_from_sums_kernel, dim3(1), dim3(64), 0, st, sums, B * C, dice, mean);
+    return pulpo::check_launch("warp_labels_soft_dice finish");
 }
 
 PULPO_API int pulpo_labels_check(const void* labels, int ldt, int64_t n, int C, int* flag, void* stream) {

@@ -228,6 +228,92 @@ __global__ __launch_bounds__(256) void jdetstd_bwd_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------ field quality (Evaluate.performance)
+// mean, unbiased std and % <= 0 of the Jacobian determinant in one pass over the field, no determinant map (evaluate.py:1440-1449:
+// HierarchicalRegularization(JDetStd) with lamb = 1 plus the JDetLeq0 expression).  jac_at / jac2_at give the determinant of
+// jacdet_fwd_kernel bit for bit.  A row is one (b, z, y): the wave's lanes run along x (LX lanes per row, 64 / LX rows per wave), so
+// the x neighbours come from the lanes' own cache lines and (b, z, y) costs one division per row, not per voxel.  Per thread the sums of
+// (J - 1) and (J - 1)^2 in double (J sits near 1: centred sums do not cancel in q - s mean) and an integer count of J <= 0; per block one
+// partial of each; the finish adds the partials in a fixed order in double.  No atomics: two calls give the same bits.
+__global__ __launch_bounds__(256) void field_quality_kernel(const float* __restrict__ df, JacGeom g, int lx_log2, long ngroups, double* __restrict__ psum,
+                                                              long long* __restrict__ pcnt) {
+    __shared__ double shd[8];
+    __shared__ long long shc[4];
+    const int LX = 1 << lx_log2, rows_per_block = 256 >> lx_log2;
+    const int xl = threadIdx.x & (LX - 1), rl = threadIdx.x >> lx_log2;
+    const long rows = (long)g.B * g.D * g.H;
+    double s = 0.0, q = 0.0;
+    long long cnt = 0;
+    for (long grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+        const long r = grp * rows_per_block + rl;
+        if (r >= rows) continue;
+        const long bz = r / g.H;
+        const int y = (int)(r - bz * g.H);
+        const long b = bz / g.D;
+        const int z = (int)(bz - b * g.D);
+        for (int x = xl; x < g.W; x += LX) {
+            const float d = g.D == 1 ? jac2_at(df, g, b, y, x, nullptr) : jac_at(df, g, b, z, y, x, nullptr);
+            const double c = (double)d - 1.0;
+            s += c;
+            q += c * c;
+            cnt += d <= 0.f ? 1 : 0;
+        }
+    }
+    s = pulpo::wave_sum_d(s);
+    q = pulpo::wave_sum_d(q);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) {
+        shd[2 * (threadIdx.x >> 6)] = s;
+        shd[2 * (threadIdx.x >> 6) + 1] = q;
+        shc[threadIdx.x >> 6] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        psum[2 * blockIdx.x] = (shd[0] + shd[2]) + (shd[4] + shd[6]);
+        psum[2 * blockIdx.x + 1] = (shd[1] + shd[3]) + (shd[5] + shd[7]);
+        pcnt[blockIdx.x] = (shc[0] + shc[1]) + (shc[2] + shc[3]);
+    }
+}
+
+// one wave: lane t adds partials t, t + 64, ... in that order, then the butterfly - the same order on every call.
+// out = (mean, std with n - 1, 100 count / n)
+__global__ void field_quality_finalize_kernel(const double* __restrict__ psum, const long long* __restrict__ pcnt, int nblk, double n,
+                                              float* __restrict__ out) {
+    double s = 0.0, q = 0.0;
+    long long cnt = 0;
+    for (int k = threadIdx.x; k < nblk; k += 64) { s += psum[2 * k]; q += psum[2 * k + 1]; cnt += pcnt[k]; }
+    s = pulpo::wave_sum_d(s);
+    q = pulpo::wave_sum_d(q);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (threadIdx.x == 0) {
+        const double cm = s / n;                                   // mean of J - 1
+        double var = n > 1.0 ? (q - s * cm) / (n - 1.0) : 0.0;
+        if (var < 0) var = 0;
+        out[0] = (float)(1.0 + cm);
+        out[1] = (float)sqrt(var);
+        out[2] = (float)(100.0 * (double)cnt / n);
+    }
+}
+
+// lanes per row: 64, 32 or 16 (at least 64 contiguous bytes per row), whichever wastes the fewest lanes on a row of W voxels (the larger on ties)
+inline int field_quality_lx_log2(int W) {
+    int best = 6;
+    long waste = ((W + 63) / 64) * 64 - W;
+    for (int l = 5; l >= 4; --l) {
+        const int LX = 1 << l;
+        const long w = (long)((W + LX - 1) / LX) * LX - W;
+        if (w < waste) { waste = w; best = l; }
+    }
+    return best;
+}
+
+inline long field_quality_groups(int B, int D, int H, int W) {
+    const long rows = (long)B * D * H, rpb = 256 >> field_quality_lx_log2(W);
+    return (rows + rpb - 1) / rpb;
+}
+
 JacGeom make_geom(int B, int D, int H, int W, int normalize) {
     JacGeom g;
     g.B = B; g.D = D; g.H = H; g.W = W;
@@ -302,6 +388,29 @@ PULPO_API int pulpo_jdetstd_bwd(const float* df, const float* jdet, const double
     if (e != hipSuccess) return pulpo::fail((int)e, "jdetstd_bwd memset: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(jdetstd_bwd_kernel, dim3(eblocks(n)), dim3(256), 0, st, df, make_geom(B, D, H, W, normalize), jdet, stat, gscale, lamb, (double)n, gdf);
     return pulpo::check_launch("jdetstd_bwd");
+}
+
+// Field quality of evaluate.py:1440-1449 in one pass: out = (mean, unbiased std, 100 * count(J <= 0) / n) of jacobian_det(df) over all
+// n = B*D*H*W voxels, the determinant of pulpo_jacdet_fwd bit for bit, never stored.  ws: pulpo_field_quality_ws_bytes(B, D, H, W) bytes
+PULPO_API int pulpo_field_quality_blocks(int B, int D, int H, int W) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+    return (int)std::min<long>(field_quality_groups(B, D, H, W), 1024);
+}
+PULPO_API size_t pulpo_field_quality_ws_bytes(int B, int D, int H, int W) {
+    return (size_t)pulpo_field_quality_blocks(B, D, H, W) * (2 * sizeof(double) + sizeof(long long));
+}
+PULPO_API int pulpo_field_quality(const float* df, float* out, void* ws, int B, int D, int H, int W, int normalize, void* stream) {
+    PULPO_REQUIRE(df && out && ws && B > 0 && D > 0 && H > 0 && W > 0, "field_quality: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = pulpo_field_quality_blocks(B, D, H, W);
+    double* psum = (double*)ws;
+    long long* pcnt = (long long*)(psum + 2 * (size_t)nblk);
+    hipLaunchKernelGGL(field_quality_kernel, dim3(nblk), dim3(256), 0, st, df, make_geom(B, D, H, W, normalize), field_quality_lx_log2(W),
+                       field_quality_groups(B, D, H, W), psum, pcnt);
+    int rc = pulpo::check_launch("field_quality");
+    if (rc) return rc;
+    hipLaunchKernelGGL(field_quality_finalize_kernel, dim3(1), dim3(64), 0, st, psum, pcnt, nblk, (double)B * D * H * W, out);
+    return pulpo::check_launch("field_quality finalize");
 }
 
 // ------------------------------------------------------------------------------------------------ evaluation scalars (evaluate.py)

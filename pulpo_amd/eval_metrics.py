@@ -1,6 +1,6 @@
 """Evaluation metrics of the reference's harness on the device.
 
-`Evaluate.rmse` / `.dsc` / `.jdet` / `.warp_landmarks` (evaluate.py:315-335, 410-423) and the "JDetLeq0" expression (evaluate.py:1441-1446)
+`Evaluate.rmse` / `.dsc` / `.jdet` / `.lm_mae` / `.lm_euclid` / `.warp_landmarks` (evaluate.py:315-379, 410-423) and the "JDetLeq0" expression (evaluate.py:1441-1446)
 are methods / inline code of the unchanged caller; these functions compute the same scalars with HIP kernels (one streaming pass and a
 device-side finish, no intermediate tensors) so that `Evaluate` can call them instead of its torch expressions."""
 from __future__ import annotations
@@ -31,6 +31,22 @@ def jdet(df: torch.Tensor) -> torch.Tensor:
 def jdet_leq0_percent(df: torch.Tensor) -> torch.Tensor:
     """percentage of voxels whose Jacobian determinant is <= 0 (evaluate.py:1441-1446): folding / non-diffeomorphic voxels"""
     return ops.percent_leq0(ops.jacobian_det(df, True))
+
+
+def field_quality(df: torch.Tensor, normalize: bool = True):
+    """(mean, std, percentage <= 0) of the Jacobian determinant in one pass over the field, no determinant map: the JDetStd (lamb = 1) and
+    JDetLeq0 rows of Evaluate.performance (evaluate.py:1440-1449)"""
+    return ops.field_quality(df, normalize)
+
+
+def lm_mae(lm1: torch.Tensor, lm2: torch.Tensor) -> torch.Tensor:
+    """median Manhattan distance between two sets of landmarks (1, n, ndims) (evaluate.py:355-366); torch.median: the lower median"""
+    return torch.median(torch.abs(lm1 - lm2).sum(dim=2))
+
+
+def lm_euclid(lm1: torch.Tensor, lm2: torch.Tensor) -> torch.Tensor:
+    """mean Euclidean distance between two sets of landmarks (1, n, ndims) (evaluate.py:368-379)"""
+    return torch.mean(torch.sqrt(((lm1 - lm2) ** 2).sum(dim=2)))
 
 
 def warp_landmarks(lm: torch.Tensor, df: torch.Tensor) -> torch.Tensor:

@@ -1,0 +1,147 @@
+"""The deterministic half of the reference's evaluation harness on the device: `Evaluate.performance` (evaluate.py:1379-1498), the per
+latent level RMSE, JDetStd, JDetLeq0, Dice, LM_MAE and LM_Euclid of `predict_deterministic`, and the naive baseline of
+`Evaluate.performance_affine` (evaluate.py:1190-1204).  `uncertainty.mc_uncertainty` + `uncertainty_scores` are the Monte-Carlo half.
+
+    scores = performance(model, x, y, seg_x=..., seg_y=..., lm_x=..., lm_y=..., num_classes=...)     # evaluate.py:1423-1474 for one pair
+    table.add(k, j, scores)                                                                            # evaluate.py:1476-1478, no host sync
+    data, (sets, mets) = table.mean()                                                                  # evaluate.py:1480-1488
+
+The two field-quality rows come from one pass over each level's field (ops.field_quality: no determinant map), the Dice row from one
+fused pass per level over the field and the two full-resolution label maps (ops.warp_labels_soft_dice: no one-hot tensor, neither the
+warped one nor the resized target).  Pandas, LaTeX and plots stay with the caller.  Evaluation only: no autograd, GPU tensors only."""
+from __future__ import annotations
+
+import warnings
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import eval_metrics, ops
+from .uncertainty import _as_labels
+
+METRICS = ("RMSE", "JDetStd", "JDetLeq0", "Dice", "LM_MAE", "LM_Euclid")
+
+
+def _zero(ref: torch.Tensor) -> torch.Tensor:
+    return torch.zeros((), device=ref.device, dtype=torch.float32)
+
+
+@torch.no_grad()
+def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Tensor], y: torch.Tensor, *, seg_x: Optional[torch.Tensor] = None,
+                 seg_y: Optional[torch.Tensor] = None, lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
+                 num_classes: Optional[int] = None) -> Dict[str, Dict[int, torch.Tensor]]:
+    """The level losses of evaluate.py:1433-1474 for one pair: {metric: {level: 0-d device tensor}}.
+
+    outputs[l], final_dfs[l]: the warped image and the final field of level l (predict_deterministic + combine_dfs); y: the fixed image.
+      RMSE[l]      sqrt(L2_loss(outputs[l], y resized to the level) / num_pixels_l)                       (evaluate.py:1437-1438)
+      JDetStd[l]   unbiased std of jacobian_det(final_dfs[l])      = HierarchicalRegularization(JDetStd)(final_dfs, lamb=1)   (:1441)
+      JDetLeq0[l]  100 * count(jacobian_det(final_dfs[l]) <= 0) / numel                                   (:1444-1448)
+    seg_x and seg_y (label maps (B, 1, ...) uint8 / int32 / int64 with num_classes, or the reference's float one-hot maps), both at full
+    resolution, add
+      Dice[l]      1 - Soft_dice_loss(spatial_transform(final_dfs[l], seg_x), seg_y resized to the level) / num_pixels_l   (:1427, 1454-1455)
+    lm_x and lm_y (1, n, ndims) add
+      LM_MAE / LM_Euclid: lm_mae / lm_euclid(warp_landmarks(lm_x, final_dfs[0]), lm_y) at level 0, the reference's 0 at the levels above
+      and, for empty landmark tensors, at level 0 too (:1457-1474).
+    Without segmentations or landmarks their rows are absent (the reference stores 0: PerformanceTable fills rows that were not added with 0)."""
+    levels = sorted(outputs.keys())
+    if sorted(final_dfs.keys()) != levels:
+        raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs {sorted(final_dfs.keys())}")
+    if (seg_x is None) != (seg_y is None):
+        raise ValueError("level_scores: seg_x and seg_y go together")
+    if (lm_x is None) != (lm_y is None):
+        raise ValueError("level_scores: lm_x and lm_y go together")
+    res: Dict[str, Dict[int, torch.Tensor]] = {"RMSE": {}, "JDetStd": {}, "JDetLeq0": {}}
+    for l in levels:
+        out = outputs[l]
+        size = tuple(out.shape[2:])
+        target = y if size == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)          # F.interpolate(y, size), skipped at equal size
+        num_pixels = float(np.prod(size))
+        res["RMSE"][l] = torch.sqrt(ops.l2_loss(out, target) / num_pixels)
+        _, res["JDetStd"][l], res["JDetLeq0"][l] = ops.field_quality(final_dfs[l], True)
+    if seg_x is not None:
+        lab_x, C = _as_labels(seg_x, num_classes, "level_scores")
+        lab_y, _ = _as_labels(seg_y, C, "level_scores")
+        res["Dice"] = {l: ops.warp_labels_soft_dice(final_dfs[l], lab_x, C, lab_y)[1] for l in levels}
+    if lm_x is not None:
+        res["LM_MAE"] = {l: _zero(y) for l in levels}
+        res["LM_Euclid"] = {l: _zero(y) for l in levels}
+        if lm_x.numel() and lm_y.numel():
+            moved = ops.warp_landmarks(lm_x, final_dfs[0])
+            ref = lm_y.to(device=moved.device, dtype=moved.dtype)
+            res["LM_MAE"][0] = eval_metrics.lm_mae(moved, ref)
+            res["LM_Euclid"][0] = eval_metrics.lm_euclid(moved, ref)
+    return res
+
+
+@torch.no_grad()
+def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torch.Tensor] = None, seg_y: Optional[torch.Tensor] = None,
+                lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
+                num_classes: Optional[int] = None) -> Dict[str, Dict[int, torch.Tensor]]:
+    """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
+    caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
+    feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
+    unless the samplers are pinned (network_blocks.FixedNoiseSampler)."""
+    outputs, individual_dfs = model.predict_deterministic(x, y)
+    _, final_dfs = model.combine_dfs(individual_dfs)
+    return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes)
+
+
+@torch.no_grad()
+def affine_scores(x: torch.Tensor, y: torch.Tensor, seg_x: Optional[torch.Tensor] = None, seg_y: Optional[torch.Tensor] = None,
+                  lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The naive baseline of Evaluate.performance_affine (evaluate.py:1190-1204), the scores of the unregistered pair: RMSE = rmse(x, y);
+    with (one-hot or soft) segmentation maps Dice = dsc(seg_x, seg_y); with landmarks LM_MAE / LM_Euclid of the unwarped landmarks."""
+    res = {"RMSE": eval_metrics.rmse(x, y)}
+    if seg_x is not None and seg_y is not None:
+        res["Dice"] = eval_metrics.dsc(seg_x, seg_y)
+    if lm_x is not None and lm_y is not None:
+        ref = lm_y.to(device=lm_x.device, dtype=lm_x.dtype)
+        res["LM_MAE"] = eval_metrics.lm_mae(lm_x, ref)
+        res["LM_Euclid"] = eval_metrics.lm_euclid(lm_x, ref)
+    return res
+
+
+class PerformanceTable:
+    """The all_metrics array of Evaluate.performance (evaluate.py:1388, 1476-1488) kept on the device: add() stores one pair's scalars
+    without a host synchronisation, mean() makes one device -> host transfer and applies the reference's aggregation - entries that are
+    exactly 0 (a metric the pair does not have, a level without landmarks, an input slot a shorter loader never filled) are missing."""
+
+    def __init__(self, metric_names: Sequence[str], latent_levels: int, loader_names: Sequence[str], num_inputs: int) -> None:
+        self.metric_names, self.loader_names = list(metric_names), list(loader_names)
+        self.latent_levels, self.num_inputs = int(latent_levels), int(num_inputs)
+        if not self.metric_names or not self.loader_names or self.latent_levels < 1 or self.num_inputs < 1:
+            raise ValueError("PerformanceTable: at least one metric, level, loader and input")
+        self._values = None               # [metrics, levels, datasets, inputs] on the device of the first score
+
+    def add(self, k: int, j: int, scores: Dict[str, Dict[int, torch.Tensor]]) -> None:
+        """loader k, input j: scores as level_scores / performance return them; a metric of the table that is absent from scores stays 0"""
+        if not (0 <= k < len(self.loader_names) and 0 <= j < self.num_inputs):
+            raise IndexError(f"PerformanceTable.add: loader {k}, input {j} outside ({len(self.loader_names)}, {self.num_inputs})")
+        unknown = set(scores) - set(self.metric_names)
+        if unknown:
+            raise KeyError(f"PerformanceTable.add: metrics {sorted(unknown)} are not in the table ({self.metric_names})")
+        for h, name in enumerate(self.metric_names):
+            for l, v in scores.get(name, {}).items():
+                if not 0 <= l < self.latent_levels:
+                    raise IndexError(f"PerformanceTable.add: level {l} of {name} outside {self.latent_levels} levels")
+                v = torch.as_tensor(v).detach().reshape(())
+                if self._values is None:
+                    self._values = torch.zeros((len(self.metric_names), self.latent_levels, len(self.loader_names), self.num_inputs),
+                                               device=v.device, dtype=torch.float64)
+                self._values[h, l, k, j] = v                       # a device-side copy of one scalar: nothing waits for it
+
+    def mean(self) -> Tuple[np.ndarray, Tuple[np.ndarray, np.ndarray]]:
+        """([levels, datasets x metrics] array, (sets, mets) column labels): zeros -> NaN, nanmean over the inputs, columns ordered as
+        evaluate.py:1483-1488 (np.repeat(loader_names, num_metrics), np.tile(metric_names, num_datasets))"""
+        shape = (len(self.metric_names), self.latent_levels, len(self.loader_names), self.num_inputs)
+        all_metrics = np.zeros(shape, dtype=float) if self._values is None else self._values.cpu().numpy()        # the one transfer
+        all_metrics = all_metrics.copy()
+        all_metrics[all_metrics == 0] = np.nan
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=RuntimeWarning)                      # "Mean of empty slice": an all-missing cell is NaN
+            mean_metrics = np.nanmean(all_metrics, axis=-1)
+        data = np.concatenate(mean_metrics.T, axis=1)
+        sets = np.repeat(self.loader_names, len(self.metric_names))
+        mets = np.tile(self.metric_names, len(self.loader_names))
+        return data, (sets, mets)

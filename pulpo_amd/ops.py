@@ -2200,6 +2200,24 @@ def percent_leq0(x):
     return out
 
 
+@torch.no_grad()
+def field_quality(df, normalize: bool = True):
+    """(mean, unbiased std, 100 * count(J <= 0) / numel) of jacobian_det(df, normalize) as 0-d device tensors, in one pass that reads the
+    field once and stores no determinant map (evaluate.py:1440-1449: JDetStd with lamb = 1 and JDetLeq0).  The determinant is
+    jacobian_det's bit for bit; deterministic.  df (B,3,D,H,W) or (B,2,H,W).  Evaluation only: no autograd."""
+    if _is2d(df):
+        return field_quality(_lift(df), normalize)
+    _require_gpu(df)
+    d = planar(df.detach())
+    B, C, D, H, W = d.shape
+    if C != (2 if D == 1 else 3):
+        raise PulpoHipError("field_quality: displacement field (B,3,D,H,W) or, for slices, (B,2,1,H,W) expected")
+    ws = torch.empty(lib.query("pulpo_field_quality_ws_bytes", B, D, H, W), device=d.device, dtype=torch.uint8)
+    out = torch.empty(3, device=d.device, dtype=torch.float32)
+    lib.call("pulpo_field_quality", _ptr(d), _ptr(out), _ptr(ws), B, D, H, W, int(bool(normalize)), _stream())
+    return out[0], out[1], out[2]
+
+
 def warp_landmarks(lm, df):
     """lm.long() - df[:, :, lm[0,:,0], lm[0,:,1], lm[0,:,2]].transpose(-2, -1)   (evaluate.py:410-423, src/components/utils.py:15-25)
     lm: (1, n_landmarks, ndims); df: (n_samples, ndims, ...) -> (n_samples, n_landmarks, ndims) float.  Out-of-range landmarks raise
@@ -2300,6 +2318,38 @@ def warp_labels(df, labels, num_classes: int, target=None, onehot: bool = False,
     _raise_on_flag(flag, "warp_labels")
     out = [t.squeeze(2) if is2d else t for t in (oh, am) if t is not None] + ([dice] if dice is not None else [])
     return out[0] if len(out) == 1 else tuple(out)
+
+
+@torch.no_grad()
+def warp_labels_soft_dice(df, labels, num_classes: int, target):
+    """The level Dice of Evaluate.performance (evaluate.py:1427, 1454-1455) without a one-hot tensor: for p = warp3d(df, one_hot(labels)) and
+    t = F.interpolate(one_hot(target), size=grid of df, tri/bilinear, align_corners=False), dice_bc = (2 sum(p t) + 1e-6) / (sum(t^2) +
+    sum(p^2) + 1e-6) with sums over the grid (Soft_dice_loss, src/losses.py:137-145).  df (B,3,D,H,W) fp32 (2-D: (B,2,H,W)); labels and target
+    (B,1,...) uint8 / int32 label maps, each on a grid of its own (the full-resolution maps for every level's field).  Returns (dice_bc (B, C),
+    their mean as a 0-d tensor = 1 - level_dice / num_pixels).  Deterministic.  A label outside [0, num_classes) raises IndexError (one
+    host read).  Evaluation only: no autograd."""
+    _require_gpu(df)
+    _require_labels(labels, target)
+    if target is None:
+        raise ValueError("warp_labels_soft_dice: a target label map is required")
+    if _is2d(df):
+        df, labels, target = _lift_field(df), _lift(labels), _lift(target)
+    df, labels, target = planar(df.detach()), labels.contiguous(), target.to(labels.dtype).contiguous()
+    B, C = df.shape[0], int(num_classes)
+    for name, t in (("label", labels), ("target", target)):
+        if t.dim() != 5 or t.shape[1] != 1 or t.shape[0] != B:
+            raise PulpoHipError(f"{name} map (B, 1, ...) expected for a field of shape {tuple(df.shape)}, got {tuple(t.shape)}")
+    dev = df.device
+    dice = torch.empty((B, C), device=dev, dtype=torch.float32)
+    mean = torch.empty((), device=dev, dtype=torch.float32)
+    flag = torch.zeros(3, device=dev, dtype=torch.int32)
+    _check_labels(labels, C, flag, 1)
+    _check_labels(target, C, flag, 2)
+    ws = torch.empty(lib.query("pulpo_warp_labels_ws_bytes", B, C), device=dev, dtype=torch.uint8)
+    lib.call("pulpo_warp_labels_soft_dice", _ptr(df), _ptr(labels), _ptr(target), _LABEL_DT[labels.dtype], C, _ptr(dice), _ptr(mean), _ptr(ws),
+             _int_ptr(flag, 0), B, *[int(v) for v in df.shape[2:]], *[int(v) for v in labels.shape[2:]], *[int(v) for v in target.shape[2:]], _stream())
+    _raise_on_flag(flag, "warp_labels_soft_dice")
+    return dice, mean
 
 
 class LabelMoments(StreamingMoments):

@@ -19,15 +19,15 @@ import torch
 from . import ops
 
 
-def _as_labels(seg: torch.Tensor, num_classes: Optional[int]) -> Tuple[torch.Tensor, int]:
+def _as_labels(seg: torch.Tensor, num_classes: Optional[int], who: str = "mc_uncertainty") -> Tuple[torch.Tensor, int]:
     """a label map (B, 1, ...) plus its class count, from either a label map (uint8 / int32 / int64, num_classes required) or the
     reference's float one-hot map (B, C, ...), converted once by arg-max"""
     if seg.is_floating_point() and seg.shape[1] > 1:
         if num_classes is not None and num_classes != seg.shape[1]:
-            raise ValueError(f"mc_uncertainty: num_classes {num_classes} differs from the one-hot map's {seg.shape[1]} channels")
+            raise ValueError(f"{who}: num_classes {num_classes} differs from the one-hot map's {seg.shape[1]} channels")
         return ops.labels_from_onehot(seg), int(seg.shape[1])
     if num_classes is None:
-        raise ValueError("mc_uncertainty: a label-map segmentation needs num_classes")
+        raise ValueError(f"{who}: a label-map segmentation needs num_classes")
     if seg.dtype not in (torch.uint8, torch.int32):
         seg = seg.to(torch.int32)
     return seg, int(num_classes)
