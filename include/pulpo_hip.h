@@ -34,7 +34,7 @@ extern "C" {
  * PULPO_ABI_VERSION is bumped whenever a prototype below changes its argument list or a buffer contract, or an entry point is removed
  * (history: INTEGRATION.md "ABI history").  pulpo_abi_version() returns the value the library was built with: a client compares it with
  * the header it was compiled against before the first call (pulpo_amd/_lib.py does). */
-#define PULPO_ABI_VERSION 5
+#define PULPO_ABI_VERSION 6
 int pulpo_abi_version(void);
 const char* pulpo_last_error(void);
 
@@ -286,6 +286,33 @@ int pulpo_warp_landmarks(const float* lm /*(nlm,nd)*/, const float* df /*(nsamp,
 int pulpo_field_quality_blocks(int B, int D, int H, int W);
 size_t pulpo_field_quality_ws_bytes(int B, int D, int H, int W);
 int pulpo_field_quality(const float* df, float* out /* 3 floats */, void* ws, int B, int D, int H, int W, int normalize, void* stream);
+
+/* ------------------------------------------------------------------------------------------ inverse fields (since ABI 6)
+ * Inference only: no backward forms.  The level fields are stationary velocity fields, so the inverse of the flow VecInt(v) is VecInt(-v).
+ * pulpo_vecint_pair_fwd: VecInt.forward (src/network_blocks.py:160-177) on v and on -v in one call: fwd = VecInt(v), the result of
+ *   pulpo_vecint_fwd (the same coordinate arithmetic and gather), inv = VecInt(-v).  v, fwd, inv planar (B,3,D,H,W); D == 1 is the 2-D form
+ *   (channel 0 zero).  No intermediate field is kept: fields of up to 2048 voxels per batch element run every step in one launch out of
+ *   LDS, larger ones one launch per squaring step for both directions, ping-ponging between (fwd, inv) and two scratch fields.
+ *   nsteps == 0: fwd = v, inv = -v.  scratch: pulpo_vecint_pair_scratch_floats() floats (2 fields, or 0 for the one-launch form).
+ * The two operators below sample GEOMETRICALLY: position p + d in voxel units clamped to [0, S - 1], trilinear with upper corner
+ *   min(i0 + 1, S - 1), so that a zero field is the identity.  This is deliberately NOT SpatialTransformer's (S-1)-normalised,
+ *   align_corners=False sampling (src/network_blocks.py:101-121), whose zero field is not the identity; it reads a
+ *   field the way the reference's landmark rule does (evaluate.py:410-423: displacements in voxels at voxel centres).
+ * pulpo_inverse_consistency: a, b planar (B,3,D,H,W), or (B,2,1,H,W) for D == 1.  r(p) = b(p) + a(p + b(p)) per voxel, in double;
+ *   out[0] = mean of ||r||_2 over the B*D*H*W voxels, out[1] = its maximum - how far a o b is from the identity, the sanity number of a
+ *   diffeomorphic model next to "JDetLeq0" (evaluate.py:1441-1446).  One pass, no composed field; block partials in double added in a fixed
+ *   order: two calls give the same bits.  ws: pulpo_inverse_consistency_ws_bytes(B, D, H, W) bytes.
+ * pulpo_transport_points: out[s][k][:] = pts[k] + field[s](pts[k]), the field sampled at the point's own fractional position.  With the
+ *   inverse field this carries landmarks from the moving to the fixed image exactly where Evaluate.warp_landmarks (evaluate.py:410-423,
+ *   long(lm) - df[long(lm)]) is the first-order approximation at a truncated position.  Layout as pulpo_warp_landmarks: pts (npts,nd),
+ *   field (nsamp,nd,D,H,W), nd 3, or 2 with D == 1; *flag (zeroed here) = 1 if a point lies outside [0, S - 1]. */
+size_t pulpo_vecint_pair_scratch_floats(int B, int D, int H, int W, int nsteps);
+int pulpo_vecint_pair_fwd(const float* v, float* fwd, float* inv, float* scratch /*nullable if the query is 0*/, int B, int D, int H, int W, int nsteps,
+                          void* stream);
+size_t pulpo_inverse_consistency_ws_bytes(int B, int D, int H, int W);
+int pulpo_inverse_consistency(const float* a, const float* b, float* out /* 2 floats */, void* ws, int B, int D, int H, int W, void* stream);
+int pulpo_transport_points(const float* pts /*(npts,nd)*/, const float* field /*(nsamp,nd,D,H,W)*/, float* out /*(nsamp,npts,nd)*/, int npts,
+                           int nsamp, int nd, int D, int H, int W, int* flag, void* stream);
 
 /* ------------------------------------------------------------------------------- Monte-Carlo uncertainty statistics
  * evaluate.py:222-251 stacks N sampled volumes / fields per level and takes torch.std(axis=0) (unbiased) then torch.mean over the

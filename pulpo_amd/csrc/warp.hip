@@ -254,24 +254,7 @@ __global__ __launch_bounds__(VI_THREADS) void vecint_fwd_lds_kernel(const float*
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int vox = tid + j * VI_THREADS;
-            if (vox < V) {
-                const int x = vox % W, y = (vox / W) % H, z = vox / (W * H);
-                const Corner cz = sample_coord((float)z, fld[vox], D, D);
-                const Corner cy = sample_coord((float)y, fld[V + vox], H, H);
-                const Corner cx = sample_coord((float)x, fld[2 * V + vox], W, W);
-                const int o00 = (cz.i0 * H + cy.i0) * W, o01 = (cz.i0 * H + cy.i1) * W;
-                const int o10 = (cz.i1 * H + cy.i0) * W, o11 = (cz.i1 * H + cy.i1) * W;
-                const float wz0 = 1.f - cz.f, wy0 = 1.f - cy.f, wx0 = 1.f - cx.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float* s = fld + c * V;
-                    float val = wz0 * wy0 * wx0 * s[o00 + cx.i0] + wz0 * wy0 * cx.f * s[o00 + cx.i1] + wz0 * cy.f * wx0 * s[o01 + cx.i0] +
-                                wz0 * cy.f * cx.f * s[o01 + cx.i1] + cz.f * wy0 * wx0 * s[o10 + cx.i0] + cz.f * wy0 * cx.f * s[o10 + cx.i1] +
-                                cz.f * cy.f * wx0 * s[o11 + cx.i0] + cz.f * cy.f * cx.f * s[o11 + cx.i1];
-                    val += s[vox];
-                    nv[j][c] = val;
-                }
-            }
+            if (vox < V) pulpo::vecint_step_voxel(fld, V, vox, D, H, W, nv[j]);
         }
         __syncthreads();                               // every gather of this step is done: the field may be overwritten
         float* out = work + (long)(k + 1) * n + b * 3 * V;

@@ -54,6 +54,13 @@ def warp_landmarks(lm: torch.Tensor, df: torch.Tensor) -> torch.Tensor:
     return ops.warp_landmarks(lm, df)
 
 
+def transport_landmarks(lm: torch.Tensor, inv_df: torch.Tensor) -> torch.Tensor:
+    """landmarks of the moving image carried onto the fixed image by the INVERSE field, sampled trilinearly at the landmarks' own
+    positions: lm + inv_df(lm).  warp_landmarks (evaluate.py:410-423), long(lm) - df[long(lm)], is the first-order approximation of this
+    map, evaluated at a truncated position.  lm (1, n, ndims), inv_df (n_samples, ndims, ...) -> (n_samples, n, ndims)."""
+    return ops.transport_points(lm, inv_df)
+
+
 def resize_dfs(dfs: Dict[int, torch.Tensor], target_size=None) -> Dict[int, torch.Tensor]:
     """every level's field resized (and rescaled) to the size of level 0 or to `target_size` - the evident intent of the reference's
     src/components/utils.py:4-13, which cannot run as written (`range(dfs.keys())`, the batch dimension used as a size; SURVEY.md §2 #7)"""

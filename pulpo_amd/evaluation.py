@@ -21,6 +21,8 @@ from . import eval_metrics, ops
 from .uncertainty import _as_labels
 
 METRICS = ("RMSE", "JDetStd", "JDetLeq0", "Dice", "LM_MAE", "LM_Euclid")
+# the rows level_scores adds when it is given the inverse fields (no counterpart in the reference, which has no inverse transform)
+INVERSE_METRICS = ("InvCons", "InvConsMax", "LM_MAE_inv", "LM_Euclid_inv")
 
 
 def _zero(ref: torch.Tensor) -> torch.Tensor:
@@ -30,7 +32,7 @@ def _zero(ref: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Tensor], y: torch.Tensor, *, seg_x: Optional[torch.Tensor] = None,
                  seg_y: Optional[torch.Tensor] = None, lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
-                 num_classes: Optional[int] = None) -> Dict[str, Dict[int, torch.Tensor]]:
+                 num_classes: Optional[int] = None, final_dfs_inv: Optional[Dict[int, torch.Tensor]] = None) -> Dict[str, Dict[int, torch.Tensor]]:
     """The level losses of evaluate.py:1433-1474 for one pair: {metric: {level: 0-d device tensor}}.
 
     outputs[l], final_dfs[l]: the warped image and the final field of level l (predict_deterministic + combine_dfs); y: the fixed image.
@@ -43,7 +45,11 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
     lm_x and lm_y (1, n, ndims) add
       LM_MAE / LM_Euclid: lm_mae / lm_euclid(warp_landmarks(lm_x, final_dfs[0]), lm_y) at level 0, the reference's 0 at the levels above
       and, for empty landmark tensors, at level 0 too (:1457-1474).
-    Without segmentations or landmarks their rows are absent (the reference stores 0: PerformanceTable fills rows that were not added with 0)."""
+    Without segmentations or landmarks their rows are absent (the reference stores 0: PerformanceTable fills rows that were not added with 0).
+    final_dfs_inv[l] (the inverse fields of model.combine_dfs_bidirectional) adds, beside the rows above, which do not change,
+      InvCons[l] / InvConsMax[l]   mean / maximum over the voxels of ||inv(p) + fwd(p + inv(p))||_2 in voxels (ops.inverse_consistency)
+      LM_MAE_inv / LM_Euclid_inv   with landmarks: lm_mae / lm_euclid(transport_landmarks(lm_x, final_dfs_inv[0]), lm_y) at level 0, the
+                                   landmarks carried by the inverse field sampled at their own positions; 0 where LM_MAE / LM_Euclid are."""
     levels = sorted(outputs.keys())
     if sorted(final_dfs.keys()) != levels:
         raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs {sorted(final_dfs.keys())}")
@@ -51,6 +57,8 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
         raise ValueError("level_scores: seg_x and seg_y go together")
     if (lm_x is None) != (lm_y is None):
         raise ValueError("level_scores: lm_x and lm_y go together")
+    if final_dfs_inv is not None and sorted(final_dfs_inv.keys()) != levels:
+        raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs_inv {sorted(final_dfs_inv.keys())}")
     res: Dict[str, Dict[int, torch.Tensor]] = {"RMSE": {}, "JDetStd": {}, "JDetLeq0": {}}
     for l in levels:
         out = outputs[l]
@@ -71,20 +79,37 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
             ref = lm_y.to(device=moved.device, dtype=moved.dtype)
             res["LM_MAE"][0] = eval_metrics.lm_mae(moved, ref)
             res["LM_Euclid"][0] = eval_metrics.lm_euclid(moved, ref)
+    if final_dfs_inv is not None:
+        res["InvCons"], res["InvConsMax"] = {}, {}
+        for l in levels:
+            res["InvCons"][l], res["InvConsMax"][l] = ops.inverse_consistency(final_dfs[l], final_dfs_inv[l])
+        if lm_x is not None:
+            res["LM_MAE_inv"] = {l: _zero(y) for l in levels}
+            res["LM_Euclid_inv"] = {l: _zero(y) for l in levels}
+            if lm_x.numel() and lm_y.numel():
+                moved = eval_metrics.transport_landmarks(lm_x, final_dfs_inv[0])
+                ref = lm_y.to(device=moved.device, dtype=moved.dtype)
+                res["LM_MAE_inv"][0] = eval_metrics.lm_mae(moved, ref)
+                res["LM_Euclid_inv"][0] = eval_metrics.lm_euclid(moved, ref)
     return res
 
 
 @torch.no_grad()
 def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torch.Tensor] = None, seg_y: Optional[torch.Tensor] = None,
                 lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
-                num_classes: Optional[int] = None) -> Dict[str, Dict[int, torch.Tensor]]:
+                num_classes: Optional[int] = None, inverse: bool = False) -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
-    unless the samplers are pinned (network_blocks.FixedNoiseSampler)."""
+    unless the samplers are pinned (network_blocks.FixedNoiseSampler).  inverse=True also integrates the inverse fields
+    (model.combine_dfs_bidirectional: one integration call per level for both directions) and adds the INVERSE_METRICS rows."""
     outputs, individual_dfs = model.predict_deterministic(x, y)
-    _, final_dfs = model.combine_dfs(individual_dfs)
-    return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes)
+    final_dfs_inv = None
+    if inverse:
+        _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
+    else:
+        _, final_dfs = model.combine_dfs(individual_dfs)
+    return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv)
 
 
 @torch.no_grad()

@@ -242,24 +242,63 @@ class PULPo(ABC, LightningModule):
         outs = self.autoencoder(x, self.downpath(x, y, _needed=self._needed_levels), deterministic=True)
         return outs[7], outs[4]
 
+    @torch.no_grad()
+    def predict_bidirectional(self, x: torch.Tensor, y: torch.Tensor, N: int = 1, deterministic: bool = False):
+        """predict (or, with deterministic, predict_deterministic) + combine_dfs with the inverse transform beside it: a dict of
+          outputs, individual_dfs   what predict / predict_deterministic return
+          final_dfs                 combine_dfs(individual_dfs)[1]
+          final_dfs_inv             the inverse fields of combine_dfs_bidirectional
+          outputs_inv               {l: spatial_transform(final_dfs_inv[l], y)}: the fixed image on the moving image's grid, warped the
+                                    way predict warps x
+        Inference only: no autograd."""
+        if deterministic:
+            outputs, individual_dfs = self.predict_deterministic(x, y)
+            _, final, final_inv = self.combine_dfs_bidirectional(individual_dfs)
+        else:
+            _, samples = self.predict_output_samples(x, y, N)
+            individual_dfs = {k: v.mean(dim=1) for k, v in samples.items()}
+            _, final, final_inv = self.combine_dfs_bidirectional(individual_dfs)
+            outputs = {k: self.autoencoder.decoders[k].spatial_transform(final[k], x) for k in final}          # as predict
+        outputs_inv = {k: self.autoencoder.decoders[k].spatial_transform(final_inv[k], y) for k in final_inv}
+        return {"outputs": outputs, "individual_dfs": individual_dfs, "final_dfs": final, "final_dfs_inv": final_inv, "outputs_inv": outputs_inv}
+
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:  # type: ignore[override]
         return self.autoencoder(x, self.downpath(x, y, _needed=self._needed_levels))[7][0]
 
     # ------------------------------------------------------------------------------------------------ helpers
     def combine_dfs(self, individual_dfs: Dict[int, torch.Tensor]):
         """individual level fields -> (combined, integrated + resized) fields (reference models.py:349-368)"""
-        combined, final = {}, {}
+        combined, final = self._combine_levels(individual_dfs), {}
+        for l in reversed(range(self.latent_levels)):
+            final[l] = self._resize_integrated(l, ops.vecint(combined[l], 7))
+        return combined, final
+
+    def _combine_levels(self, individual_dfs: Dict[int, torch.Tensor]) -> Dict[int, torch.Tensor]:
+        """the combined velocity field of every level: the level's own plus the resized one of the level below (reference models.py:349-360)"""
+        combined = {}
         for l in reversed(range(self.latent_levels)):
             if l + 1 in combined:
                 ratio = individual_dfs[l].shape[2] / individual_dfs[l + 1].shape[2]
                 combined[l] = ResizeTransform(vel_resize=1 / ratio, ndims=self.ndims)(combined[l + 1], add=individual_dfs[l])
             else:
                 combined[l] = individual_dfs[l]
+        return combined
+
+    def _resize_integrated(self, l: int, integrated: torch.Tensor) -> torch.Tensor:
+        """an integrated level field at its final size: the input size at level 0 and with df_resolution "full_res", its own otherwise"""
+        target = self.input_size if (l == 0 or self.hparams.df_resolution == "full_res") else integrated.shape[2:]
+        return ResizeTransform(vel_resize=1 / (target[0] / integrated.shape[2]), ndims=self.ndims)(integrated)
+
+    def combine_dfs_bidirectional(self, individual_dfs: Dict[int, torch.Tensor]):
+        """combine_dfs with the inverse transform: (combined, final, final_inv).  The level fields are stationary velocity fields, so the
+        inverse of the flow is the integral of -combined[l]: final_inv[l] is that integral, resized like final[l].  Both integrals come from
+        one ops.vecint_pair call per level (under no_grad: no intermediate fields kept; with gradients: two vecint calls)."""
+        combined = self._combine_levels(individual_dfs)
+        final, final_inv = {}, {}
         for l in reversed(range(self.latent_levels)):
-            integrated = ops.vecint(combined[l], 7)
-            target = self.input_size if (l == 0 or self.hparams.df_resolution == "full_res") else combined[l].shape[2:]
-            final[l] = ResizeTransform(vel_resize=1 / (target[0] / integrated.shape[2]), ndims=self.ndims)(integrated)
-        return combined, final
+            fwd, inv = ops.vecint_pair(combined[l], 7)
+            final[l], final_inv[l] = self._resize_integrated(l, fwd), self._resize_integrated(l, inv)
+        return combined, final, final_inv
 
     def transform_segmentation(self, dfs: Dict[int, torch.Tensor], seg: torch.Tensor):
         """warp the (pooled) segmentation maps with each level's field (reference models.py:370-388)"""

@@ -1808,6 +1808,34 @@ def vecint(v, nsteps: int = 7):
     return _VecInt.apply(v, int(nsteps))
 
 
+def vecint_pair(v, nsteps: int = 7):
+    """(VecInt(v), VecInt(-v)): the integrated field and its inverse (a stationary velocity field's flow is inverted by integrating -v;
+    network_blocks.py:160-177).  Under torch.no_grad(), or when v does not require grad, one pulpo_vecint_pair_fwd call that keeps no
+    intermediate field (two results + two scratch fields; none of the nsteps + 1 fields per direction that vecint saves for its backward
+    pass).  Otherwise (vecint(v), vecint(-v)), so that a bidirectional loss backpropagates through the existing backward kernels."""
+    if torch.is_grad_enabled() and v.requires_grad:
+        return vecint(v, nsteps), vecint(-v, nsteps)
+    if _is2d(v):
+        fwd, inv = vecint_pair(_lift_field(v), nsteps)
+        return _unlift_field(fwd), _unlift_field(inv)
+    _require_gpu(v)
+    v = planar(v.detach())
+    nsteps = int(nsteps)
+    B, C, D, H, W = v.shape
+    if C != 3:
+        raise PulpoHipError(f"vecint_pair: velocity field (B,3,D,H,W) or (B,2,H,W) expected, got {tuple(v.shape)}")
+    fwd, inv = torch.empty_like(v), torch.empty_like(v)
+    nscr = lib.query("pulpo_vecint_pair_scratch_floats", B, D, H, W, nsteps)
+    scratch = torch.empty(nscr, device=v.device, dtype=torch.float32) if nscr else None
+    t0 = _hbm_begin("vecint_pair_fwd")
+    lib.call("pulpo_vecint_pair_fwd", _ptr(v), _ptr(fwd), _ptr(inv), _ptr(scratch), B, D, H, W, nsteps, _stream())
+    # the one-launch form reads v per direction and writes a result each; the step form reads v once, writes two fields, then every step
+    # reads and writes both directions' fields
+    fields = 4 if (nsteps and not nscr) else 3 + 4 * nsteps
+    _hbm_end(t0, "vecint_pair_fwd", 4.0 * v.numel() * fields)
+    return fwd, inv
+
+
 # ------------------------------------------------------------------------------------------------ losses
 class _NCC(torch.autograd.Function):
     @staticmethod
@@ -2236,6 +2264,54 @@ def warp_landmarks(lm, df):
              ctypes.cast(flag.data_ptr(), ctypes.POINTER(ctypes.c_int)), _stream())
     if int(flag.item()):
         raise IndexError("warp_landmarks: landmark index out of bounds of the displacement field")
+    return out
+
+
+@torch.no_grad()
+def inverse_consistency(a, b):
+    """(mean, max) over all voxels of ||b(p) + a(p + b(p))||_2 in voxel units as 0-d device tensors: how far the composition a o b is from
+    the identity (a = final field, b = its inverse: the sanity number of a diffeomorphic model next to JDetLeq0).  a sampled geometrically
+    - position clamped to [0, S - 1], trilinear, a zero field is the identity - not with SpatialTransformer's normalisation.  One pass,
+    no composed field; deterministic.  a, b (B,3,D,H,W) or (B,2,H,W) of one shape.  Evaluation only: no autograd."""
+    _require_gpu(a, b)
+    if tuple(a.shape) != tuple(b.shape):
+        raise PulpoHipError(f"inverse_consistency: fields of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if _is2d(a):
+        a, b = _lift(a), _lift(b)
+    a, b = planar(a.detach()), planar(b.detach())
+    B, C, D, H, W = a.shape
+    if C != (2 if D == 1 else 3):
+        raise PulpoHipError("inverse_consistency: displacement fields (B,3,D,H,W) or, for slices, (B,2,H,W) expected")
+    ws = torch.empty(lib.query("pulpo_inverse_consistency_ws_bytes", B, D, H, W), device=a.device, dtype=torch.uint8)
+    out = torch.empty(2, device=a.device, dtype=torch.float32)
+    t0 = _hbm_begin("inverse_consistency")
+    lib.call("pulpo_inverse_consistency", _ptr(a), _ptr(b), _ptr(out), _ptr(ws), B, D, H, W, _stream())
+    _hbm_end(t0, "inverse_consistency", 4.0 * (a.numel() + b.numel()))                  # both fields read once (the gather hits in cache)
+    return out[0], out[1]
+
+
+def transport_points(pts, field):
+    """pts + field(pts): points carried by a displacement field sampled trilinearly at their own fractional positions (geometric
+    sampling, as inverse_consistency).  With the inverse field of vecint_pair / combine_dfs_bidirectional this moves landmarks of the moving
+    image onto the fixed image exactly; warp_landmarks' long(lm) - df[long(lm)] is its first-order approximation at a truncated position.
+    pts: (1, n, ndims) voxel coordinates; field: (n_samples, ndims, ...) -> (n_samples, n, ndims).  A point outside [0, S - 1] raises
+    IndexError like warp_landmarks (one host read of a device flag: an evaluation-time helper)."""
+    _require_gpu(field)
+    nd = field.dim() - 2
+    if pts.dim() != 3 or pts.shape[0] != 1 or pts.shape[2] != nd or field.shape[1] != nd or nd not in (2, 3):
+        raise PulpoHipError(f"transport_points: pts (1, n, ndims) and field (samples, ndims, ...) expected, got {tuple(pts.shape)} and {tuple(field.shape)}")
+    d = field.detach().contiguous()
+    p = pts.detach().to(device=d.device, dtype=torch.float32).contiguous()
+    npts, ns = int(pts.shape[1]), int(d.shape[0])
+    D, H, W = (1, *d.shape[2:]) if nd == 2 else d.shape[2:]
+    out = torch.empty((ns, npts, nd), device=d.device, dtype=torch.float32)
+    flag = torch.empty(1, device=d.device, dtype=torch.int32)
+    t0 = _hbm_begin("transport_points")
+    lib.call("pulpo_transport_points", _ptr(p), _ptr(d), _ptr(out), npts, ns, nd, int(D), int(H), int(W),
+             ctypes.cast(flag.data_ptr(), ctypes.POINTER(ctypes.c_int)), _stream())
+    _hbm_end(t0, "transport_points", 4.0 * (p.numel() + out.numel() + 8 * nd * npts * ns))      # the points, the results, 8 corners per component
+    if int(flag.item()):
+        raise IndexError("transport_points: point outside the displacement field")
     return out
 
 
