@@ -34,7 +34,7 @@ extern "C" {
  * PULPO_ABI_VERSION is bumped whenever a prototype below changes its argument list or a buffer contract, or an entry point is removed
  * (history: INTEGRATION.md "ABI history").  pulpo_abi_version() returns the value the library was built with: a client compares it with
  * the header it was compiled against before the first call (pulpo_amd/_lib.py does). */
-#define PULPO_ABI_VERSION 6
+#define PULPO_ABI_VERSION 7
 int pulpo_abi_version(void);
 const char* pulpo_last_error(void);
 
@@ -213,6 +213,10 @@ int pulpo_feedback_up2_bwd(const float* gout, int64_t gops, float* const* gsrcs 
  *   on coordinates normalised by (S-1); image size may differ from the grid size (src/models.py:330).
  * vecint: VecInt.forward (src/network_blocks.py:173-177).  work = (nsteps+1) field buffers, result = the last one. */
 int pulpo_warp3d_fwd(const float* df, const float* img, float* out, int B, int C, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, void* stream);
+/* pulpo_warp3d_fwd for a single-channel weight volume (cost-function masks): the same sample positions and corners, the
+ * interpolation as nested differences a + f (b - a), which returns a constant volume exactly (the eight fp32 corner weights of
+ * pulpo_warp3d_fwd do not sum to exactly 1).  mask (B,1,Di,Hi,Wi) -> out (B,1,Dg,Hg,Wg); forward only. */
+int pulpo_warp_mask_fwd(const float* df, const float* mask, float* out, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, void* stream);
 int pulpo_warp3d_bwd(const float* df, const float* img, const float* gout, float* gdf, float* gimg, int B, int C, int Dg, int Hg, int Wg, int Di,
                      int Hi, int Wi, void* stream);
 int pulpo_vecint_fwd(const float* v, float* work, int B, int D, int H, int W, int nsteps, void* stream);
@@ -232,6 +236,22 @@ int pulpo_ncc_fwd(const float* I, const float* J, float* S /*5N, saved*/, float*
                   int win, void* stream);
 int pulpo_ncc_bwd(const float* I, const float* J, const float* S, float* T /*6N scratch*/, const float* gscale, float coef, float* gJ, int B, int D,
                   int H, int W, int win, void* stream);
+/* Cost-function masking (no counterpart in the reference, whose loaders raise "Mask not implemented").  wa and wb
+ * (wb nullable = 1) are weight volumes (B,1,D,H,W) in [0,1], m = wa * wb is formed inside the kernels.  The window sums run over all
+ * voxels; m weights the per-voxel cost.  The forward kernels write TWO columns per block, partial[2 * blk] = sum of m * cost and
+ * partial[2 * blk + 1] = sum of m (2 * pulpo_loss_blocks / pulpo_metric_blocks floats); pulpo_masked_finish reduces them in double on the
+ * device:  q = scale * sum0 / M (0 when M == 0),
+ *   out[0] = root ? sqrt(q) : q                          the loss
+ *   out[1] = d out[0] / d sum0  (0 when M == 0, or when root and q == 0): the backward entry points take  upstream * out[1]  as gscale
+ *   out[2] = M / count,  out[3] = M
+ * ncc_masked:    scale = -gamma * V                   -> -gamma * V * sum(m cc) / M;     bwd: gJ = coef * gscale * (box(m a) + 2 J box(m b) + I box(m c))
+ * sqdiff_masked: a, b planar (B,C,V), m broadcast over the C channels, sum of m counted once per voxel;
+ *                scale = V / C -> L2_masked, scale = 1 / C with root -> RMSE_masked;  bwd: ga = coef * gscale * 2 m (a - b) */
+int pulpo_ncc_masked_fwd(const float* I, const float* J, const float* wa, const float* wb /*nullable*/, float* S /*5N, saved*/,
+                         float* T /*10N scratch*/, float* partial /*2 * pulpo_loss_blocks(N)*/, int B, int D, int H, int W, int win, void* stream);
+int pulpo_ncc_masked_bwd(const float* I, const float* J, const float* S, const float* wa, const float* wb /*nullable*/, float* T /*6N scratch*/,
+                         const float* gscale, float coef, float* gJ, int B, int D, int H, int W, int win, void* stream);
+int pulpo_masked_finish(const float* partial, int nblk, double scale, int root, double count, float* out /*4*/, void* stream);
 int pulpo_kl_fwd(const float* mu, const float* sigma, const float* mu1 /*nullable: 0*/, const float* sigma1 /*nullable: 1*/, int64_t n,
                  float* partial, void* stream);
 int pulpo_kl_bwd(const float* mu, const float* sigma, const float* mu1, const float* sigma1, const float* gscale, float coef, float* gmu,
@@ -251,6 +271,10 @@ int pulpo_weighted_sum_bwd(const float* gtotal, const float* glevels, const floa
 int pulpo_metric_blocks(int64_t n);
 int pulpo_sqdiff_fwd(const float* a, const float* b, int64_t n, float* partial, void* stream);
 int pulpo_sqdiff_bwd(const float* a, const float* b, const float* gscale, float coef, float* ga, int64_t n, void* stream);
+int pulpo_sqdiff_masked_fwd(const float* a, const float* b, const float* wa, const float* wb /*nullable*/,
+                            float* partial /*2 * pulpo_metric_blocks(B*C*V)*/, int B, int C, int64_t V, void* stream);
+int pulpo_sqdiff_masked_bwd(const float* a, const float* b, const float* wa, const float* wb /*nullable*/, const float* gscale, float coef, float* ga,
+                            int B, int C, int64_t V, void* stream);
 int pulpo_dice_blocks(int64_t V);
 int pulpo_dice_fwd(const float* inp, const float* tgt, int nplanes, int64_t V, float dice_factor, float* partial, double* numden, float* loss,
                    void* stream);

@@ -106,6 +106,41 @@ __global__ __launch_bounds__(256) void ncc_final_kernel(const float* __restrict_
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
+// ncc_final_kernel with a cost-function mask (m = wa * wb, wb nullable): the window sums are those of the unmasked kernel, the voxel's
+// cc is weighted by m; partial[2 blk] = sum of m * cc, partial[2 blk + 1] = sum of m
+__global__ __launch_bounds__(256) void ncc_masked_final_kernel(const float* __restrict__ in, float* __restrict__ S, long N, int extent, long stride, int pad,
+                                                                 float nwin, const float* __restrict__ wa, const float* __restrict__ wb,
+                                                                 float* __restrict__ partial) {
+    __shared__ float sh[4];
+    float local = 0.f, msum = 0.f;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < N; e += (long)gridDim.x * blockDim.x) {
+        const int pos = (int)((e / stride) % extent);
+        const int lo = max(-pad, -pos), hi = min(pad, extent - 1 - pos);
+        float s[5];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) {
+            const float* q = in + c * N + e;
+            float acc = 0.f;
+            for (int k = lo; k <= hi; ++k) acc += q[k * stride];
+            s[c] = acc;
+            S[c * N + e] = acc;
+        }
+        const float uI = s[0] / nwin, uJ = s[1] / nwin;
+        const float cross = s[4] - uJ * s[0] - uI * s[1] + uI * uJ * nwin;
+        const float Iv = s[2] - 2.f * uI * s[0] + uI * uI * nwin;
+        const float Jv = s[3] - 2.f * uJ * s[1] + uJ * uJ * nwin;
+        const float m = wb != nullptr ? wa[e] * wb[e] : wa[e];
+        local += m * (cross * cross / (Iv * Jv + 1e-8f));
+        msum += m;
+    }
+    const float t = block_sum_256(local, sh);
+    const float tm = block_sum_256(msum, sh);
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = t;
+        partial[2 * blockIdx.x + 1] = tm;
+    }
+}
+
 // ---- marching form of the strided passes (windows up to 11): a thread walks a segment of one line along the axis and keeps the window's
 // 2 PAD + 1 values of every channel in registers, so each input value is loaded once (the kernels above re-read it for each of the 9 taps:
 // at 160^3 the D pass's working set - 9 planes x 5 channels, 4.6 MB - exceeds an XCD's L2 and the pass ran at 0.9 TB/s).  The window
@@ -113,6 +148,8 @@ __global__ __launch_bounds__(256) void ncc_final_kernel(const float* __restrict_
 //   MODE 0: out = box(in)                                  (nch = NCH channels)
 //   MODE 1: S = box(in), partial[block] = sum of cc        (ncc_final_kernel)
 //   MODE 2: gJ = k0 (box(a) + 2 J box(b) + I box(c))       (ncc_bwd_final_kernel)
+//   MODE 3: MODE 1 with a mask: partial[2 block] = sum of m cc, partial[2 block + 1] = sum of m   (ncc_masked_final_kernel);
+//           the mask planes wa and wb (nullable) arrive in the I and J arguments, which MODE 1 leaves unused
 // Work items = (segment, group of 256 lines), distributed over the workgroups in a strided loop.
 template <int NCH, int PAD, int MODE>
 __global__ __launch_bounds__(256) void box_march_kernel(const float* __restrict__ in, float* __restrict__ out, long N, long nlines, int extent,
@@ -124,6 +161,7 @@ __global__ __launch_bounds__(256) void box_march_kernel(const float* __restrict_
     const long nlg = (nlines + 255) / 256;
     const long nitem = nlg * nseg;
     float local = 0.f;
+    [[maybe_unused]] float msum = 0.f;
     [[maybe_unused]] const float k0 = MODE == 2 ? coef * (gscale != nullptr ? gscale[0] : 1.f) : 0.f;
     for (long item = blockIdx.x; item < nitem; item += gridDim.x) {
         const long lg = item % nlg;
@@ -171,6 +209,16 @@ __global__ __launch_bounds__(256) void box_march_kernel(const float* __restrict_
                         const float Iv = sum[2] - 2.f * uI * sum[0] + uI * uI * nwin;
                         const float Jv = sum[3] - 2.f * uJ * sum[1] + uJ * uJ * nwin;
                         local += cross * cross / (Iv * Jv + 1e-8f);
+                    } else if constexpr (MODE == 3) {
+#pragma unroll
+                        for (int c = 0; c < NCH; ++c) out[c * N + e] = sum[c];
+                        const float uI = sum[0] / nwin, uJ = sum[1] / nwin;
+                        const float cross = sum[4] - uJ * sum[0] - uI * sum[1] + uI * uJ * nwin;
+                        const float Iv = sum[2] - 2.f * uI * sum[0] + uI * uI * nwin;
+                        const float Jv = sum[3] - 2.f * uJ * sum[1] + uJ * uJ * nwin;
+                        const float m = J != nullptr ? I[e] * J[e] : I[e];
+                        local += m * (cross * cross / (Iv * Jv + 1e-8f));
+                        msum += m;
                     } else {
                         out[e] = k0 * (sum[0] + 2.f * J[e] * sum[1] + I[e] * sum[2]);
                     }
@@ -181,6 +229,14 @@ __global__ __launch_bounds__(256) void box_march_kernel(const float* __restrict_
     if constexpr (MODE == 1) {
         const float t = block_sum_256(local, sh);
         if (threadIdx.x == 0) partial[blockIdx.x] = t;
+    }
+    if constexpr (MODE == 3) {
+        const float t = block_sum_256(local, sh);
+        const float tm = block_sum_256(msum, sh);
+        if (threadIdx.x == 0) {
+            partial[2 * blockIdx.x] = t;
+            partial[2 * blockIdx.x + 1] = tm;
+        }
     }
 }
 
@@ -224,6 +280,59 @@ __global__ __launch_bounds__(256) void ncc_abc_kernel(const float* __restrict__ 
         A[e] = -2.f * r * SI / nwin + 2.f * r * r * Iv * SJ / nwin;
         A[N + e] = -r * r * Iv;
         A[2 * N + e] = 2.f * r;
+    }
+}
+
+// ncc_abc_kernel with the voxel's three fields weighted by the mask m = wa * wb (wb nullable): d(sum m cc) = box(m a) + 2 J box(m b) + I box(m c)
+__global__ __launch_bounds__(256) void ncc_masked_abc_kernel(const float* __restrict__ S, float* __restrict__ A, long N, float nwin,
+                                                               const float* __restrict__ wa, const float* __restrict__ wb) {
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < N; e += (long)gridDim.x * blockDim.x) {
+        const float SI = S[e], SJ = S[N + e], SII = S[2 * N + e], SJJ = S[3 * N + e], SIJ = S[4 * N + e];
+        const float cross = SIJ - SI * SJ / nwin;
+        const float Iv = SII - SI * SI / nwin;
+        const float Jv = SJJ - SJ * SJ / nwin;
+        const float Dn = Iv * Jv + 1e-8f;
+        const float r = cross / Dn;
+        const float m = wb != nullptr ? wa[e] * wb[e] : wa[e];
+        A[e] = m * (-2.f * r * SI / nwin + 2.f * r * r * Iv * SJ / nwin);
+        A[N + e] = m * (-r * r * Iv);
+        A[2 * N + e] = m * (2.f * r);
+    }
+}
+
+// both columns of a masked loss's block partials, summed in double in a fixed order, and the scalars the loss and its backward pass need
+// (include/pulpo_hip.h): nothing of the M == 0 guard or of the factor 1 / M touches the host
+__global__ __launch_bounds__(256) void masked_finish_kernel(const float* __restrict__ partial, int nblk, double scale, int root, double count,
+                                                              float* __restrict__ out) {
+    __shared__ double red[2][256];
+    double s = 0.0, m = 0.0;
+    for (int r = threadIdx.x; r < nblk; r += 256) {
+        s += (double)partial[2 * r];
+        m += (double)partial[2 * r + 1];
+    }
+    red[0][threadIdx.x] = s;
+    red[1][threadIdx.x] = m;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + half];
+            red[1][threadIdx.x] += red[1][threadIdx.x + half];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double S0 = red[0][0], M = red[1][0];
+        const bool live = M > 0.0;
+        const double q = live ? scale * S0 / M : 0.0;
+        double val = q, dval = live ? scale / M : 0.0;
+        if (root) {
+            val = q > 0.0 ? sqrt(q) : 0.0;
+            dval = q > 0.0 ? dval / (2.0 * val) : 0.0;
+        }
+        out[0] = (float)val;
+        out[1] = (float)dval;
+        out[2] = (float)(M / count);
+        out[3] = (float)M;
     }
 }
 
@@ -450,6 +559,70 @@ PULPO_API int pulpo_ncc_bwd(const float* I, const float* J, const float* S, floa
     if (march) return launch_march<3, 2>(pad, eblocks(N, 1024), st, T1, gJ, N, D, (long)H * W, 0.f, nullptr, I, J, gscale, coef);
     hipLaunchKernelGGL(ncc_bwd_final_kernel, dim3(eblocks(N)), dim3(256), 0, st, T1, I, J, gscale, coef, gJ, N, D, (long)H * W, pad);
     return pulpo::check_launch("ncc bwd final");
+}
+
+// pulpo_ncc_fwd with a cost-function mask: the W and H passes are the unmasked ones, the last (D) pass weights cc by m = wa * wb and
+// reduces two columns (sum of m cc, sum of m).  partial: 2 * pulpo_loss_blocks(N) floats; finish with pulpo_masked_finish(scale = -gamma V).
+PULPO_API int pulpo_ncc_masked_fwd(const float* I, const float* J, const float* wa, const float* wb, float* S, float* T, float* partial, int B, int D,
+                                   int H, int W, int win, void* stream) {
+    PULPO_REQUIRE(I && J && wa && S && T && partial && B > 0 && D > 0 && H > 0 && W > 0, "ncc_masked_fwd: bad arguments");
+    PULPO_REQUIRE(win >= 1 && (win & 1) && win <= 31, "ncc_masked_fwd: window must be odd and <= 31");
+    hipStream_t st = (hipStream_t)stream;
+    const long N = (long)B * D * H * W;
+    const int pad = win / 2, span = 64 - 2 * pad, segs = pulpo::cdiv(W, span);
+    const long nrows = (long)B * D * H;
+    float* T1 = T;
+    float* T2 = T + 5 * N;
+    hipLaunchKernelGGL(box_x_kernel<0>, dim3(eblocks(nrows * segs * 64)), dim3(256), 0, st, I, J, T1, N, nrows, W, pad, 5, segs);
+    int rc = pulpo::check_launch("ncc masked box_x");
+    if (rc) return rc;
+    const bool march = pad >= 1 && pad <= 5;
+    if (march && H > 1) rc = launch_march<5, 0>(pad, eblocks(N, 1024), st, T1, T2, N, H, (long)W, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f);
+    else {
+        hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N)), dim3(256), 0, st, T1, T2, N, 5, H, (long)W, pad);
+        rc = pulpo::check_launch("ncc masked box_y");
+    }
+    if (rc) return rc;
+    if (march) return launch_march<5, 3>(pad, pulpo_loss_blocks(N), st, T2, S, N, D, (long)H * W, ncc_window_count(win, D), partial, wa, wb, nullptr, 0.f);
+    hipLaunchKernelGGL(ncc_masked_final_kernel, dim3(pulpo_loss_blocks(N)), dim3(256), 0, st, T2, S, N, D, (long)H * W, pad, ncc_window_count(win, D), wa, wb,
+                       partial);
+    return pulpo::check_launch("ncc masked final");
+}
+
+// gJ = coef * gscale[0] * d(sum m cc)/dJ: the masked ncc_abc kernel, then the three box passes and the combine of pulpo_ncc_bwd.  T: 6*N floats.
+PULPO_API int pulpo_ncc_masked_bwd(const float* I, const float* J, const float* S, const float* wa, const float* wb, float* T, const float* gscale,
+                                   float coef, float* gJ, int B, int D, int H, int W, int win, void* stream) {
+    PULPO_REQUIRE(I && J && S && wa && T && gJ && B > 0 && D > 0 && H > 0 && W > 0, "ncc_masked_bwd: bad arguments");
+    PULPO_REQUIRE(win >= 1 && (win & 1) && win <= 31, "ncc_masked_bwd: window must be odd and <= 31");
+    hipStream_t st = (hipStream_t)stream;
+    const long N = (long)B * D * H * W;
+    const int pad = win / 2, span = 64 - 2 * pad, segs = pulpo::cdiv(W, span);
+    const long nrows = (long)B * D * H;
+    float* T1 = T;
+    float* T2 = T + 3 * N;
+    hipLaunchKernelGGL(ncc_masked_abc_kernel, dim3(eblocks(N)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D), wa, wb);
+    int rc = pulpo::check_launch("ncc masked abc");
+    if (rc) return rc;
+    hipLaunchKernelGGL(box_x_kernel<1>, dim3(eblocks(nrows * segs * 64)), dim3(256), 0, st, T1, nullptr, T2, N, nrows, W, pad, 3, segs);
+    rc = pulpo::check_launch("ncc masked bwd box_x");
+    if (rc) return rc;
+    const bool march = pad >= 1 && pad <= 5;
+    if (march && H > 1) rc = launch_march<3, 0>(pad, eblocks(N, 1024), st, T2, T1, N, H, (long)W, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f);
+    else {
+        hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N)), dim3(256), 0, st, T2, T1, N, 3, H, (long)W, pad);
+        rc = pulpo::check_launch("ncc masked bwd box_y");
+    }
+    if (rc) return rc;
+    if (march) return launch_march<3, 2>(pad, eblocks(N, 1024), st, T1, gJ, N, D, (long)H * W, 0.f, nullptr, I, J, gscale, coef);
+    hipLaunchKernelGGL(ncc_bwd_final_kernel, dim3(eblocks(N)), dim3(256), 0, st, T1, I, J, gscale, coef, gJ, N, D, (long)H * W, pad);
+    return pulpo::check_launch("ncc masked bwd final");
+}
+
+// the scalars of a masked loss from its two-column block partials (include/pulpo_hip.h); out: 4 floats
+PULPO_API int pulpo_masked_finish(const float* partial, int nblk, double scale, int root, double count, float* out, void* stream) {
+    PULPO_REQUIRE(partial && out && nblk > 0 && count > 0, "masked_finish: bad arguments");
+    hipLaunchKernelGGL(masked_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nblk, scale, root, count, out);
+    return pulpo::check_launch("masked_finish");
 }
 
 // sum over all elements of the KL integrand; finish with pulpo_colsum(scale = 0.5 / B).  mu1 / sigma1 nullable = N(0,1).

@@ -35,6 +35,41 @@ __global__ __launch_bounds__(256) void sqdiff_bwd_kernel(const float* __restrict
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) ga[e] = k0 * (a[e] - b[e]);
 }
 
+// L2_loss with a cost-function mask m = wa * wb (wb nullable) of shape (B,1,V), broadcast over the C channels of a, b (B,C,V):
+// partial[2 blk] = sum of m (a - b)^2, partial[2 blk + 1] = sum of m, every voxel's m counted once (at channel 0)
+__global__ __launch_bounds__(256) void sqdiff_masked_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ wa,
+                                                                  const float* __restrict__ wb, int C, long V, long n, float* __restrict__ partial) {
+    __shared__ float sh[4];
+    float local = 0.f, msum = 0.f;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const long plane = e / V, v = e - plane * V;
+        const long bi = plane / C;
+        const long mi = bi * V + v;
+        const float m = wb != nullptr ? wa[mi] * wb[mi] : wa[mi];
+        const float d = a[e] - b[e];
+        local += m * (d * d);
+        if (plane - bi * C == 0) msum += m;
+    }
+    const float t = block_sum_256(local, sh);
+    const float tm = block_sum_256(msum, sh);
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = t;
+        partial[2 * blockIdx.x + 1] = tm;
+    }
+}
+
+__global__ __launch_bounds__(256) void sqdiff_masked_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ wa,
+                                                                  const float* __restrict__ wb, const float* __restrict__ gscale, float coef,
+                                                                  float* __restrict__ ga, int C, long V, long n) {
+    const float k0 = 2.f * coef * (gscale != nullptr ? gscale[0] : 1.f);
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const long plane = e / V, v = e - plane * V;
+        const long mi = (plane / C) * V + v;
+        const float m = wb != nullptr ? wa[mi] * wb[mi] : wa[mi];
+        ga[e] = k0 * (m * (a[e] - b[e]));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ Soft dice
 // grid (nb, nplanes): partial[(plane*nb + blk)*3 + {0,1,2}] = sum t*i, sum t*t, sum i*i over the block's voxels of that plane
 __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict__ inp, const float* __restrict__ tgt, long V, float* __restrict__ partial) {
@@ -343,6 +378,23 @@ PULPO_API int pulpo_sqdiff_bwd(const float* a, const float* b, const float* gsca
     PULPO_REQUIRE(a && b && ga && n > 0, "sqdiff_bwd: bad arguments");
     hipLaunchKernelGGL(sqdiff_bwd_kernel, dim3(eblocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, gscale, coef, ga, (long)n);
     return pulpo::check_launch("sqdiff_bwd");
+}
+// masked L2_loss: a, b planar (B,C,V), wa / wb (nullable) (B,1,V).  partial: 2 * pulpo_metric_blocks(B*C*V) floats (sum of m d^2, sum of m);
+// finish with pulpo_masked_finish (scale = V / C: L2_masked; scale = 1 / C and root: RMSE_masked)
+PULPO_API int pulpo_sqdiff_masked_fwd(const float* a, const float* b, const float* wa, const float* wb, float* partial, int B, int C, int64_t V,
+                                      void* stream) {
+    PULPO_REQUIRE(a && b && wa && partial && B > 0 && C > 0 && V > 0, "sqdiff_masked_fwd: bad arguments");
+    const long n = (long)B * C * V;
+    hipLaunchKernelGGL(sqdiff_masked_fwd_kernel, dim3(pulpo_metric_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, wa, wb, C, (long)V, n, partial);
+    return pulpo::check_launch("sqdiff_masked_fwd");
+}
+// ga = coef * gscale[0] * 2 m (a - b)
+PULPO_API int pulpo_sqdiff_masked_bwd(const float* a, const float* b, const float* wa, const float* wb, const float* gscale, float coef, float* ga, int B,
+                                      int C, int64_t V, void* stream) {
+    PULPO_REQUIRE(a && b && wa && ga && B > 0 && C > 0 && V > 0, "sqdiff_masked_bwd: bad arguments");
+    const long n = (long)B * C * V;
+    hipLaunchKernelGGL(sqdiff_masked_bwd_kernel, dim3(eblocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, wa, wb, gscale, coef, ga, C, (long)V, n);
+    return pulpo::check_launch("sqdiff_masked_bwd");
 }
 
 // Soft_dice_loss: nplanes = B*C planes of V voxels. partial: nplanes*pulpo_dice_blocks(V)*3 floats; numden: 2*nplanes doubles (kept for backward)

@@ -44,6 +44,33 @@ __global__ __launch_bounds__(256) void warp_fwd_kernel(const float* __restrict__
     }
 }
 
+// warp_fwd_kernel<1> for a weight volume (a cost-function mask): the same sample position and corners, the
+// interpolation written as nested differences a + f (b - a) instead of eight products with the corner weights.  The eight fp32 weights
+// do not sum to exactly 1 (a warped volume of ones is 1 - 1.2e-7 at one voxel in eight); the nested form returns a constant volume
+// exactly, so a mask of ones stays a mask of ones.  No gradient: masks are constants of the loss.
+__global__ __launch_bounds__(256) void warp_mask_fwd_kernel(const float* __restrict__ df, const float* __restrict__ img, float* __restrict__ out, int B,
+                                                              int Dg, int Hg, int Wg, int Di, int Hi, int Wi) {
+    const long Vg = (long)Dg * Hg * Wg, Vi = (long)Di * Hi * Wi;
+    const long total = (long)B * Vg;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long b = B == 1 ? 0 : e / Vg, v = e - b * Vg;
+        const int vi = (int)v;
+        const int x = vi % Wg, y = (vi / Wg) % Hg, z = vi / (Wg * Hg);
+        const float* d = df + b * 3 * Vg + v;
+        const Corner cz = sample_coord((float)z, d[0], Dg, Di);
+        const Corner cy = sample_coord((float)y, d[Vg], Hg, Hi);
+        const Corner cx = sample_coord((float)x, d[2 * Vg], Wg, Wi);
+        const long o00 = ((long)cz.i0 * Hi + cy.i0) * Wi, o01 = ((long)cz.i0 * Hi + cy.i1) * Wi;
+        const long o10 = ((long)cz.i1 * Hi + cy.i0) * Wi, o11 = ((long)cz.i1 * Hi + cy.i1) * Wi;
+        const float* s = img + b * Vi;
+        const float a00 = s[o00 + cx.i0], a01 = s[o01 + cx.i0], a10 = s[o10 + cx.i0], a11 = s[o11 + cx.i0];
+        const float x00 = a00 + cx.f * (s[o00 + cx.i1] - a00), x01 = a01 + cx.f * (s[o01 + cx.i1] - a01);
+        const float x10 = a10 + cx.f * (s[o10 + cx.i1] - a10), x11 = a11 + cx.f * (s[o11 + cx.i1] - a11);
+        const float y0 = x00 + cy.f * (x01 - x00), y1 = x10 + cy.f * (x11 - x10);
+        out[e] = y0 + cz.f * (y1 - y0);
+    }
+}
+
 // gdf (nullable) and gimg (nullable) are ACCUMULATED with float atomics (caller zero-fills or pre-loads them).
 // gdf_direct: write gdf with plain stores instead (only legal when nothing else adds to gdf concurrently).
 template <bool GDF_ATOMIC>
@@ -387,6 +414,15 @@ __global__ __launch_bounds__(256) void fx_to_float_kernel(long long* __restrict_
 }  // namespace
 
 // df: (B,3,Dg,Hg,Wg) planar; img: (B,C,Di,Hi,Wi) planar; out: (B,C,Dg,Hg,Wg)
+// out (B,1,Dg,Hg,Wg) = the single-channel weight volume mask (B,1,Di,Hi,Wi) under pulpo_warp3d_fwd's warp, constants preserved exactly
+PULPO_API int pulpo_warp_mask_fwd(const float* df, const float* mask, float* out, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, void* stream) {
+    PULPO_REQUIRE(df && mask && out && B > 0, "warp_mask_fwd: bad arguments");
+    PULPO_REQUIRE(Dg >= 1 && Hg > 1 && Wg > 1 && Di > 0 && Hi > 0 && Wi > 0 && (Dg > 1 || Di == 1), "warp_mask_fwd: grid H, W must be > 1 (depth 1 = 2-D form, with a depth-1 mask)");
+    PULPO_REQUIRE((long)Dg * Hg * Wg < (1L << 31), "warp_mask_fwd: grids of 2^31 voxels and more are not supported");
+    hipLaunchKernelGGL(warp_mask_fwd_kernel, dim3(eblocks((long)B * Dg * Hg * Wg)), dim3(256), 0, (hipStream_t)stream, df, mask, out, B, Dg, Hg, Wg, Di, Hi, Wi);
+    return pulpo::check_launch("warp_mask_fwd");
+}
+
 PULPO_API int pulpo_warp3d_fwd(const float* df, const float* img, float* out, int B, int C, int Dg, int Hg, int Wg, int Di, int Hi, int Wi,
                                void* stream) {
     PULPO_REQUIRE(df && img && out && B > 0 && C > 0, "warp3d_fwd: bad arguments");

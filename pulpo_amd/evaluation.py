@@ -23,6 +23,8 @@ from .uncertainty import _as_labels
 METRICS = ("RMSE", "JDetStd", "JDetLeq0", "Dice", "LM_MAE", "LM_Euclid")
 # the rows level_scores adds when it is given the inverse fields (no counterpart in the reference, which has no inverse transform)
 INVERSE_METRICS = ("InvCons", "InvConsMax", "LM_MAE_inv", "LM_Euclid_inv")
+# the rows level_scores adds when it is given cost-function masks
+MASK_METRICS = ("RMSE_masked", "MaskFrac")
 
 
 def _zero(ref: torch.Tensor) -> torch.Tensor:
@@ -32,7 +34,8 @@ def _zero(ref: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Tensor], y: torch.Tensor, *, seg_x: Optional[torch.Tensor] = None,
                  seg_y: Optional[torch.Tensor] = None, lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
-                 num_classes: Optional[int] = None, final_dfs_inv: Optional[Dict[int, torch.Tensor]] = None) -> Dict[str, Dict[int, torch.Tensor]]:
+                 num_classes: Optional[int] = None, final_dfs_inv: Optional[Dict[int, torch.Tensor]] = None,
+                 mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None) -> Dict[str, Dict[int, torch.Tensor]]:
     """The level losses of evaluate.py:1433-1474 for one pair: {metric: {level: 0-d device tensor}}.
 
     outputs[l], final_dfs[l]: the warped image and the final field of level l (predict_deterministic + combine_dfs); y: the fixed image.
@@ -49,7 +52,12 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
     final_dfs_inv[l] (the inverse fields of model.combine_dfs_bidirectional) adds, beside the rows above, which do not change,
       InvCons[l] / InvConsMax[l]   mean / maximum over the voxels of ||inv(p) + fwd(p + inv(p))||_2 in voxels (ops.inverse_consistency)
       LM_MAE_inv / LM_Euclid_inv   with landmarks: lm_mae / lm_euclid(transport_landmarks(lm_x, final_dfs_inv[0]), lm_y) at level 0, the
-                                   landmarks carried by the inverse field sampled at their own positions; 0 where LM_MAE / LM_Euclid are."""
+                                   landmarks carried by the inverse field sampled at their own positions; 0 where LM_MAE / LM_Euclid are.
+    mask_x and / or mask_y (weight volumes (B,1,...) in [0,1] at full resolution, 1 = counted; no counterpart in the reference) add,
+    beside the rows above, which do not change, with m_l = warp_mask(final_dfs[l], mask_x) * (mask_y resized to the level), the level masks
+    of the training step (PULPo.level_masks),
+      RMSE_masked[l]   sqrt(sum(m_l (outputs[l] - target)^2) / (C sum(m_l))), 0 for an empty m_l      (ops.rmse_masked)
+      MaskFrac[l]      mean of m_l"""
     levels = sorted(outputs.keys())
     if sorted(final_dfs.keys()) != levels:
         raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs {sorted(final_dfs.keys())}")
@@ -67,6 +75,15 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
         num_pixels = float(np.prod(size))
         res["RMSE"][l] = torch.sqrt(ops.l2_loss(out, target) / num_pixels)
         _, res["JDetStd"][l], res["JDetLeq0"][l] = ops.field_quality(final_dfs[l], True)
+    if mask_x is not None or mask_y is not None:
+        res["RMSE_masked"], res["MaskFrac"] = {}, {}
+        for l in levels:
+            size = tuple(outputs[l].shape[2:])
+            target = y if size == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
+            wx = ops.warp_mask(final_dfs[l], mask_x) if mask_x is not None else None
+            wy = None if mask_y is None else (mask_y.float() if size == tuple(mask_y.shape[2:]) else ops.resize_trilinear(mask_y.float(), size))
+            pair = (wx, wy) if wx is not None else (wy, None)
+            res["RMSE_masked"][l], res["MaskFrac"][l] = ops.rmse_masked(outputs[l], target, pair[0], pair[1])
     if seg_x is not None:
         lab_x, C = _as_labels(seg_x, num_classes, "level_scores")
         lab_y, _ = _as_labels(seg_y, C, "level_scores")
@@ -97,19 +114,22 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
 @torch.no_grad()
 def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torch.Tensor] = None, seg_y: Optional[torch.Tensor] = None,
                 lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
-                num_classes: Optional[int] = None, inverse: bool = False) -> Dict[str, Dict[int, torch.Tensor]]:
+                num_classes: Optional[int] = None, inverse: bool = False, mask_x: Optional[torch.Tensor] = None,
+                mask_y: Optional[torch.Tensor] = None) -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
     unless the samplers are pinned (network_blocks.FixedNoiseSampler).  inverse=True also integrates the inverse fields
-    (model.combine_dfs_bidirectional: one integration call per level for both directions) and adds the INVERSE_METRICS rows."""
+    (model.combine_dfs_bidirectional: one integration call per level for both directions) and adds the INVERSE_METRICS rows; mask_x / mask_y
+    add the MASK_METRICS rows."""
     outputs, individual_dfs = model.predict_deterministic(x, y)
     final_dfs_inv = None
     if inverse:
         _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
     else:
         _, final_dfs = model.combine_dfs(individual_dfs)
-    return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv)
+    return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv,
+                        mask_x=mask_x, mask_y=mask_y)
 
 
 @torch.no_grad()

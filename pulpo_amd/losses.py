@@ -11,7 +11,7 @@ kernels as depth-1 volumes.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -43,6 +43,12 @@ class KL_nondiagonal:
 def L2_loss(input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """spatial sum of squared differences, mean over batch and channels (reference losses.py:79-83)"""
     return ops.l2_loss(input, target)
+
+
+def L2_loss_masked(input: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, mask2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """L2_loss with the per-voxel cost weighted by m = mask * mask2 ((B,1,...) weights in [0,1], 1 = counted) and normalised by the
+    mask's volume: V * sum(m d^2) / (C * sum(m)), 0 for an empty mask"""
+    return ops.l2_loss_masked(input, target, mask, mask2)
 
 
 def Soft_dice_loss(input: torch.Tensor, target: torch.Tensor, dice_factor=1) -> torch.Tensor:
@@ -82,6 +88,15 @@ def NCC_loss(y_pred: torch.Tensor, y_true: torch.Tensor, win_size: int = 9, gamm
     if y_pred.dim() not in (4, 5):
         raise NotImplementedError("NCC_loss: volumes (B,1,D,H,W) or slices (B,1,H,W) expected")
     return ops.ncc_loss(y_pred, y_true, win_size, gamma)
+
+
+def NCC_loss_masked(y_pred: torch.Tensor, y_true: torch.Tensor, mask: torch.Tensor, mask2: Optional[torch.Tensor] = None, win_size: int = 9,
+                    gamma: float = 0.05) -> torch.Tensor:
+    """NCC_loss with cost-function masking: -gamma * V * sum(m cc) / sum(m), m = mask * mask2, 0 for an empty mask.  The window sums run
+    over all voxels; the mask weights the per-voxel cost"""
+    if y_pred.dim() not in (4, 5):
+        raise NotImplementedError("NCC_loss_masked: volumes (B,1,D,H,W) or slices (B,1,H,W) expected")
+    return ops.ncc_loss_masked(y_pred, y_true, mask, mask2, win_size, gamma)
 
 
 def L2_reg(deformation_field: torch.Tensor, lamb=0) -> torch.Tensor:
@@ -150,7 +165,19 @@ class HierarchicalReconstructionLoss(nn.Module):
         self.ndims = ndims
         self.mode = "trilinear" if ndims == 3 else "bilinear"
 
-    def forward(self, y_hat, y, y_hat_seg=None, seg_y=None, gamma: float = 0.05, dice_factor: int = 1):
+    def _ncc(self, l, y_hat_l, y_target, pair, gamma):
+        if pair is None:
+            return NCC_loss(y_hat_l, y_target, gamma=gamma, win_size=self.window_size[l])
+        return NCC_loss_masked(y_hat_l, y_target, pair[0], pair[1], gamma=gamma, win_size=self.window_size[l])
+
+    @staticmethod
+    def _mse(y_hat_l, y_target, pair):
+        return L2_loss(y_hat_l, y_target) if pair is None else L2_loss_masked(y_hat_l, y_target, pair[0], pair[1])
+
+    def forward(self, y_hat, y, y_hat_seg=None, seg_y=None, gamma: float = 0.05, dice_factor: int = 1,
+                masks: Optional[Dict[int, Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]] = None):
+        """masks (not in the reference): {level: (mask_a, mask_b)}, weight volumes at the level's size, either of a pair may be None; a level
+        with a pair uses the masked NCC / MSE term (cost weighted by mask_a * mask_b), the Dice term is unchanged"""
         single = len(self.recon_loss) == 1 and self.recon_loss[0] in ("mse", "ncc", "dice")
         loss = 0.0
         all_levels, terms = {}, {}
@@ -158,16 +185,19 @@ class HierarchicalReconstructionLoss(nn.Module):
             size = y_hat[l].shape[2:]
             # F.interpolate(y, size) of the reference; the identity resize at full resolution is skipped
             y_target = y if tuple(size) == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
+            pair = masks.get(l) if masks is not None else None
+            if pair is not None:
+                pair = tuple(m for m in pair if m is not None)
+                pair = None if not pair else (pair[0], pair[1] if len(pair) > 1 else None)
             if single and self.recon_loss[0] != "dice":
                 # one term per level (the default, ["ncc"]): weighting and summation of all levels in one launch; x / 1 is x
-                terms[l] = (NCC_loss(y_hat[l], y_target, gamma=gamma, win_size=self.window_size[l]) if self.recon_loss[0] == "ncc"
-                            else L2_loss(y_hat[l], y_target))
+                terms[l] = self._ncc(l, y_hat[l], y_target, pair, gamma) if self.recon_loss[0] == "ncc" else self._mse(y_hat[l], y_target, pair)
                 continue
             term = 0.0
             if "mse" in self.recon_loss:
-                term = term + w * L2_loss(y_hat[l], y_target)
+                term = term + w * self._mse(y_hat[l], y_target, pair)
             if "ncc" in self.recon_loss:
-                term = term + w * NCC_loss(y_hat[l], y_target, gamma=gamma, win_size=self.window_size[l])
+                term = term + w * self._ncc(l, y_hat[l], y_target, pair, gamma)
             if "dice" in self.recon_loss:
                 seg_size = y_hat_seg[l].shape[2:]
                 seg_target = seg_y if tuple(seg_size) == tuple(seg_y.shape[2:]) else ops.resize_trilinear(seg_y, seg_size)

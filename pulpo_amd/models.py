@@ -124,7 +124,25 @@ class PULPo(ABC, LightningModule):
         self._pending_nan_probe = None          # (pinned flag, event) of an earlier step's NaN test
 
     # ------------------------------------------------------------------------------------------------ steps
-    def _forward_and_losses(self, x, y, seg_x=None, seg_y=None):
+    @torch.no_grad()
+    def level_masks(self, final_dfs, mask_x=None, mask_y=None):
+        """{level: (mask_x warped by the level's field - the warp y_hat[l] gets, in the constant-preserving form of ops.warp_mask -, mask_y
+        resized to the level as y is)} for cost-function masking; None unless the model was built with mask=True and at least one mask is
+        non-empty"""
+        has = lambda m: m is not None and m.numel() > 0
+        if not self.mask or not (has(mask_x) or has(mask_y)):
+            return None
+        mx = mask_x.float() if has(mask_x) else None
+        my = mask_y.float() if has(mask_y) else None
+        pairs = {}
+        for l, df in final_dfs.items():
+            size = tuple(df.shape[2:])
+            wx = ops.warp_mask(df, mx) if mx is not None else None
+            wy = None if my is None else (my if size == tuple(my.shape[2:]) else ops.resize_trilinear(my, size))
+            pairs[l] = (wx, wy)
+        return pairs
+
+    def _forward_and_losses(self, x, y, seg_x=None, seg_y=None, mask_x=None, mask_y=None):
         acts = self.downpath(x, y, _needed=self._needed_levels)
         outs = self.autoencoder(x, acts)
         mus, sigmas, samples, velocity_fields, individual_dfs, combined_dfs, final_dfs, y_hat = outs
@@ -134,7 +152,9 @@ class PULPo(ABC, LightningModule):
         else:
             y_hat_seg = {k: None for k in final_dfs}
         kl, kl_levels = self.hierarchical_kl_loss(prior_mus, prior_sigmas, mus, sigmas, scale=self.beta)       # (kl * beta, beta * levels: models.py:161-162)
-        rec, rec_levels = self.hierarchical_recon_loss(y_hat, y, y_hat_seg, seg_y, gamma=self.hparams.gamma, dice_factor=self.hparams.dice_factor)
+        masks = self.level_masks(final_dfs, mask_x, mask_y)
+        rec, rec_levels = self.hierarchical_recon_loss(y_hat, y, y_hat_seg, seg_y, gamma=self.hparams.gamma, dice_factor=self.hparams.dice_factor,
+                                                       **({} if masks is None else {"masks": masks}))
         reg, reg_levels = self.hierarchical_regularization(final_dfs, lamb=self.hparams.lamb)
         total = kl + rec + reg
         return outs, (prior_mus, prior_sigmas), (total, kl, rec, reg), (kl_levels, rec_levels, reg_levels)
@@ -201,7 +221,7 @@ class PULPo(ABC, LightningModule):
         eng = self._engine()
         if eng is not None and torch.is_grad_enabled():
             eng.arm(not self._ddp_wrapped())          # multi-rank: this forward pass registers the triggers of the bucketed gradient exchange
-        outs, priors, (total, kl, rec, reg), levels = self._forward_and_losses(x, y, seg_x, seg_y)
+        outs, priors, (total, kl, rec, reg), levels = self._forward_and_losses(x, y, seg_x, seg_y, mask1, mask2)
         self.log_dict({"train/kl_loss": kl, "train/reconstruction_loss": rec, "train/regularization_loss": reg, "train/total_loss": total},
                       on_step=True, on_epoch=True, prog_bar=True)
         self._log_levels("train", outs[0], outs[1], priors, levels, on_step=False, on_epoch=True)
@@ -215,7 +235,7 @@ class PULPo(ABC, LightningModule):
         if batch_idx == self.trainer.num_val_batches[0] - 1:
             self.validation_counter += 1
         x, y, seg_x, seg_y, lm1, lm2, mask1, mask2 = batch
-        outs, priors, (total, kl, rec, reg), levels = self._forward_and_losses(x, y, seg_x, seg_y)
+        outs, priors, (total, kl, rec, reg), levels = self._forward_and_losses(x, y, seg_x, seg_y, mask1, mask2)
         self.log_dict({"val/kl_loss": kl, "val/reconstruction_loss": rec, "val/regularization_loss": reg, "val/total_loss": total}, on_epoch=True)
         self._log_levels("val", outs[0], outs[1], priors, levels, on_epoch=True)
         return total

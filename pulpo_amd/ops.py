@@ -1769,6 +1769,24 @@ def warp3d(df, img):
     return _Warp.apply(df, img)
 
 
+@torch.no_grad()
+def warp_mask(df, mask):
+    """a (B,1,...) weight volume under warp3d's warp, for cost-function masking: the same sample positions, the interpolation written so
+    that a constant volume comes back exactly (a mask of ones stays a mask of ones; warp3d returns 1 - 1.2e-7 at one voxel in eight).
+    No gradient.  Another dtype is converted to fp32."""
+    if _is2d(df):
+        return warp_mask(_lift_field(df), _lift(mask)).squeeze(2)
+    if mask.dim() != 5 or mask.shape[1] != 1 or mask.shape[0] != df.shape[0]:
+        raise ValueError(f"warp_mask: a (B,1,D,H,W) weight volume expected for a field of shape {tuple(df.shape)}, got {tuple(mask.shape)}")
+    df, mask = planar(df.detach()), planar(mask.detach() if mask.dtype == torch.float32 else mask.detach().float())
+    _require_gpu(df, mask)
+    B, _, Dg, Hg, Wg = df.shape
+    _, _, Di, Hi, Wi = mask.shape
+    out = torch.empty((B, 1, Dg, Hg, Wg), device=df.device, dtype=torch.float32)
+    lib.call("pulpo_warp_mask_fwd", _ptr(df), _ptr(mask), _ptr(out), B, Dg, Hg, Wg, Di, Hi, Wi, _stream())
+    return out
+
+
 class _VecInt(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, nsteps: int):
@@ -1877,6 +1895,83 @@ def ncc_loss(pred, true, win: int = 9, gamma: float = 0.05):
     if _is2d(pred):                                    # depth 1 selects the win x win window count in the kernel
         return ncc_loss(_lift(pred), _lift(true), win, gamma)
     return _NCC.apply(pred, true, int(win), float(gamma))
+
+
+# ---- cost-function masking: m = mask * mask2 weights the per-voxel cost, the loss is normalised by M = sum of m
+def _as_masks(img: torch.Tensor, mask, mask2, name: str):
+    """the masks of a (B,C,D,H,W) image as contiguous fp32 (B,1,D,H,W) device tensors (another dtype is converted here, once)"""
+    if mask is None:
+        raise ValueError(f"{name}: mask is required (mask2 is the optional one)")
+    want = (img.shape[0], 1) + tuple(img.shape[2:])
+    out = []
+    for m in (mask, mask2):
+        if m is None:
+            out.append(None)
+            continue
+        if tuple(m.shape) != want:
+            raise ValueError(f"{name}: mask of shape {tuple(m.shape)} for an image of shape {tuple(img.shape)} (expected {want})")
+        m = m.detach()
+        if not m.is_cuda:
+            raise PulpoHipError("pulpo_amd operators run on the GPU only (got a CPU mask); there is no CPU fallback")
+        out.append(planar(m if m.dtype == torch.float32 else m.float()))
+    return out[0], out[1]
+
+
+def _masked_finish(part: torch.Tensor, nblk: int, scale: float, root: bool, count: float) -> torch.Tensor:
+    """(loss, d loss / d sum, M / count, M) of a masked loss from its two-column block partials, on the device"""
+    out = torch.empty(4, device=part.device, dtype=torch.float32)
+    lib.call("pulpo_masked_finish", _ptr(part), nblk, float(scale), int(root), float(count), _ptr(out), _stream())
+    return out
+
+
+class _NCCMasked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, true, wa, wb, win: int, gamma: float):
+        _require_gpu(pred, true, wa, wb)
+        pred, true = planar(pred), planar(true)
+        B, C, D, H, W = pred.shape
+        if C != 1:
+            raise PulpoHipError("ncc: single-channel volumes expected")
+        N = B * D * H * W
+        dev = pred.device
+        S = torch.empty(5 * N, device=dev, dtype=torch.float32)
+        T = torch.empty(10 * N, device=dev, dtype=torch.float32)
+        nblk = lib.query("pulpo_loss_blocks", N)
+        part = torch.empty(2 * nblk, device=dev, dtype=torch.float32)
+        nmask = 1 if wb is None else 2
+        t0 = _hbm_begin("ncc_masked_fwd")
+        lib.call("pulpo_ncc_masked_fwd", _ptr(true), _ptr(pred), _ptr(wa), _ptr(wb), _ptr(S), _ptr(T), _ptr(part), B, D, H, W, win, _stream())
+        _hbm_end(t0, "ncc_masked_fwd", 4.0 * (22 + nmask) * N)   # ncc_fwd's traffic and one read of every mask plane
+        fin = _masked_finish(part, nblk, -gamma * (D * H * W), False, float(N))
+        ctx.save_for_backward(pred, true, S, wa, wb, fin)
+        ctx.win = win
+        return fin                                           # (loss, d loss / d sum, MaskFrac, M): the caller takes element 0
+
+    @staticmethod
+    def backward(ctx, gfin):
+        pred, true, S, wa, wb, fin = ctx.saved_tensors
+        B, _, D, H, W = pred.shape
+        N = B * D * H * W
+        T = torch.empty(6 * N, device=pred.device, dtype=torch.float32)
+        gJ = torch.empty_like(pred)
+        gs = (gfin[0] * fin[1]).contiguous()                 # upstream * (-gamma V / M), 0 for an empty mask: device scalars
+        nmask = 1 if wb is None else 2
+        t0 = _hbm_begin("ncc_masked_bwd")
+        lib.call("pulpo_ncc_masked_bwd", _ptr(true), _ptr(pred), _ptr(S), _ptr(wa), _ptr(wb), _ptr(T), _ptr(gs), 1.0, _ptr(gJ), B, D, H, W, ctx.win,
+                 _stream())
+        _hbm_end(t0, "ncc_masked_bwd", 4.0 * (20 + nmask) * N)
+        return gJ, None, None, None, None, None
+
+
+def ncc_loss_masked(pred, true, mask, mask2=None, win: int = 9, gamma: float = 0.05):
+    """-gamma V sum(m cc) / M with m = mask * mask2 and M = sum(m) (0 for an empty mask): NCC_loss with the per-voxel cost weighted by m,
+    the window statistics over all voxels.  Masks: (B,1,...) weights in [0,1], 1 = counted.  Gradient to pred only."""
+    if _is2d(pred):
+        if mask is not None and mask.dim() != 4 or mask2 is not None and mask2.dim() != 4:
+            raise ValueError(f"ncc_loss_masked: masks of a (B,1,H,W) image are (B,1,H,W), got {tuple(mask.shape)}")
+        return ncc_loss_masked(_lift(pred), _lift(true), _lift(mask), _lift(mask2), win, gamma)
+    wa, wb = _as_masks(pred, mask, mask2, "ncc_loss_masked")
+    return _NCCMasked.apply(pred, true, wa, wb, int(win), float(gamma))[0]
 
 
 class _KL(torch.autograd.Function):
@@ -2028,6 +2123,55 @@ def l2_loss(inp, target):
     if _is2d(inp):
         return l2_loss(_lift(inp), _lift(target))
     return _SqDiff.apply(inp, target)
+
+
+class _SqDiffMasked(torch.autograd.Function):
+    """(L2_masked or, with root, RMSE_masked; MaskFrac) - DESIGN.md section 3i"""
+
+    @staticmethod
+    def forward(ctx, a, b, wa, wb, root: bool):
+        _require_gpu(a, b, wa, wb)
+        a, b = planar(a), planar(b)
+        B, C = a.shape[0], a.shape[1]
+        V = a.numel() // (B * C)
+        nblk = lib.query("pulpo_metric_blocks", a.numel())
+        part = torch.empty(2 * nblk, device=a.device, dtype=torch.float32)
+        lib.call("pulpo_sqdiff_masked_fwd", _ptr(a), _ptr(b), _ptr(wa), _ptr(wb), _ptr(part), B, C, V, _stream())
+        fin = _masked_finish(part, nblk, (1.0 if root else float(V)) / C, root, float(B * V))
+        ctx.save_for_backward(a, b, wa, wb, fin)
+        return fin                                           # (value, d value / d sum, MaskFrac, M)
+
+    @staticmethod
+    def backward(ctx, gfin):
+        a, b, wa, wb, fin = ctx.saved_tensors
+        B, C = a.shape[0], a.shape[1]
+        ga = torch.empty_like(a)
+        gs = (gfin[0] * fin[1]).contiguous()
+        lib.call("pulpo_sqdiff_masked_bwd", _ptr(a), _ptr(b), _ptr(wa), _ptr(wb), _ptr(gs), 1.0, _ptr(ga), B, C, a.numel() // (B * C), _stream())
+        return ga, None, None, None, None
+
+
+def _sqdiff_masked(inp, target, mask, mask2, root: bool, name: str):
+    if _is2d(inp):
+        if mask is not None and mask.dim() != 4 or mask2 is not None and mask2.dim() != 4:
+            raise ValueError(f"{name}: masks of a (B,C,H,W) image are (B,1,H,W), got {tuple(mask.shape)}")
+        return _sqdiff_masked(_lift(inp), _lift(target), _lift(mask), _lift(mask2), root, name)
+    if inp.shape != target.shape:
+        raise ValueError(f"{name}: input {tuple(inp.shape)} and target {tuple(target.shape)} differ in shape")
+    wa, wb = _as_masks(inp, mask, mask2, name)
+    return _SqDiffMasked.apply(inp, target, wa, wb, root)
+
+
+def l2_loss_masked(inp, target, mask, mask2=None):
+    """V sum(m (inp - target)^2) / (C M), m = mask * mask2 broadcast over the channels, M = sum(m) (0 for an empty mask): L2_loss with
+    the per-voxel cost weighted by m.  Gradient to inp only."""
+    return _sqdiff_masked(inp, target, mask, mask2, False, "l2_loss_masked")[0]
+
+
+def rmse_masked(inp, target, mask, mask2=None):
+    """(sqrt(L2_masked / V), MaskFrac = M / (B V)) as 0-d device tensors"""
+    fin = _sqdiff_masked(inp, target, mask, mask2, True, "rmse_masked")
+    return fin[0], fin[2].detach()
 
 
 class _Dice(torch.autograd.Function):
