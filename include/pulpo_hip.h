@@ -34,7 +34,7 @@ extern "C" {
  * PULPO_ABI_VERSION is bumped whenever a prototype below changes its argument list or a buffer contract, or an entry point is removed
  * (history: INTEGRATION.md "ABI history").  pulpo_abi_version() returns the value the library was built with: a client compares it with
  * the header it was compiled against before the first call (pulpo_amd/_lib.py does). */
-#define PULPO_ABI_VERSION 7
+#define PULPO_ABI_VERSION 8
 int pulpo_abi_version(void);
 const char* pulpo_last_error(void);
 
@@ -280,8 +280,9 @@ int pulpo_dice_fwd(const float* inp, const float* tgt, int nplanes, int64_t V, f
                    void* stream);
 int pulpo_dice_bwd(const float* inp, const float* tgt, const double* numden, const float* gscale, int nplanes, int64_t V, float dice_factor,
                    float* ginp, void* stream);
-int pulpo_jacdet_fwd(const float* df, float* out, float* partial /*nullable*/, int B, int D, int H, int W, int normalize, void* stream);
-int pulpo_jdetstd_finalize(const float* partial, int64_t n, float lamb, double* stat, float* loss, void* stream);
+/* jacdet partial (since ABI 8): 2 * pulpo_metric_blocks(B*D*H*W) DOUBLES, each block's sums of J - 1 and (J - 1)^2 (centred: J sits near 1) */
+int pulpo_jacdet_fwd(const float* df, float* out, double* partial /*nullable*/, int B, int D, int H, int W, int normalize, void* stream);
+int pulpo_jdetstd_finalize(const double* partial, int64_t n, float lamb, double* stat, float* loss, void* stream);
 /* KL_nondiagonal.loss (src/losses.py:8-44, 3-D): mu, sigma planar (B,3,D,H,W), nplanes = B*3 */
 int pulpo_kl_nondiag_fwd(const float* mu, const float* sigma, int64_t nplanes, int D, int H, int W, float prior_lambda, float* partial, float* loss,
                          void* stream);
@@ -380,8 +381,9 @@ int pulpo_map_ncc_blocks(int64_t n);
 int pulpo_map_ncc(const float* a, const float* b, int64_t n, double* partial, double* out, void* stream);
 
 /* --------------------------------------------------------------------------------------------------- optimizer
- * torch.optim.Adam(lr) defaults (src/models.py:398-400) over a flat fp32 arena; gscale pre-multiplies the gradient. */
-int pulpo_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step, float gscale,
+ * torch.optim.Adam(lr) defaults (src/models.py:398-400) over a flat fp32 arena; gscale pre-multiplies the gradient.  beta1, beta2 are doubles
+ * (since ABI 8): 1 - beta and 1 - beta^step are formed in double. */
+int pulpo_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps, int step, float gscale,
                     void* stream);
 
 /* ------------------------------------------------------------------------- Winograd F(2x2x2,3x3x3): the deep layers (since ABI 3)

@@ -1,6 +1,6 @@
 // Alternative reconstruction losses / regulariser / evaluation metrics of PULPo:
 //   L2_loss (src/losses.py:79-83), Soft_dice_loss (:137-145), jacobian_det (:172-199), JDetStd (:202-204).
-// All are HBM-bound streaming kernels with two-stage deterministic reductions (fp32 block partials -> double).
+// All are HBM-bound streaming kernels with two-stage deterministic reductions (fp32 block partials -> double; JDetStd: centred, double throughout).
 #include "common.h"
 
 namespace {
@@ -174,31 +174,42 @@ __device__ __forceinline__ float jac_at(const float* __restrict__ df, const JacG
            Jl[0][2] * (Jl[1][0] * Jl[2][1] - Jl[2][0] * Jl[1][1]);
 }
 
-__global__ __launch_bounds__(256) void jacdet_fwd_kernel(const float* __restrict__ df, JacGeom g, float* __restrict__ out, float* __restrict__ partial) {
-    __shared__ float sh[4];
+// The determinant map, and for JDetStd the block's sums of J - 1 and (J - 1)^2.  J sits near 1 on the near-identity fields a registration
+// produces: uncentred fp32 sums cancel in q - s mean (the std came out as noise or 0 below |J - 1| ~ 1e-2), so the sums are centred at 1 and
+// kept in double per thread, per block and across blocks, as field_quality_kernel keeps them.  Fixed order, no atomics: deterministic.
+__global__ __launch_bounds__(256) void jacdet_fwd_kernel(const float* __restrict__ df, JacGeom g, float* __restrict__ out, double* __restrict__ partial) {
+    __shared__ double shd[8];
     const long V = (long)g.D * g.H * g.W, total = (long)g.B * V;
-    float s = 0.f, q = 0.f;
+    double s = 0.0, q = 0.0;
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const long b = e / V, v = e - b * V;
         const int x = (int)(v % g.W), y = (int)((v / g.W) % g.H), z = (int)(v / ((long)g.W * g.H));
         const float d = g.D == 1 ? jac2_at(df, g, b, y, x, nullptr) : jac_at(df, g, b, z, y, x, nullptr);
         out[e] = d;
-        s += d; q += d * d;
+        const double c = (double)d - 1.0;
+        s += c; q += c * c;
     }
     if (partial != nullptr) {
-        const float ts = block_sum_256(s, sh), tq = block_sum_256(q, sh);
-        if (threadIdx.x == 0) { partial[2 * blockIdx.x] = ts; partial[2 * blockIdx.x + 1] = tq; }
+        s = pulpo::wave_sum_d(s);
+        q = pulpo::wave_sum_d(q);
+        if ((threadIdx.x & 63) == 0) { shd[2 * (threadIdx.x >> 6)] = s; shd[2 * (threadIdx.x >> 6) + 1] = q; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            partial[2 * blockIdx.x] = (shd[0] + shd[2]) + (shd[4] + shd[6]);
+            partial[2 * blockIdx.x + 1] = (shd[1] + shd[3]) + (shd[5] + shd[7]);
+        }
     }
 }
 
-// stat[0] = mean, stat[1] = unbiased std (doubles); loss = lamb * std
-__global__ void jdetstd_finalize_kernel(const float* __restrict__ partial, int nblk, double n, float lamb, double* __restrict__ stat, float* __restrict__ loss) {
+// partial: the blocks' sums of J - 1 and (J - 1)^2.  stat[0] = mean of J, stat[1] = unbiased std (doubles); loss = lamb * std
+__global__ void jdetstd_finalize_kernel(const double* __restrict__ partial, int nblk, double n, float lamb, double* __restrict__ stat,
+                                        float* __restrict__ loss) {
     double s = 0, q = 0;
     for (int k = 0; k < nblk; ++k) { s += partial[2 * k]; q += partial[2 * k + 1]; }
-    const double mean = s / n;
-    double var = (q - s * mean) / (n - 1.0);
+    const double cm = s / n;                              // mean of J - 1
+    double var = (q - s * cm) / (n - 1.0);
     if (var < 0) var = 0;
-    stat[0] = mean; stat[1] = sqrt(var);
+    stat[0] = 1.0 + cm; stat[1] = sqrt(var);
     loss[0] = (float)(lamb * sqrt(var));
 }
 
@@ -418,15 +429,16 @@ PULPO_API int pulpo_dice_bwd(const float* inp, const float* tgt, const double* n
     return pulpo::check_launch("dice_bwd");
 }
 
-// jacobian_det: df planar (B,3,D,H,W) -> out (B,D,H,W).  partial (nullable): 2*pulpo_metric_blocks(B*D*H*W) floats of (sum, sum sq) for JDetStd
-PULPO_API int pulpo_jacdet_fwd(const float* df, float* out, float* partial, int B, int D, int H, int W, int normalize, void* stream) {
+// jacobian_det: df planar (B,3,D,H,W) -> out (B,D,H,W).  partial (nullable): 2*pulpo_metric_blocks(B*D*H*W) DOUBLES per block, the sums of
+// J - 1 and (J - 1)^2, for JDetStd
+PULPO_API int pulpo_jacdet_fwd(const float* df, float* out, double* partial, int B, int D, int H, int W, int normalize, void* stream) {
     PULPO_REQUIRE(df && out && B > 0 && D > 0 && H > 0 && W > 0, "jacdet_fwd: bad arguments");
     const long n = (long)B * D * H * W;
     hipLaunchKernelGGL(jacdet_fwd_kernel, dim3(pulpo_metric_blocks(n)), dim3(256), 0, (hipStream_t)stream, df, make_geom(B, D, H, W, normalize), out, partial);
     return pulpo::check_launch("jacdet_fwd");
 }
 // JDetStd = lamb * std(jacobian_det): stat = (mean, std) doubles kept for backward
-PULPO_API int pulpo_jdetstd_finalize(const float* partial, int64_t n, float lamb, double* stat, float* loss, void* stream) {
+PULPO_API int pulpo_jdetstd_finalize(const double* partial, int64_t n, float lamb, double* stat, float* loss, void* stream) {
     PULPO_REQUIRE(partial && stat && loss && n > 1, "jdetstd_finalize: bad arguments");
     hipLaunchKernelGGL(jdetstd_finalize_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, partial, pulpo_metric_blocks(n), (double)n, lamb, stat, loss);
     return pulpo::check_launch("jdetstd_finalize");

@@ -2227,7 +2227,7 @@ class _JDetStd(torch.autograd.Function):
         B, C, D, H, W = df.shape
         n = B * D * H * W
         jd = torch.empty((B, D, H, W), device=df.device, dtype=torch.float32)
-        part = torch.empty(2 * lib.query("pulpo_metric_blocks", n), device=df.device, dtype=torch.float32)
+        part = torch.empty(2 * lib.query("pulpo_metric_blocks", n), device=df.device, dtype=torch.float64)     # block sums of J - 1, (J - 1)^2
         stat = torch.empty(2, device=df.device, dtype=torch.float64)
         loss = torch.empty((), device=df.device, dtype=torch.float32)
         lib.call("pulpo_jacdet_fwd", _ptr(df), _ptr(jd), _ptr(part), B, D, H, W, int(normalize), _stream())

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from metrics_ref import jacobian_det_2d
 from oracle import pulpo_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -61,21 +62,6 @@ def folded_field(B, grid, amplitude=3.0):
     nd = len(grid)
     c = (torch.rand(B, nd, *[max(2, s // 3) for s in grid], generator=torch.Generator().manual_seed(5)) * 2 - 1) * amplitude
     return F.interpolate(c, size=grid, mode="trilinear" if nd == 3 else "bilinear", align_corners=False)
-
-
-def jacobian_det_2d(df, normalize=True):
-    """the reference's 2-D determinant (src/losses.py:153-171) in the dtype of df, written like O.jacobian_det"""
-    _, _, H, W = df.shape
-    S = (H, W)
-    u = torch.stack([df[:, i] * 2 / S[i] for i in range(2)], dim=1) if normalize else df
-    uf = u.flip(1) * torch.tensor([(H - 2) / 2, (W - 2) / 2], dtype=df.dtype).view(1, 2, 1, 1)
-    J = [[None] * 2 for _ in range(2)]
-    for a in range(2):
-        idx = torch.arange(S[a])
-        g = 0.5 * (uf.index_select(2 + a, (idx + 1).clamp(max=S[a] - 1)) - uf.index_select(2 + a, (idx - 1).clamp(min=0)))
-        for c in range(2):
-            J[a][c] = g[:, c] + (1.0 if a == c else 0.0)
-    return J[0][0] * J[1][1] - J[1][0] * J[0][1]
 
 
 # (batch, grid, amplitude of the recipe).  Amplitude 3 meets both guards below in fp64 at every shape, normalised or not (checked on the
