@@ -252,6 +252,20 @@ int pulpo_ncc_masked_fwd(const float* I, const float* J, const float* wa, const 
 int pulpo_ncc_masked_bwd(const float* I, const float* J, const float* S, const float* wa, const float* wb /*nullable*/, float* T /*6N scratch*/,
                          const float* gscale, float coef, float* gJ, int B, int D, int H, int W, int win, void* stream);
 int pulpo_masked_finish(const float* partial, int nblk, double scale, int root, double count, float* out /*4*/, void* stream);
+/* MIND-SSC similarity term (no counterpart in the reference): the 12-channel self-similarity descriptor
+ *   f_k = exp(-(D_k - min_j D_j) / (mean_k (D_k - min_j D_j) + eps)),  D_k = clamped 3^3 box mean of the squared difference of the image at the
+ *   two offsets of channel k (offsets -z +z -y +y -x +x times the dilation d, replicate padding), and cost = 1/12 sum_k (f_k[pred] - f_k[true])^2.
+ * Images planar (B,1,D,H,W) fp32, every extent >= 2, d >= 1 (as far as the staged tile fits 64 KiB of LDS: d <= 7), eps > 0; N = B*D*H*W.
+ * mind_descriptor: out = (B,12,D,H,W) stored as 12 planes of N floats, out[k N + e].
+ * mind_fwd: partial = pulpo_mind_blocks(B,D,H,W,d) rows of one column (wa NULL: sum of cost; finish with pulpo_colsum(scale = 1/B)) or of two
+ *   columns (masks wa, wb nullable: sum of m cost, sum of m; finish with pulpo_masked_finish(scale = V)).
+ * mind_bwd: gpred = coef * gscale[0] * d(sum m cost)/d pred (gscale nullable = 1); scratch: 12 N floats.  No atomics: bit-identical run to run. */
+int pulpo_mind_blocks(int B, int D, int H, int W, int d);
+int pulpo_mind_descriptor(const float* I, float* out /*12N*/, int B, int D, int H, int W, int d, float eps, void* stream);
+int pulpo_mind_fwd(const float* y_true, const float* y_pred, const float* wa /*nullable*/, const float* wb /*nullable*/, float* partial, int B, int D,
+                   int H, int W, int d, float eps, void* stream);
+int pulpo_mind_bwd(const float* y_true, const float* y_pred, const float* wa /*nullable*/, const float* wb /*nullable*/, float* scratch /*12N*/,
+                   const float* gscale, float coef, float* gpred, int B, int D, int H, int W, int d, float eps, void* stream);
 int pulpo_kl_fwd(const float* mu, const float* sigma, const float* mu1 /*nullable: 0*/, const float* sigma1 /*nullable: 1*/, int64_t n,
                  float* partial, void* stream);
 int pulpo_kl_bwd(const float* mu, const float* sigma, const float* mu1, const float* sigma1, const float* gscale, float coef, float* gmu,

@@ -25,6 +25,8 @@ METRICS = ("RMSE", "JDetStd", "JDetLeq0", "Dice", "LM_MAE", "LM_Euclid")
 INVERSE_METRICS = ("InvCons", "InvConsMax", "LM_MAE_inv", "LM_Euclid_inv")
 # the rows level_scores adds when it is given cost-function masks
 MASK_METRICS = ("RMSE_masked", "MaskFrac")
+# the row level_scores adds with mind=True: the cross-contrast counterpart of RMSE, which means nothing between contrasts
+MIND_METRICS = ("MIND",)
 
 
 def _zero(ref: torch.Tensor) -> torch.Tensor:
@@ -35,7 +37,8 @@ def _zero(ref: torch.Tensor) -> torch.Tensor:
 def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Tensor], y: torch.Tensor, *, seg_x: Optional[torch.Tensor] = None,
                  seg_y: Optional[torch.Tensor] = None, lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
                  num_classes: Optional[int] = None, final_dfs_inv: Optional[Dict[int, torch.Tensor]] = None,
-                 mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None) -> Dict[str, Dict[int, torch.Tensor]]:
+                 mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
+                 mind_eps: float = 1e-5) -> Dict[str, Dict[int, torch.Tensor]]:
     """The level losses of evaluate.py:1433-1474 for one pair: {metric: {level: 0-d device tensor}}.
 
     outputs[l], final_dfs[l]: the warped image and the final field of level l (predict_deterministic + combine_dfs); y: the fixed image.
@@ -57,7 +60,10 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
     beside the rows above, which do not change, with m_l = warp_mask(final_dfs[l], mask_x) * (mask_y resized to the level), the level masks
     of the training step (PULPo.level_masks),
       RMSE_masked[l]   sqrt(sum(m_l (outputs[l] - target)^2) / (C sum(m_l))), 0 for an empty m_l      (ops.rmse_masked)
-      MaskFrac[l]      mean of m_l"""
+      MaskFrac[l]      mean of m_l
+    mind=True (3-D only; no counterpart in the reference) adds, beside the rows above, which do not change,
+      MIND[l]          mean over batch, voxels and the 12 channels of the squared difference of the MIND-SSC descriptors of outputs[l] and
+                       the target = mind_loss(outputs[l], target, mind_dilation, mind_eps) / num_pixels_l"""
     levels = sorted(outputs.keys())
     if sorted(final_dfs.keys()) != levels:
         raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs {sorted(final_dfs.keys())}")
@@ -84,6 +90,12 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
             wy = None if mask_y is None else (mask_y.float() if size == tuple(mask_y.shape[2:]) else ops.resize_trilinear(mask_y.float(), size))
             pair = (wx, wy) if wx is not None else (wy, None)
             res["RMSE_masked"][l], res["MaskFrac"][l] = ops.rmse_masked(outputs[l], target, pair[0], pair[1])
+    if mind:
+        res["MIND"] = {}
+        for l in levels:
+            size = tuple(outputs[l].shape[2:])
+            target = y if size == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
+            res["MIND"][l] = ops.mind_loss(outputs[l], target, mind_dilation, mind_eps) / float(np.prod(size))
     if seg_x is not None:
         lab_x, C = _as_labels(seg_x, num_classes, "level_scores")
         lab_y, _ = _as_labels(seg_y, C, "level_scores")
@@ -115,13 +127,14 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
 def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torch.Tensor] = None, seg_y: Optional[torch.Tensor] = None,
                 lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
                 num_classes: Optional[int] = None, inverse: bool = False, mask_x: Optional[torch.Tensor] = None,
-                mask_y: Optional[torch.Tensor] = None) -> Dict[str, Dict[int, torch.Tensor]]:
+                mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
+                mind_eps: float = 1e-5) -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
     unless the samplers are pinned (network_blocks.FixedNoiseSampler).  inverse=True also integrates the inverse fields
     (model.combine_dfs_bidirectional: one integration call per level for both directions) and adds the INVERSE_METRICS rows; mask_x / mask_y
-    add the MASK_METRICS rows."""
+    add the MASK_METRICS rows, mind=True the MIND_METRICS row."""
     outputs, individual_dfs = model.predict_deterministic(x, y)
     final_dfs_inv = None
     if inverse:
@@ -129,7 +142,7 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
     else:
         _, final_dfs = model.combine_dfs(individual_dfs)
     return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv,
-                        mask_x=mask_x, mask_y=mask_y)
+                        mask_x=mask_x, mask_y=mask_y, mind=mind, mind_dilation=mind_dilation, mind_eps=mind_eps)
 
 
 @torch.no_grad()

@@ -99,6 +99,19 @@ def NCC_loss_masked(y_pred: torch.Tensor, y_true: torch.Tensor, mask: torch.Tens
     return ops.ncc_loss_masked(y_pred, y_true, mask, mask2, win_size, gamma)
 
 
+def MIND_loss(y_pred: torch.Tensor, y_true: torch.Tensor, dilation: int = 2, eps: float = 1e-5) -> torch.Tensor:
+    """MIND-SSC similarity between two contrasts: sum over voxels, mean over the batch of the squared difference of the 12-channel
+    self-similarity descriptors (mean over the channels) - on L2_loss's scale.  3-D volumes only"""
+    return ops.mind_loss(y_pred, y_true, dilation, eps)
+
+
+def MIND_loss_masked(y_pred: torch.Tensor, y_true: torch.Tensor, mask: torch.Tensor, mask2: Optional[torch.Tensor] = None, dilation: int = 2,
+                     eps: float = 1e-5) -> torch.Tensor:
+    """MIND_loss with cost-function masking: V * sum(m cost) / sum(m), m = mask * mask2, 0 for an empty mask.  The descriptors are formed
+    from all voxels; the mask weights the per-voxel cost (DESIGN.md sections 3i, 3j)"""
+    return ops.mind_loss_masked(y_pred, y_true, mask, mask2, dilation, eps)
+
+
 def L2_reg(deformation_field: torch.Tensor, lamb=0) -> torch.Tensor:
     """lamb * H*W*D * mean of squared forward differences over the [1:,1:,1:] block"""
     if deformation_field.dim() not in (4, 5):
@@ -157,9 +170,11 @@ class HierarchicalKLLoss(nn.Module):
 class HierarchicalReconstructionLoss(nn.Module):
     """sum_l w_l * recon(y_hat_l, y resized to level l) / len(recon_loss)   (losses.py:279-325)"""
 
-    def __init__(self, recon_loss: List[str], weight_dict: Dict[int, float], similarity_pyramid: bool, ndims: int, window_size: Dict[int, float]) -> None:
+    def __init__(self, recon_loss: List[str], weight_dict: Dict[int, float], similarity_pyramid: bool, ndims: int, window_size: Dict[int, float],
+                 mind_dilation: int = 2, mind_eps: float = 1e-5) -> None:
         super().__init__()
         self.recon_loss = recon_loss
+        self.mind_dilation, self.mind_eps = mind_dilation, mind_eps
         self.weight_dict = _apply_pyramid(weight_dict, similarity_pyramid)
         self.window_size = window_size
         self.ndims = ndims
@@ -174,11 +189,17 @@ class HierarchicalReconstructionLoss(nn.Module):
     def _mse(y_hat_l, y_target, pair):
         return L2_loss(y_hat_l, y_target) if pair is None else L2_loss_masked(y_hat_l, y_target, pair[0], pair[1])
 
+    def _mind(self, y_hat_l, y_target, pair):
+        """no gamma: the term is on MSE's scale already"""
+        if pair is None:
+            return MIND_loss(y_hat_l, y_target, self.mind_dilation, self.mind_eps)
+        return MIND_loss_masked(y_hat_l, y_target, pair[0], pair[1], self.mind_dilation, self.mind_eps)
+
     def forward(self, y_hat, y, y_hat_seg=None, seg_y=None, gamma: float = 0.05, dice_factor: int = 1,
                 masks: Optional[Dict[int, Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]] = None):
         """masks (not in the reference): {level: (mask_a, mask_b)}, weight volumes at the level's size, either of a pair may be None; a level
-        with a pair uses the masked NCC / MSE term (cost weighted by mask_a * mask_b), the Dice term is unchanged"""
-        single = len(self.recon_loss) == 1 and self.recon_loss[0] in ("mse", "ncc", "dice")
+        with a pair uses the masked NCC / MSE / MIND term (cost weighted by mask_a * mask_b), the Dice term is unchanged"""
+        single = len(self.recon_loss) == 1 and self.recon_loss[0] in ("mse", "ncc", "dice", "mind")
         loss = 0.0
         all_levels, terms = {}, {}
         for l, w in self.weight_dict.items():
@@ -191,13 +212,18 @@ class HierarchicalReconstructionLoss(nn.Module):
                 pair = None if not pair else (pair[0], pair[1] if len(pair) > 1 else None)
             if single and self.recon_loss[0] != "dice":
                 # one term per level (the default, ["ncc"]): weighting and summation of all levels in one launch; x / 1 is x
-                terms[l] = self._ncc(l, y_hat[l], y_target, pair, gamma) if self.recon_loss[0] == "ncc" else self._mse(y_hat[l], y_target, pair)
+                if self.recon_loss[0] == "mind":
+                    terms[l] = self._mind(y_hat[l], y_target, pair)
+                else:
+                    terms[l] = self._ncc(l, y_hat[l], y_target, pair, gamma) if self.recon_loss[0] == "ncc" else self._mse(y_hat[l], y_target, pair)
                 continue
             term = 0.0
             if "mse" in self.recon_loss:
                 term = term + w * self._mse(y_hat[l], y_target, pair)
             if "ncc" in self.recon_loss:
                 term = term + w * self._ncc(l, y_hat[l], y_target, pair, gamma)
+            if "mind" in self.recon_loss:
+                term = term + w * self._mind(y_hat[l], y_target, pair)
             if "dice" in self.recon_loss:
                 seg_size = y_hat_seg[l].shape[2:]
                 seg_target = seg_y if tuple(seg_size) == tuple(seg_y.shape[2:]) else ops.resize_trilinear(seg_y, seg_size)

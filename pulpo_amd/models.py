@@ -54,6 +54,8 @@ class PULPo(ABC, LightningModule):
         mask: bool = False,
         nondiagonal: bool = False,
         cp_depth: int = 3,
+        mind_dilation: int = 2,
+        mind_eps: float = 1e-5,
     ) -> None:
         super().__init__()
         self.validation_counter = 0
@@ -118,7 +120,7 @@ class PULPo(ABC, LightningModule):
                                                        level_sizes=self.level_sizes)
         self.hierarchical_recon_loss = HierarchicalReconstructionLoss(recon_loss=recon_loss, weight_dict=rec_w,
                                                                       similarity_pyramid=similarity_pyramid, window_size=window_size,
-                                                                      ndims=self.ndims)
+                                                                      ndims=self.ndims, mind_dilation=mind_dilation, mind_eps=mind_eps)
         self.hierarchical_regularization = HierarchicalRegularization(regularizer=regularization_loss, weight_dict=reg_w,
                                                                       similarity_pyramid=similarity_pyramid)
         self._pending_nan_probe = None          # (pinned flag, event) of an earlier step's NaN test

@@ -1974,6 +1974,92 @@ def ncc_loss_masked(pred, true, mask, mask2=None, win: int = 9, gamma: float = 0
     return _NCCMasked.apply(pred, true, wa, wb, int(win), float(gamma))[0]
 
 
+# ---- MIND-SSC: a similarity term between two contrasts.  f_k = exp(-(D_k - min D) / (mean(D - min D) + eps)) over
+# the twelve self-similarity-context channels, cost = mean_k (f_k[pred] - f_k[true])^2; voxel-sum, batch-mean like L2_loss.
+def _mind_args(name: str, *imgs, dilation, eps):
+    for t in imgs:
+        if t.dim() == 4:
+            raise NotImplementedError(f"{name}: 3-D volumes (B,1,D,H,W) only; the 2-D descriptor (four channels) is not built")
+        if t.dim() != 5 or t.shape[1] != 1:
+            raise PulpoHipError(f"{name}: single-channel volumes (B,1,D,H,W) expected, got {tuple(t.shape)}")
+    if len(imgs) == 2 and imgs[0].shape != imgs[1].shape:
+        raise ValueError(f"{name}: pred {tuple(imgs[0].shape)} and true {tuple(imgs[1].shape)} differ in shape")
+    return int(dilation), float(eps)
+
+
+def _mind_bytes(pred, nmask: int, backward: bool) -> float:
+    """algorithmic HBM bytes: forward 2 images (+ masks) in; backward 2 images (+ masks) in, 12N out, 12N in, the image once more, N out"""
+    N = pred.numel()
+    return 4.0 * N * ((2 + nmask + 12 + 12 + 1 + 1) if backward else (2 + nmask))
+
+
+class _Mind(torch.autograd.Function):
+    """unmasked (wa is None): the loss scalar; masked: the four scalars of pulpo_masked_finish"""
+
+    @staticmethod
+    def forward(ctx, pred, true, wa, wb, dilation: int, eps: float):
+        _require_gpu(pred, true, wa, wb)
+        pred, true = planar(pred), planar(true)
+        B, _, D, H, W = pred.shape
+        nblk = lib.query("pulpo_mind_blocks", B, D, H, W, dilation)
+        ncol = 1 if wa is None else 2
+        part = torch.empty(max(nblk, 1) * ncol, device=pred.device, dtype=torch.float32)
+        nmask = (wa is not None) + (wb is not None)
+        t0 = _hbm_begin("mind_fwd")
+        lib.call("pulpo_mind_fwd", _ptr(true), _ptr(pred), _ptr(wa), _ptr(wb), _ptr(part), B, D, H, W, dilation, eps, _stream())
+        _hbm_end(t0, "mind_fwd", _mind_bytes(pred, nmask, False))
+        ctx.dilation, ctx.eps, ctx.masked = dilation, eps, wa is not None
+        if wa is None:
+            ctx.save_for_backward(pred, true)
+            return _colsum(part, nblk, 1, 1.0 / B).reshape(())
+        fin = _masked_finish(part, nblk, float(D * H * W), False, float(B * D * H * W))
+        ctx.save_for_backward(pred, true, wa, wb, fin)
+        return fin
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.masked:
+            pred, true, wa, wb, fin = ctx.saved_tensors
+            gs, coef = (g[0] * fin[1]).contiguous(), 1.0        # upstream * (V / M), 0 for an empty mask: device scalars
+        else:
+            (pred, true), wa, wb = ctx.saved_tensors, None, None
+            gs, coef = g.contiguous(), 1.0 / pred.shape[0]
+        B, _, D, H, W = pred.shape
+        scratch = torch.empty(12 * pred.numel(), device=pred.device, dtype=torch.float32)
+        gpred = torch.empty_like(pred)
+        nmask = (wa is not None) + (wb is not None)
+        t0 = _hbm_begin("mind_bwd")
+        lib.call("pulpo_mind_bwd", _ptr(true), _ptr(pred), _ptr(wa), _ptr(wb), _ptr(scratch), _ptr(gs), coef, _ptr(gpred), B, D, H, W, ctx.dilation,
+                 ctx.eps, _stream())
+        _hbm_end(t0, "mind_bwd", _mind_bytes(pred, nmask, True))
+        return gpred, None, None, None, None, None
+
+
+def mind_descriptor(img, dilation: int = 2, eps: float = 1e-5):
+    """(B,1,D,H,W) -> (B,12,D,H,W): the MIND-SSC descriptor, in (0,1] with maximum 1 over the channels.  No gradient."""
+    dilation, eps = _mind_args("mind_descriptor", img, dilation=dilation, eps=eps)
+    _require_gpu(img)
+    img = planar(img.detach())
+    B, _, D, H, W = img.shape
+    out = torch.empty((12, B, D, H, W), device=img.device, dtype=torch.float32)
+    lib.call("pulpo_mind_descriptor", _ptr(img), _ptr(out), B, D, H, W, dilation, eps, _stream())
+    return out.transpose(0, 1)
+
+
+def mind_loss(pred, true, dilation: int = 2, eps: float = 1e-5):
+    """sum over voxels, mean over the batch of the squared descriptor difference (mean over the 12 channels).  Gradient to pred only."""
+    dilation, eps = _mind_args("mind_loss", pred, true, dilation=dilation, eps=eps)
+    return _Mind.apply(pred, true.detach(), None, None, dilation, eps)
+
+
+def mind_loss_masked(pred, true, mask, mask2=None, dilation: int = 2, eps: float = 1e-5):
+    """V sum(m cost) / M with m = mask * mask2 and M = sum(m) (0 for an empty mask): mind_loss with the per-voxel cost weighted by m; the
+    descriptors are formed from all voxels.  Gradient to pred only."""
+    dilation, eps = _mind_args("mind_loss_masked", pred, true, dilation=dilation, eps=eps)
+    wa, wb = _as_masks(pred, mask, mask2, "mind_loss_masked")
+    return _Mind.apply(pred, true.detach(), wa, wb, dilation, eps)[0]
+
+
 class _KL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, sigma, mu1, sigma1):

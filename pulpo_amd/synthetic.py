@@ -3,7 +3,8 @@
 uniform_pair : x, y ~ U[0,1)                                  (BASELINE configs 1-3)
 oasis_like_pair : a smooth "anatomy" inside an ellipsoidal head mask with zero background, and a moving image that is the
                   fixed one deformed by a smooth random displacement of a few voxels (BASELINE configs 4-5, "OASIS-style")
-Both are generated on the CPU generator (reproducible across devices) and finished on the GPU with the HIP resampling / warp
+multimodal_pair : oasis_like_pair with the fixed image in another "contrast" (a non-monotonic intensity map): the pair for the MIND term
+All are generated on the CPU generator (reproducible across devices) and finished on the GPU with the HIP resampling / warp
 operators of the hot path."""
 from __future__ import annotations
 
@@ -38,3 +39,11 @@ def oasis_like_pair(size: Sequence[int], batch: int, seed: int, device, max_disp
     # displacement in voxels -> the SpatialTransformer's convention: the field is added to the voxel grid (network_blocks.py:101-121)
     x = ops.warp3d(field.contiguous(), y).clamp_(0.0, 1.0).contiguous()
     return x, y
+
+
+def multimodal_pair(size: Sequence[int], batch: int, seed: int, device, max_disp: float = 3.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """oasis_like_pair with the fixed image passed through v -> 4 v (1 - v) inside the head (0 outside, where v is 0): dark and bright tissue
+    of the moving image are both dark in the fixed one, mid-grey is bright - no linear relation between the two intensities, the case
+    NCC and MSE cannot handle and the MIND term is for."""
+    x, y = oasis_like_pair(size, batch, seed, device, max_disp)
+    return x, (4.0 * y * (1.0 - y)).contiguous()
