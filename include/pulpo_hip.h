@@ -399,6 +399,13 @@ int pulpo_map_ncc(const float* a, const float* b, int64_t n, double* partial, do
  * (since ABI 8): 1 - beta and 1 - beta^step are formed in double. */
 int pulpo_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps, int step, float gscale,
                     void* stream);
+/* Adam over a flat arena of velocity fields with a Gaussian anchor (instance-specific refinement; added without a
+ * version bump).  With a = prec ? prec[e] : 1 and d = p[e] - mean[e], the gradient used is g[e] + a d and the blocks' partials receive
+ * 0.5 a d^2 (the anchor's value before the update); then pulpo_adam_step's update.  mean NULL: plain Adam, bit-identical to pulpo_adam_step
+ * with gscale = 1; prec needs mean.  Every non-null array 16-byte aligned.  partial (nullable): pulpo_loss_blocks(n) floats, all written when
+ * mean is given; finish with pulpo_colsum.  One launch, no float atomics. */
+int pulpo_anchored_adam_step(float* p, const float* g, float* m, float* v, const float* mean, const float* prec, int64_t n, float lr, double beta1,
+                             double beta2, float eps, int step, float* partial, void* stream);
 
 /* ------------------------------------------------------------------------- Winograd F(2x2x2,3x3x3): the deep layers (since ABI 3)
  * The same convolution (src/network_blocks.py:23, forward and data gradient) with minimal filtering along z, y AND x: 64 products per 2x2x2

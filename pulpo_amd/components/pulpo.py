@@ -223,9 +223,10 @@ class Autoencoder(nn.Module):
         fmt = torch.channels_last_3d if srcs[0].dim() == 5 else torch.channels_last
         return torch.cat([ops.resize_trilinear(s, size) for s in srcs], dim=1).contiguous(memory_format=fmt)
 
-    def forward(self, x: torch.Tensor, down_activations, deterministic: bool = False):
+    def level_images(self, x: torch.Tensor) -> Dict[int, torch.Tensor]:
+        """the moving image on every latent level (pulpo.py:171-179): level 0 keeps the full-resolution image, the levels above get the pooled
+        one; x everywhere under df_resolution "full_res".  (Also what pulpo_amd.refine warps.)"""
         L, o = self.latent_levels, self.lk_offset
-        # moving image on every latent level (pulpo.py:171-179): level 0 keeps the full-resolution image
         if self.df_resolution == "full_res":
             level_x = {l: x for l in range(L)}
         else:
@@ -235,6 +236,11 @@ class Autoencoder(nn.Module):
             for l in range(1, L):
                 level_x[l] = ops.avg_pool2(level_x[l - 1])
             level_x[0] = x
+        return level_x
+
+    def forward(self, x: torch.Tensor, down_activations, deterministic: bool = False):
+        L, o = self.latent_levels, self.lk_offset
+        level_x = self.level_images(x)
 
         names = ("mus", "sigmas", "samples", "velocity_fields", "individual_dfs", "combined_dfs", "final_dfs", "transformed")
         store: Dict[str, Dict[int, torch.Tensor]] = {n: {} for n in names}

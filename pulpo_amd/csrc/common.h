@@ -34,6 +34,18 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// sum over a workgroup of 256 in a fixed order (wave shuffles, then four adds; sh: 4 floats of LDS); valid in thread 0.  Every thread of the
+// block must call it.  (losses.hip, metrics.hip and mind.hip keep file-local copies of the same function.)
+__device__ __forceinline__ float block_sum_256(float v, float* sh) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = 0.f;
+    if (threadIdx.x == 0) t = sh[0] + sh[1] + sh[2] + sh[3];
+    __syncthreads();
+    return t;
+}
+
 // Bijective XCD-aware remap of a 1-D block id: blocks b and b+8 share an XCD (observed round-robin dispatch), so give
 // every XCD a contiguous run of logical ids -> neighbouring tiles (which share halos / weight panels) hit the same L2.
 // Speed only, never correctness (cdna_hip_programming.md T1).

@@ -128,19 +128,27 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
                 lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
                 num_classes: Optional[int] = None, inverse: bool = False, mask_x: Optional[torch.Tensor] = None,
                 mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
-                mind_eps: float = 1e-5) -> Dict[str, Dict[int, torch.Tensor]]:
+                mind_eps: float = 1e-5, refine: Optional[Dict[str, object]] = None) -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
     unless the samplers are pinned (network_blocks.FixedNoiseSampler).  inverse=True also integrates the inverse fields
     (model.combine_dfs_bidirectional: one integration call per level for both directions) and adds the INVERSE_METRICS rows; mask_x / mask_y
-    add the MASK_METRICS rows, mind=True the MIND_METRICS row."""
-    outputs, individual_dfs = model.predict_deterministic(x, y)
+    add the MASK_METRICS rows, mind=True the MIND_METRICS row.  refine (a dict of pulpo_amd.refine.refine's keyword arguments, {} for its
+    defaults; no counterpart in the reference): the same rows for the fields of model.refine(x, y, **refine) instead of the prediction's
+    (DESIGN.md section 3k); the masks given here score, they reach the refinement only through the dict."""
     final_dfs_inv = None
-    if inverse:
-        _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
+    if refine is not None:
+        res = model.refine(x, y, **refine)
+        outputs, individual_dfs, final_dfs = res["outputs"], res["individual_dfs"], res["final_dfs"]
+        if inverse:
+            _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
     else:
-        _, final_dfs = model.combine_dfs(individual_dfs)
+        outputs, individual_dfs = model.predict_deterministic(x, y)
+        if inverse:
+            _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
+        else:
+            _, final_dfs = model.combine_dfs(individual_dfs)
     return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv,
                         mask_x=mask_x, mask_y=mask_y, mind=mind, mind_dilation=mind_dilation, mind_eps=mind_eps)
 

@@ -127,12 +127,12 @@ class PULPo(ABC, LightningModule):
 
     # ------------------------------------------------------------------------------------------------ steps
     @torch.no_grad()
-    def level_masks(self, final_dfs, mask_x=None, mask_y=None):
+    def level_masks(self, final_dfs, mask_x=None, mask_y=None, force: bool = False):
         """{level: (mask_x warped by the level's field - the warp y_hat[l] gets, in the constant-preserving form of ops.warp_mask -, mask_y
-        resized to the level as y is)} for cost-function masking; None unless the model was built with mask=True and at least one mask is
-        non-empty"""
+        resized to the level as y is)} for cost-function masking; None unless the model was built with mask=True (the flag governs training
+        batches; `force` overrides it: pulpo_amd.refine masks whenever it is given masks) and at least one mask is non-empty"""
         has = lambda m: m is not None and m.numel() > 0
-        if not self.mask or not (has(mask_x) or has(mask_y)):
+        if not (self.mask or force) or not (has(mask_x) or has(mask_y)):
             return None
         mx = mask_x.float() if has(mask_x) else None
         my = mask_y.float() if has(mask_y) else None
@@ -283,6 +283,11 @@ class PULPo(ABC, LightningModule):
             outputs = {k: self.autoencoder.decoders[k].spatial_transform(final[k], x) for k in final}          # as predict
         outputs_inv = {k: self.autoencoder.decoders[k].spatial_transform(final_inv[k], y) for k in final_inv}
         return {"outputs": outputs, "individual_dfs": individual_dfs, "final_dfs": final, "final_dfs_inv": final_inv, "outputs_inv": outputs_inv}
+
+    def refine(self, x: torch.Tensor, y: torch.Tensor, **kw):
+        """instance-specific optimisation of this pair's level fields from the model's prediction: pulpo_amd.refine.refine(self, x, y, **kw)"""
+        from .refine import refine
+        return refine(self, x, y, **kw)
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:  # type: ignore[override]
         return self.autoencoder(x, self.downpath(x, y, _needed=self._needed_levels))[7][0]

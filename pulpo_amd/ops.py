@@ -2423,6 +2423,32 @@ def adam_step(p, g, m, v, lr: float, step: int, beta1=0.9, beta2=0.999, eps=1e-8
     refresh_weight_packs()                       # the kernel rewrote parameters through raw pointers: the cached packs follow, in one launch
 
 
+def anchored_adam_step(p, g, m, v, lr: float, step: int, mean=None, prec=None, loss_out=None, beta1=0.9, beta2=0.999, eps=1e-8):
+    """Adam over a flat arena of velocity fields (pulpo_amd.refine) in one launch.  With `mean` the gradient used is
+    g + a (p - mean), a = prec (per element) or 1, and `loss_out` (a 1-element fp32 tensor, optional) receives 0.5 sum a (p - mean)^2 at the
+    iterate before the update; mean=None is adam_step's arithmetic bit for bit.  The arena holds no network parameter: no weight pack is
+    refreshed.  Every tensor flat, contiguous and 16-byte aligned (the library checks)."""
+    _require_gpu(p, g, m, v, mean, prec, loss_out)
+    if prec is not None and mean is None:
+        raise ValueError("anchored_adam_step: prec needs mean")
+    n = p.numel()
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v), ("mean", mean), ("prec", prec)):
+        if t is not None and (t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"anchored_adam_step: {name} must be contiguous with {n} elements")
+    part = None
+    if mean is not None and loss_out is not None:
+        if loss_out.numel() != 1:
+            raise ValueError("anchored_adam_step: loss_out is one fp32 element")
+        nblk = lib.query("pulpo_loss_blocks", n)
+        part = torch.empty(nblk, device=p.device, dtype=torch.float32)
+    t0 = _hbm_begin("anchored_adam_step")
+    lib.call("pulpo_anchored_adam_step", _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(mean), _ptr(prec), n, lr, beta1, beta2, eps, int(step), _ptr(part),
+             _stream())
+    _hbm_end(t0, "anchored_adam_step", (28.0 + 4.0 * (mean is not None) + 4.0 * (prec is not None)) * n)       # read p, g, m, v (mean, prec); write p, m, v
+    if part is not None:
+        lib.call("pulpo_colsum", _ptr(part), nblk, 1, _ptr(loss_out), 1.0, 0, _stream())
+
+
 # ------------------------------------------------------------------------------------------------ evaluation scalars (evaluate.py)
 def rmse(inp, target):
     """sqrt(MSELoss(inp, target)) as a 0-d device tensor (evaluate.py:315-319)"""
