@@ -8,9 +8,9 @@ wider buffer; 1- and 3-channel images / fields are plain contiguous (N,C,D,H,W) 
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
-import threading
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -256,6 +256,14 @@ def set_deterministic(on: bool = True) -> None:
     DETERMINISTIC = bool(on)
 
 
+# The fused BatchNorm-backward passes of a ConvUnit, each with the separate pass it replaces - which stays, for the shapes the fused pass does not
+# take, and which False selects everywhere (the test suite's seam: fused and separate passes must agree).
+BN_REDUCE_IN_DGRAD = True        # False: the first pass (per-tile sums) as a kernel of its own, not in the consumer's data-gradient / pooling backward
+FUSE_INPUT_WGRAD = True          # False: the input layer's second pass writes dy for the plain weight gradient instead of running inside it
+POOLED_BN_BACKWARD = True        # False: the gradient of a pooled ConvUnit output is written as a tensor, then the plain passes
+FUSE_HEAD_BN = True              # False: a head reads the last ConvUnit's activation (separate BatchNorm and head passes) instead of its pre-norm tensor
+
+
 def _use_bf16(K: int) -> bool:
     return CONV_PRECISION == "bf16" and K > 4
 
@@ -411,7 +419,7 @@ def _conv_raw(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], o
         # operand and / or result in the channel-blocked layout: the F(2x2x2,3x3x3) kernel's *_kb entry (the callers have checked the kernel family)
         xt, xb_, xp_, xkb, xblk = _opnd(x)
         ot, ob_, op_, okb, oblk = _opnd(out)
-        if algo != "wino3" or (not oblk and (oc != 1 or op % 4 or ob % 4 or out.data_ptr() % 16)) or (not xblk and grid_strides(x)[2] != 1):
+        if algo != "wino3" or (not oblk and not _vec4(out)) or (not xblk and grid_strides(x)[2] != 1):
             raise PulpoHipError("conv3d on channel-blocked tensors: F(2x2x2,3x3x3) kernel, channels-last or blocked fp32 operands only")
         t0 = _trace_begin()
         lib.call("pulpo_conv3d_k3_fwd_wino3_kb", _ptr(xt), xb_, xp_, xkb, _ptr(wp), _ptr(bias), _ptr(coef), LRELU_SLOPE, _ptr(ot), ob_, op_, okb, _ptr(stats),
@@ -420,13 +428,13 @@ def _conv_raw(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], o
         return
     xb, xp, xc = grid_strides(x)
     bf16 = algo == "bf16"
-    vec_ok = xc == 1 and xp % 4 == 0 and xb % 4 == 0 and K % 4 == 0 and x.data_ptr() % 16 == 0
+    vec_ok = _vec4(x, K)
     if algo == "wino3":
         # F(2x2x2,3x3x3): channels-last, 16-byte aligned operand and result (the deep layers' tensors are; anything else is copied into that form)
         if not vec_ok:
             x = _packed_cl(x)
             xb, xp, xc = grid_strides(x)
-        if oc != 1 or op % 4 or ob % 4 or out.data_ptr() % 16:
+        if not _vec4(out):
             raise PulpoHipError("conv3d (F(2x2x2,3x3x3) kernel): the result must be channels-last and 16-byte aligned")
         t0 = _trace_begin()
         lib.call("pulpo_conv3d_k3_fwd_wino3", _ptr(x), xb, xp, xc, _ptr(wp), _ptr(bias), _ptr(coef), LRELU_SLOPE, _ptr(out), ob, op, oc, _ptr(stats),
@@ -492,6 +500,15 @@ def _persistent_buffer(owner: torch.Tensor, name: str, numel: int, zero: bool) -
         buf = (torch.zeros if zero else torch.empty)(numel, device=owner.device, dtype=torch.float32)
         setattr(owner, name, buf)
     return buf
+
+
+# kind 0 unpacks the weight-gradient scratch `buf` (Cin a, Cout b, padded Cout c) into `dst`; kind 1 adds the column sums of a rows x b columns
+# (row length c, 0 = b) of `buf`, from `byte_offset` on, to `dst`
+def _defer_grad_job(buf: torch.Tensor, dst: torch.Tensor, kind: int, a: int, b: int, c: int, byte_offset: int = 0) -> None:
+    """queue one finishing job for flush_param_grads() and keep its source buffer alive until then"""
+    _PENDING_GRAD_JOBS.append((buf.data_ptr() + byte_offset, dst.data_ptr(), kind, a, b, c))
+    if not (_PENDING_KEEPALIVE and _PENDING_KEEPALIVE[-1] is buf):
+        _PENDING_KEEPALIVE.append(buf)
 
 
 def _pending_src(buf: torch.Tensor) -> bool:
@@ -615,6 +632,20 @@ def _dims5(t):
     return t.shape if isinstance(t, _BlockedGrad) else (blocked_shape(t) if t.dim() == 6 else tuple(t.shape))
 
 
+# The Python predicate of a fused path has to agree with the C entry point's own check, so what the sites ask differently is an argument:
+# C - the channel count must be a multiple of four as well; align - the streaming kernels move four-channel groups of the storage type (8 bytes
+# of bf16); batch=False - sites that pin the batch stride themselves (== voxels * pixel stride).  A blocked operand keeps a voxel's eight channels together.
+def _vec4(t, C: Optional[int] = None, align: int = 16, batch: bool = True) -> bool:
+    """may a kernel read or write this operand with 16-byte channel vectors (channel stride 1, pixel and batch stride % 4, pointer % align)?"""
+    buf, b, p, _, blk = _opnd(t)
+    return (blk or t.stride(1) == 1) and p % 4 == 0 and (not batch or b % 4 == 0) and (C is None or C % 4 == 0) and buf.data_ptr() % align == 0
+
+
+def _cl_rows4(t: torch.Tensor) -> bool:
+    """channels-last with a pixel stride of whole four-channel groups (what the BatchNorm-backward kernels that write a blocked dy read)"""
+    return is_cl(t) and t.stride(4) % 4 == 0
+
+
 def blocked_z_wanted(x, unit_weight, next_weight, training: bool) -> bool:
     """should the ConvUnit with `unit_weight`, applied to x, hand its output to the unit with `next_weight` in the blocked layout?"""
     if not (BLOCKED_Z and training and torch.is_grad_enabled() and CONV_PRECISION == "fp32" and not ACT_BF16 and next_weight.requires_grad
@@ -640,11 +671,20 @@ def _blocked_dy_ok(x, y, weight, wpt, need_dx: bool, need_dw: bool) -> bool:
     if need_dw:
         if _use_bf16(Cin) or x.dtype != torch.float32 or lib.query("pulpo_conv3d_k3_wgrad_algo", B, D, H, W, Cin, Cout, 1) != 3:
             return False
-        if not is_blocked(x):
-            xb, xp, xc = grid_strides(x)
-            if xc != 1 or xp % 4 or xb % 4 or Cin % 4 or x.data_ptr() % 16:
-                return False
+        if not is_blocked(x) and not _vec4(x, Cin):
+            return False
     return True
+
+
+def _wgrad_target(Cin: int, Cout: int, into: Optional[torch.Tensor], owner: Optional[torch.Tensor], dev):
+    """where a weight-gradient launch puts its result: (dw, the kernels' accumulate mode, packed-sum scratch, deferred?)"""
+    # (mode 0 writes dw, 1 adds to it, 2 - deferred: `into` and its `owner` parameter, data-parallel stepper - leaves the packed sums in the
+    #  parameter's persistent scratch for flush_param_grads())
+    deferred = into is not None and owner is not None
+    dw = into if into is not None else torch.empty((Cout, Cin, 3, 3, 3), device=dev, dtype=torch.float32)
+    nscr = lib.query("pulpo_conv3d_k3_wgrad_scratch_floats", Cin, Cout)
+    scratch = _persistent_buffer(owner, "_pulpo_wgrad_scratch", nscr, zero=True) if deferred else torch.empty(nscr, device=dev, dtype=torch.float32)
+    return dw, (2 if deferred else int(into is not None)), scratch, deferred
 
 
 def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Optional[torch.Tensor] = None,
@@ -655,10 +695,7 @@ def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Opt
     B, _, D, H, W = _dims5(x)
     if is_blocked(x) and (_use_bf16(Cin) or lib.query("pulpo_conv3d_k3_wgrad_algo", B, D, H, W, Cin, Cout, 1) != 3):
         x = blocked_to_cl(x)                         # (a blocked operand outside the F(2x2x2,3x3x3) kernel's shapes: a copy - BLOCKED_Z switched between passes)
-    deferred = into is not None and owner is not None
-    dw = into if into is not None else torch.empty((Cout, Cin, 3, 3, 3), device=x.device, dtype=torch.float32)
-    nscr = lib.query("pulpo_conv3d_k3_wgrad_scratch_floats", Cin, Cout)
-    scratch = _persistent_buffer(owner, "_pulpo_wgrad_scratch", nscr, zero=True) if deferred else torch.empty(nscr, device=x.device, dtype=torch.float32)
+    dw, mode, scratch, deferred = _wgrad_target(Cin, Cout, into, owner, x.device)
     xblk = is_blocked(x)
     xt, xb, xp, xkb, _ = _opnd(x)
     xc = 1 if xblk else grid_strides(x)[2]
@@ -673,40 +710,36 @@ def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Opt
     if DETERMINISTIC:
         # one zero-initialised copy of the packed sums per spatial split of the grid (<= ~110 MB, transient), added up in fixed order
         nslab = lib.query("pulpo_conv3d_k3_wgrad_det_slabs", Cin, Cout)
-        slabs = torch.empty(nslab * nscr, device=x.device, dtype=torch.float32)
+        slabs = torch.empty(nslab * scratch.numel(), device=x.device, dtype=torch.float32)
         det = (_ptr(slabs), nslab)
     if blocked:
         # (_blocked_dy_ok has checked: fp32 operands, channels-last x, the F(2x2x2,3x3x3) weight-gradient kernel takes the shape)
         dyt, _, _, dkb, _ = _opnd(dy)
-        lib.call("pulpo_conv3d_k3_wgrad_kb" + wg, _ptr(xt), xb, xp, xkb, _ptr(dyt), db, dp, dkb, _ptr(dw), 2 if deferred else int(into is not None), _ptr(scratch),
+        lib.call("pulpo_conv3d_k3_wgrad_kb" + wg, _ptr(xt), xb, xp, xkb, _ptr(dyt), db, dp, dkb, _ptr(dw), mode, _ptr(scratch),
                  *(det if det else (None, 0)), B, D, H, W, Cin, Cout, _stream(), *wga)
-    elif sfx:
-        if x.dtype != dy.dtype:                      # (one storage type per launch; a mixed pair - a user's fp32 input to a bf16-storage unit - is rare)
-            x, dy = x.float(), dy.float()
-            xb, xp, xc = grid_strides(x)
-            db, dp, dc = grid_strides(dy)
-        lib.call("pulpo_conv3d_k3_wgrad_bf16_det_t" if det else "pulpo_conv3d_k3_wgrad_bf16_t", _ptr(x), xb, xp, xc, _ptr(dy), db, dp, dc, _dt(x), _ptr(dw),
-                 2 if deferred else int(into is not None), _ptr(scratch), *det, B, D, H, W, Cin, Cout, _stream())
     else:
-        if x.dtype != torch.float32 or dy.dtype != torch.float32:
+        # (one storage type per launch: the bf16 kernels take either - a mixed pair, a user's fp32 input to a bf16-storage unit, is rare -, the others fp32)
+        if x.dtype != dy.dtype or (not sfx and x.dtype != torch.float32):
             x, dy = x.float(), dy.float()
             xb, xp, xc = grid_strides(x)
             db, dp, dc = grid_strides(dy)
-        lib.call(("pulpo_conv3d_k3_wgrad_det" if det else "pulpo_conv3d_k3_wgrad") + wg, _ptr(x), xb, xp, xc, _ptr(dy), db, dp, dc, _ptr(dw),
-                 2 if deferred else int(into is not None), _ptr(scratch), *det, B, D, H, W, Cin, Cout, _stream(), *wga)
+        if sfx:
+            lib.call("pulpo_conv3d_k3_wgrad_bf16_det_t" if det else "pulpo_conv3d_k3_wgrad_bf16_t", _ptr(x), xb, xp, xc, _ptr(dy), db, dp, dc, _dt(x), _ptr(dw),
+                     mode, _ptr(scratch), *det, B, D, H, W, Cin, Cout, _stream())
+        else:
+            lib.call(("pulpo_conv3d_k3_wgrad_det" if det else "pulpo_conv3d_k3_wgrad") + wg, _ptr(x), xb, xp, xc, _ptr(dy), db, dp, dc, _ptr(dw),
+                     mode, _ptr(scratch), *det, B, D, H, W, Cin, Cout, _stream(), *wga)
     if deferred and not _pending_src(scratch):
         # (ONE finishing job per scratch: a unit applied twice in a step - shared weights, two forward passes - has accumulated both weight
         #  gradients into the same packed sums by the time the job runs)
-        _PENDING_GRAD_JOBS.append((scratch.data_ptr(), dw.data_ptr(), 0, Cin, Cout, (Cout + 63) // 64 * 64))
-        _PENDING_KEEPALIVE.append(scratch)
+        _defer_grad_job(scratch, dw, 0, Cin, Cout, (Cout + 63) // 64 * 64)
     if t0 is not None:
         name = "conv3d_k3_wgrad_bf16"
         if blocked:
             name = "conv3d_k3_wgrad_w3x"
         elif not sfx:
-            vec = (xc == 1 and xp % 4 == 0 and xb % 4 == 0 and Cin % 4 == 0 and x.data_ptr() % 16 == 0 and dc == 1 and dp % 4 == 0 and db % 4 == 0
-                   and Cout % 4 == 0 and dy.data_ptr() % 16 == 0)
-            name = {0: "conv3d_k3_wgrad_mfma", 2: "conv3d_k3_wgrad_w2", 3: "conv3d_k3_wgrad_w3x"}[lib.query("pulpo_conv3d_k3_wgrad_algo", B, D, H, W, Cin, Cout, int(vec))]
+            vec = int(_vec4(x, Cin) and _vec4(dy, Cout))
+            name = {0: "conv3d_k3_wgrad_mfma", 2: "conv3d_k3_wgrad_w2", 3: "conv3d_k3_wgrad_w3x"}[lib.query("pulpo_conv3d_k3_wgrad_algo", B, D, H, W, Cin, Cout, vec)]
         _trace_end(t0, name + ("" if deferred else "(+memset,unpack)"), 54.0 * Cin * Cout * B * D * H * W, ((4 if blocked else _esize(x)) * Cin + (4 if blocked else _esize(dy)) * Cout) * B * D * H * W)
     return None if into is not None else dw
 
@@ -719,14 +752,17 @@ def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Opt
 ASYNC_WGRAD_STREAM = None
 
 
-def _wgrad_on_side_stream(x, dy, Cin, Cout, slot_w, owner):
-    main = torch.cuda.current_stream()
+def _on_side_stream(launch, operands) -> None:
     side = ASYNC_WGRAD_STREAM
-    side.wait_stream(main)                       # after everything queued so far: dy, this unit's data gradient, zero_grad
+    side.wait_stream(torch.cuda.current_stream())        # after everything queued so far: dy, this unit's data gradient, zero_grad
     with torch.cuda.stream(side):
-        _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=owner)
-    x.record_stream(side)                        # keep both operands' memory out of the allocator's hands until the side stream is done
-    (dy.buf if isinstance(dy, _BlockedGrad) else dy).record_stream(side)
+        launch()
+    for t in operands:                           # keep the operands' memory out of the allocator's hands until the side stream is done
+        t.record_stream(side)
+
+
+def _wgrad_on_side_stream(x, dy, Cin, Cout, slot_w, owner):
+    _on_side_stream(lambda: _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=owner), (x, dy.buf if isinstance(dy, _BlockedGrad) else dy))
 
 
 def join_async_wgrad():
@@ -845,7 +881,6 @@ class CoarseWindow:
 # the producer to the consumer on the tensor z itself (`_pulpo_bn_src`); the backward pass of the consumer leaves the sums here, keyed by
 # the producer's y, and the producer takes them only if the gradient it is given IS that kernel's output, untouched (same storage, same
 # version: a gradient that autograd accumulated from several consumers is a different tensor or carries a bumped version).
-BN_REDUCE_IN_DGRAD = os.environ.get("PULPO_BN_REDUCE_IN_DGRAD", "1") != "0"      # (A/B switch)
 _BN_TILE_PARTS: dict = {}
 
 
@@ -858,15 +893,13 @@ def _dgrad_with_bn_reduction(bn_src, x, dy, wpt, dx, K: int, N: int) -> bool:
     dyt, db, dp, dkb, blocked = _opnd(dy)
     dc = 1 if blocked else grid_strides(dy)[2]
     dxt, ob, op, okb, oblk = _opnd(dx)
-    oc = 1 if oblk else grid_strides(dx)[2]
     if (blocked or oblk) and algo != "wino3":
         return False
-    yb, yp, yc = grid_strides(y_prev)
+    yb, yp, _ = grid_strides(y_prev)
     # (the C entry point also needs the gradient operand vectorisable: channels-last, 16-byte aligned, K % 4 == 0 - checked here so that a
     #  consumer unit with an odd channel count falls back to the separate reduction pass instead of raising in the middle of backward)
-    vec_ok = blocked or (dc == 1 and dp % 4 == 0 and db % 4 == 0 and K % 4 == 0 and dy.data_ptr() % 16 == 0)
-    if (not vec_ok or tuple(y_prev.shape) != tuple(_dims5(dx)) or oc != 1 or yc != 1 or op % 4 or ob % 4 or yp % 4 or yb % 4 or dx.data_ptr() % 16
-            or y_prev.data_ptr() % 16 or not lib.query("pulpo_conv3d_k3_dgrad_wino2_bnred_ok", B, D, H, W, K, N)):
+    vec_ok = blocked or _vec4(dy, K)
+    if (not vec_ok or tuple(y_prev.shape) != tuple(_dims5(dx)) or not _vec4(dx) or not _vec4(y_prev) or not lib.query("pulpo_conv3d_k3_dgrad_wino2_bnred_ok", B, D, H, W, K, N)):
         return False
     ntile = lib.query("pulpo_conv3d_k3_stat_tiles", B, D, H, W)
     part = torch.empty(ntile * 2 * N, device=dy.device, dtype=torch.float32)
@@ -895,24 +928,19 @@ def _take_bn_tile_parts(y: torch.Tensor, coef: torch.Tensor, dz: torch.Tensor):
     return part, ntile
 
 
-_TLS = threading.local()
-
-
 # ---- producers that write straight into a slice of a wider channels-last buffer (round 5).  PULPoEncoder concatenates the up-sampled
 # feedback path's output with the DownPath activation of its level (torch.cat([feedback, down_activation], 1), components/pulpo.py:252): two
 # strided copy kernels per level and step (111 us at 80^3).  DownPath allocates the concatenation's buffer up front and its last ConvUnit, like
 # the feedback path's later, writes its output into its channel range - every kernel addresses operands through explicit pixel strides, so the
 # slices are ordinary operands, and the concatenation is the buffer itself (cat_prewritten).
-def _take_out_slot(B, C, D, H, W, dev, dtype):
-    slot = getattr(_TLS, "out_slot", None)
-    _TLS.out_slot = None
-    if slot is None:
+def _out_slot(out, B, C, D, H, W, dev, dtype):
+    """the channel range of `out` = (buffer, first channel) that a ConvUnit writes its result into, or None (no slot, or the shapes do not fit)"""
+    if out is None:
         return None
-    buf, off = slot
-    if (buf.dim() != 5 or tuple(buf.shape[2:]) != (D, H, W) or buf.shape[0] != B or buf.dtype != dtype or buf.device != dev or off < 0 or off + C > buf.shape[1]
-            or not is_cl(buf) or off % 8 or buf.shape[1] % 8):
-        return None
-    return buf[:, off:off + C]
+    buf, off = out
+    fits = (buf.dim() == 5 and tuple(buf.shape[2:]) == (D, H, W) and buf.shape[0] == B and buf.dtype == dtype and buf.device == dev and off >= 0
+            and off + C <= buf.shape[1] and is_cl(buf) and off % 8 == 0 and buf.shape[1] % 8 == 0)
+    return buf[:, off:off + C] if fits else None
 
 
 CAT_PREWRITTEN_HITS = 0          # concatenations that cost nothing so far (tests look at it)
@@ -946,19 +974,99 @@ def cat_channels(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.cat([a, b], dim=1)
 
 
+# ---- the ConvUnit autograd node.  A Function takes and returns tensors, so everything else about one application travels in a _UnitCall: the
+# caller (conv_bn_lrelu, the head wrappers) fills in what the node needs besides the tensors that can ask for a gradient, forward() fills in what
+# the caller needs back.  backward() is five stages, each a function of plain values below:
+#   1 _bwd_dz_source    the incoming gradients of the node's outputs -> where dz is read from (a _DzSource; None: no gradient arrived)
+#   2 _bwd_bn_sums      the first BatchNorm-backward pass - per-tile (sum dbn, sum dbn * xhat) - and its finalize.  The sums come from one of four
+#                       places: left behind by the data-gradient convolution (or pooling backward) that PRODUCED dz, if that was the operator behind
+#                       this unit (_BN_TILE_PARTS); the pooled pass; the head's backward; else a pass of its own over dz and y
+#   3 _bwd_bn_apply     the second pass writes dy, blocked or channels-last (_bn_apply_entry: the entry point for the source and dy's layout), and the
+#                       conv-bias gradient's partial rows - except for the input layer, whose weight gradient forms dy itself (stage 4): no dy
+#   4 _bwd_param_grads  the conv-bias gradient (deferred, or column sums now) and the weight gradient, which goes ONE of four ways: fused with the
+#                       second pass (_input_layer_param_grads; scratch, accumulate mode and deferral as _wgrad_raw's); to the side stream behind
+#                       this unit's data gradient (the job is handed to stage 5); to the coarse window (in line, held back, or on ITS side stream);
+#                       in line
+#   5 _bwd_data_grad    dx in x's layout - with the producing unit's BatchNorm reduction riding along where it can - then stage 4's side-stream job
+class _UnitCall:
+    __slots__ = ("bn_src", "out", "pool_after", "pool_only", "blocked_out", "training", "momentum", "eps", "running_mean", "running_var",
+                 "num_batches_tracked", "head_nout", "head_eps", "head_params", "y", "coef", "pooled", "pool_only_done")
+
+    def __init__(self, **given):
+        assert not set(given) - set(self.__slots__), given
+        # (forward() fills in the rest: the pre-norm tensor and coefficient block - the `_pulpo_bn_src` tag -, AvgPool(result) where the same pass
+        #  wrote it, and whether that pooled tensor ALONE was returned)
+        for name in self.__slots__:
+            setattr(self, name, given.get(name))
+
+
+# where a ConvUnit's backward reads dz, the gradient of its activation - exactly one of
+#   dz      a tensor: channels-last, or (`blk`) blocked as the next unit's data-gradient kernel wrote it
+#   pooled  (gpool, gskip or None): dz = gskip + avg_pool_backward(gpool), never written
+#   head    (nout, the head kernels' pointer operands, the tensors behind them): dz = W^T dpre, never written
+_DzSource = collections.namedtuple("_DzSource", "dz blk pooled head", defaults=(None, False, None, None))
+
+
+# what backward() returns: one entry per argument of _ConvBNLReLU.forward (x, weight, bias, gamma, beta, head_w, head_b, call)
+def _unit_grads(dx=None, dw=None, dbias=None, dgamma=None, dbeta=None, head_dw=None, head_db=None):
+    return dx, dw, dbias, dgamma, dbeta, head_dw, head_db, None
+
+
+def _fwd_heads(y, coef, head_w, head_b, head_eps, nout: int, dims):
+    # the 1x1x1 head on the pre-norm tensor -> ([field] or [mu, sigma, sample], planar noise)
+    _require_gpu(head_w, head_b, head_eps)
+    B, Cout, D, H, W = dims
+    V = D * H * W
+    outs = [torch.empty((B, 3, D, H, W), device=y.device, dtype=torch.float32) for _ in range(1 if nout == 3 else 3)]
+    epsc = planar(head_eps) if head_eps is not None else None
+    t0 = _hbm_begin("heads_fwd_bn")
+    lib.call("pulpo_heads_fwd_bn_t", _ptr(y), y.stride(4), _ptr(coef), LRELU_SLOPE, _ptr(head_w), _ptr(head_b), _ptr(epsc), _ptr(outs[0]),
+             _ptr(outs[1]) if nout == 6 else None, _ptr(outs[2]) if nout == 6 else None, nout, B, V, Cout, _stream())
+    _hbm_end(t0, "heads_fwd_bn", B * V * (4.0 * Cout + 4.0 * (12 if nout == 6 else 3)))       # read y (+ eps), write mu / sigma / z (or the field)
+    return outs, epsc
+
+
+def _fwd_bn_lrelu_apply(y, coef, call, dims, zdt):
+    # z = lrelu(bn(y)) in the form its readers want -> (z or None, AvgPool(z) or None, pool_only?)
+    B, Cout, D, H, W = dims
+    dev, npix = y.device, B * D * H * W
+    # pool_only: nobody reads the un-pooled activation (DownPath levels above the first latent level: only AvgPool(z) goes on) - it is not written
+    pool_only = bool(call.pool_only and call.pool_after and lib.query("pulpo_bn_lrelu_apply_pool2_ok", Cout, y.stride(4), Cout, Cout))
+    blocked_out = bool(call.blocked_out and call.training and not call.pool_after and not pool_only and zdt == y.dtype == torch.float32 and Cout % 8 == 0)
+    z = None if (pool_only or blocked_out) else _out_slot(call.out, B, Cout, D, H, W, dev, zdt)
+    if z is None and not pool_only and not blocked_out:
+        z = new_cl(B, Cout, D, H, W, dev, zdt)
+    pooled = None
+    if blocked_out:
+        # the next ConvUnit of the sequence reads z through its F(2x2x2,3x3x3) kernels only (blocked_z_wanted): [Cout / 8][B][D][H][W][8]
+        global BLOCKED_Z_HITS
+        BLOCKED_Z_HITS += 1
+        z = torch.empty((Cout // 8, B, D, H, W, 8), device=dev, dtype=torch.float32)
+        entry, args = "pulpo_bn_lrelu_apply_kb", (_ptr(y), y.stride(4), _ptr(z), 8, npix * 8, _ptr(coef), npix, Cout, LRELU_SLOPE)
+    elif pool_only or (call.pool_after and lib.query("pulpo_bn_lrelu_apply_pool2_ok", Cout, y.stride(4), z.stride(4), Cout)):
+        # the caller pools this output next (DownPath): z and AvgPool(z) from one read of y; avg_pool2_skip() picks the pooled tensor up
+        pooled = new_cl(B, Cout, (D + 1) // 2, (H + 1) // 2, (W + 1) // 2, dev, zdt)
+        entry, args = "pulpo_bn_lrelu_apply_pool2_t", (_ptr(y), _dt(y), y.stride(4), _ptr(z), _dt(pooled), z.stride(4) if z is not None else Cout, _ptr(pooled),
+                                                       pooled.stride(4), _ptr(coef), B, D, H, W, Cout, LRELU_SLOPE)
+    else:
+        entry, args = "pulpo_bn_lrelu_apply_t", (_ptr(y), _dt(y), y.stride(4), _ptr(z), _dt(z), z.stride(4), _ptr(coef), npix, Cout, LRELU_SLOPE)
+    t0 = _hbm_begin("bn_lrelu_apply")
+    lib.call(entry, *args, _stream())
+    _hbm_end(t0, "bn_lrelu_apply", (_esize(y) + (0 if pool_only else (2.0 if zdt == torch.bfloat16 else 4.0))) * Cout * npix)      # read y, write z
+    return z, pooled, pool_only
+
+
 class _ConvBNLReLU(torch.autograd.Function):
     """ConvUnit: Conv3d(k3,p1,bias) -> BatchNorm3d -> LeakyReLU(0.2)   (reference src/network_blocks.py:22-26)"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, num_batches_tracked, training: bool, momentum: float, eps: float,
-                bn_src=None, pool_after: bool = False, pool_only: bool = False, blocked_out: bool = False, head_w=None, head_b=None, head_eps=None,
-                head_nout: int = 0, head_params=None):
-        """head_nout = 3 / 6 (conv_bn_lrelu_heads): the unit's activation is read by a 1x1x1 head (head_w [nout][Cout], head_b [nout], head_eps) and by
-        nothing else - the node returns the head's outputs, and neither the activation nor its gradient is written"""
+    def forward(ctx, x, weight, bias, gamma, beta, head_w, head_b, call: _UnitCall):
+        """call.head_nout = 3 / 6 (_conv_bn_lrelu_heads): the unit's activation is read by a 1x1x1 head (head_w [nout][Cout], head_b [nout], call.head_eps)
+        and by nothing else - the node returns the head's outputs, and neither the activation nor its gradient is written"""
         _require_gpu(x, act=True)
         _require_gpu(weight, bias, gamma, beta)
-        ctx.bn_src = bn_src
-        ctx.head = None
+        training = call.training
+        ctx.bn_src = call.bn_src
         # x: (B, C, D, H, W), or the blocked output (C / 8, B, D, H, W, 8) of the previous ConvUnit of the sequence (is_blocked)
         ctx.dx_blocked = is_blocked(x)
         if not ctx.dx_blocked:
@@ -984,72 +1092,33 @@ class _ConvBNLReLU(torch.autograd.Function):
             _conv_raw(x, wp, bias, y, Cin, Cout, stats)
             nsd = lib.query("pulpo_bn_fwd_finalize_scratch_doubles", ntile, Cout)
             scratch = torch.empty(nsd, device=dev, dtype=torch.float64) if nsd else None
-            lib.call("pulpo_bn_fwd_finalize", _ptr(stats), ntile, Cout, float(B * D * H * W), _ptr(gamma), _ptr(beta), _ptr(running_mean),
-                     _ptr(running_var), _ptr(num_batches_tracked), momentum, eps, _ptr(coef), _ptr(scratch), _stream())
+            lib.call("pulpo_bn_fwd_finalize", _ptr(stats), ntile, Cout, float(B * D * H * W), _ptr(gamma), _ptr(beta), _ptr(call.running_mean),
+                     _ptr(call.running_var), _ptr(call.num_batches_tracked), call.momentum, call.eps, _ptr(coef), _ptr(scratch), _stream())
         else:
-            lib.call("pulpo_bn_eval_coef", _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), eps, Cout, _ptr(coef), _stream())
+            lib.call("pulpo_bn_eval_coef", _ptr(gamma), _ptr(beta), _ptr(call.running_mean), _ptr(call.running_var), call.eps, Cout, _ptr(coef), _stream())
             if not any(ctx.needs_input_grad) and ydt == zdt:
                 # inference: conv + folded BatchNorm + LeakyReLU in one kernel, the pre-norm tensor is never written
-                zo = _take_out_slot(B, Cout, D, H, W, dev, zdt)
+                zo = _out_slot(call.out, B, Cout, D, H, W, dev, zdt)
                 if zo is not None:
                     y = zo
                 _conv_raw(x, wp, bias, y, Cin, Cout, None, coef=coef)
                 return y
             _conv_raw(x, wp, bias, y, Cin, Cout, None)
-        if head_nout:
-            # (conv_bn_lrelu_heads has checked: training statistics, fp32 storage, no pooling, no output slot)
-            _require_gpu(head_w, head_b, head_eps)
-            V = D * H * W
-            outs = [torch.empty((B, 3, D, H, W), device=dev, dtype=torch.float32) for _ in range(1 if head_nout == 3 else 3)]
-            epsc = planar(head_eps) if head_eps is not None else None
-            t0 = _hbm_begin("heads_fwd_bn")
-            lib.call("pulpo_heads_fwd_bn_t", _ptr(y), y.stride(4), _ptr(coef), LRELU_SLOPE, _ptr(head_w), _ptr(head_b), _ptr(epsc), _ptr(outs[0]),
-                     _ptr(outs[1]) if head_nout == 6 else None, _ptr(outs[2]) if head_nout == 6 else None, head_nout, B, V, Cout, _stream())
-            _hbm_end(t0, "heads_fwd_bn", B * V * (4.0 * Cout + 4.0 * (12 if head_nout == 6 else 3)))       # read y (+ eps), write mu / sigma / z (or the field)
-            ctx.save_for_backward(x, weight, y, coef, head_w, epsc, outs[1] if head_nout == 6 else None)
-            ctx.training = training
-            ctx.params = (weight, bias, gamma, beta)
-            ctx.head = (head_nout, head_params)
-            ctx.pooled_out = ctx.pool_only = False
-            _TLS.produced = None
-            return outs[0] if head_nout == 3 else tuple(outs)
-        # pool_only: nobody reads the un-pooled activation (DownPath levels above the first latent level: only AvgPool(z) goes on) - it is not written
-        pool_only = bool(pool_only and pool_after and lib.query("pulpo_bn_lrelu_apply_pool2_ok", Cout, y.stride(4), Cout, Cout))
-        blocked_out = bool(blocked_out and training and not pool_after and not pool_only and zdt == torch.float32 and ydt == torch.float32 and Cout % 8 == 0)
-        z = None if (pool_only or blocked_out) else _take_out_slot(B, Cout, D, H, W, dev, zdt)
-        if z is None and not pool_only and not blocked_out:
-            z = new_cl(B, Cout, D, H, W, dev, zdt)
-        pooled = None
-        nbytes = (_esize(y) + (0 if pool_only else (2.0 if zdt == torch.bfloat16 else 4.0))) * Cout * B * D * H * W             # read y, write z
-        if blocked_out:
-            # the next ConvUnit of the sequence reads z through its F(2x2x2,3x3x3) kernels only (blocked_z_wanted): [Cout / 8][B][D][H][W][8]
-            global BLOCKED_Z_HITS
-            BLOCKED_Z_HITS += 1
-            z = torch.empty((Cout // 8, B, D, H, W, 8), device=dev, dtype=torch.float32)
-            t0 = _hbm_begin("bn_lrelu_apply")
-            lib.call("pulpo_bn_lrelu_apply_kb", _ptr(y), y.stride(4), _ptr(z), 8, B * D * H * W * 8, _ptr(coef), B * D * H * W, Cout, LRELU_SLOPE, _stream())
-            _hbm_end(t0, "bn_lrelu_apply", nbytes)
-        elif pool_only or (pool_after and lib.query("pulpo_bn_lrelu_apply_pool2_ok", Cout, y.stride(4), z.stride(4), Cout)):
-            # the caller pools this output next (DownPath): z and AvgPool(z) from one read of y; avg_pool2_skip() picks the pooled tensor up
-            pooled = new_cl(B, Cout, (D + 1) // 2, (H + 1) // 2, (W + 1) // 2, dev, zdt)
-            t0 = _hbm_begin("bn_lrelu_apply")
-            lib.call("pulpo_bn_lrelu_apply_pool2_t", _ptr(y), _dt(y), y.stride(4), _ptr(z), _dt(pooled), z.stride(4) if z is not None else Cout, _ptr(pooled),
-                     pooled.stride(4), _ptr(coef), B, D, H, W, Cout, LRELU_SLOPE, _stream())
-            _hbm_end(t0, "bn_lrelu_apply", nbytes)
-        else:
-            t0 = _hbm_begin("bn_lrelu_apply")
-            lib.call("pulpo_bn_lrelu_apply_t", _ptr(y), _dt(y), y.stride(4), _ptr(z), _dt(z), z.stride(4), _ptr(coef), B * D * H * W, Cout, LRELU_SLOPE,
-                     _stream())
-            _hbm_end(t0, "bn_lrelu_apply", nbytes)
-        ctx.save_for_backward(x, weight, y, coef)
         ctx.training = training
         ctx.params = (weight, bias, gamma, beta)      # for DIRECT_PARAM_GRADS (their .grad slots)
-        _TLS.produced = (y, coef, pooled)            # read back by conv_bn_lrelu (the Function returns tensors only)
-        ctx.pooled_out = pooled is not None
+        ctx.pool_only = False
+        ctx.head = (call.head_nout, call.head_params) if call.head_nout else None
+        if call.head_nout:
+            # (_conv_bn_lrelu_heads has checked: training statistics, fp32 storage, no pooling, no output slot)
+            outs, epsc = _fwd_heads(y, coef, head_w, head_b, call.head_eps, call.head_nout, (B, Cout, D, H, W))
+            ctx.save_for_backward(x, weight, y, coef, head_w, epsc, outs[1] if call.head_nout == 6 else None)
+            return outs[0] if call.head_nout == 3 else tuple(outs)
+        z, pooled, pool_only = _fwd_bn_lrelu_apply(y, coef, call, (B, Cout, D, H, W), zdt)
+        ctx.save_for_backward(x, weight, y, coef)
+        call.y, call.coef, call.pooled, call.pool_only_done = y, coef, pooled, pool_only      # read back by conv_bn_lrelu
         ctx.pool_only = pool_only
         if pool_only:
             ctx.set_materialize_grads(False)
-            _TLS.pool_only_done = True
             return pooled
         if pooled is not None:
             # (round 5) z AND AvgPool(z) are outputs of this node: their gradients arrive together, and the backward pass forms
@@ -1059,240 +1128,257 @@ class _ConvBNLReLU(torch.autograd.Function):
         return z
 
     @staticmethod
-    def backward(ctx, dz, dpool=None, dsample=None):
-        head = ctx.head
-        if head is not None:                         # (the node's outputs are the head's: the field, or mu / sigma / sample)
-            head_g, dz, dpool = (dz, dpool, dsample), None, None
-        elif ctx.pool_only:                          # (the node's only output is the pooled tensor)
-            dz, dpool = None, dz
+    def backward(ctx, *grads):
         x, weight, y, coef = ctx.saved_tensors[:4]
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
         B, Cin, D, H, W = _dims5(x)
-        Cout = weight.shape[0]
-        dev = x.device
-        npix = B * D * H * W
-        nblk = lib.query("pulpo_bn_bwd_blocks", npix, Cout)
-        NG = 20                                      # inputs of forward()
-        dz_blk = is_blocked(dz)                      # the gradient of a blocked activation arrives blocked (the next unit's data-gradient kernel wrote it so)
-        if dz_blk and (dz.dtype != torch.float32 or not dz.is_contiguous() or tuple(blocked_shape(dz)) != (B, Cout, D, H, W)):
-            dz, dz_blk = blocked_to_cl(dz.float()), False
-        pooled_src = None                            # (gpool, gskip or None): dz = gskip + avg_pool_backward(gpool), never written
-        if dpool is not None:
-            gp = to_cl(dpool)
-            gz = dz
-            if gz is not None and gz.dtype != gp.dtype:
-                gz = gz.to(gp.dtype)
-            grp = 4 * int(_esize(gp))
-            skip_ok = gz is None
-            if gz is not None:
-                sb, sp, sc = grid_strides(gz)
-                skip_ok = _dense_grid(gz) and sc == 1 and sb == D * H * W * sp and sp % 4 == 0 and gz.data_ptr() % grp == 0
-            if (Cout % 4 == 0 and Cout // 4 <= 256 and skip_ok and gp.stride(4) % 4 == 0 and gp.data_ptr() % grp == 0 and y.stride(1) == 1
-                    and y.stride(4) % 4 == 0 and y.data_ptr() % (4 * int(_esize(y))) == 0 and _dense_grid(y) and POOLED_BN_BACKWARD):
-                pooled_src = (gp, gz)
-            else:                                    # shapes the fused passes do not take: the gradient as a tensor, then the plain path
-                gin = new_cl(B, Cout, D, H, W, dev, gp.dtype)
-                if skip_ok and gz is not None:
-                    lib.call("pulpo_avgpool2_bwd_t", _ptr(gp), gp.stride(4), _ptr(gz), grid_strides(gz)[1], _ptr(gin), gin.stride(4), _dt(gp), B, D, H, W, Cout, _stream())
-                else:
-                    lib.call("pulpo_avgpool2_bwd_t", _ptr(gp), gp.stride(4), None, 0, _ptr(gin), gin.stride(4), _dt(gp), B, D, H, W, Cout, _stream())
-                    if gz is not None:
-                        gin = gin + gz
-                dz = gin
-        elif dz is None and head is None:
-            return (None,) * NG
-        tiles = None
-        if pooled_src is not None:
-            gp, gz = pooled_src
-            part = torch.empty(nblk * 2 * Cout, device=dev, dtype=torch.float32)
-            t0 = _hbm_begin("avgpool2_bwd_bnred")
-            lib.call("pulpo_avgpool2_bwd_bnred_t", _ptr(gp), gp.stride(4), _ptr(gz), grid_strides(gz)[1] if gz is not None else 0, None, 0, _dt(gp), _ptr(y), _dt(y),
-                     y.stride(4), _ptr(coef), LRELU_SLOPE, _ptr(part), B, D, H, W, Cout, _stream())
-            # read the pooled gradient, the skip gradient and y (the summed gradient is not written)
-            _hbm_end(t0, "avgpool2_bwd_bnred", Cout * (_esize(gp) * (gp.numel() // Cout + (npix if gz is not None else 0)) + _esize(y) * npix))
-        elif head is None:
-            if not dz_blk:
-                dz = to_cl(dz)
-            # first pass (sum dbn, sum dbn * xhat): already done by the epilogue of the data-gradient convolution that PRODUCED dz, if that was
-            # the ConvUnit behind this one (see _BN_TILE_PARTS); else a pass of its own over dz and y
-            tiles = _take_bn_tile_parts(y, coef, dz)
-            if tiles is None and dz_blk:             # (the separate reduction pass reads channels-last: autograd summed several gradients of z - a copy)
-                dz, dz_blk = blocked_to_cl(dz), False
-        heads_src, head_dw, head_db = None, None, None
-        if head is not None:
-            # the head's backward and this unit's first BatchNorm-backward pass in one kernel over y: dz = W^T dpre is formed per element for the sums
-            # (and again by the second pass below) and never written
-            nout, hparams = head
-            hw, heps, hsigma = ctx.saved_tensors[4:7]
-            V = D * H * W
-            g = [planar(t) if t is not None else None for t in head_g]
-            if nout == 3 and g[0] is None:
-                g[0] = torch.zeros((B, 3, D, H, W), device=dev)
-            hblk = lib.query("pulpo_heads_bwd_blocks", B, V, Cout)
-            hpart, hslots = _heads_part_rows(hparams, ctx.needs_input_grad[15] and ctx.needs_input_grad[16], hblk, nout, Cout, dev)
-            part = torch.empty(hblk * 2 * Cout, device=dev, dtype=torch.float32)
-            heads_src = (_ptr(hw), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(heps), _ptr(hsigma))
-            t0 = _hbm_begin("heads_bwd_bn")
-            lib.call("pulpo_heads_bwd_bn_t", _ptr(y), y.stride(4), _ptr(coef), LRELU_SLOPE, *heads_src, _ptr(hpart), _ptr(part), nout, B, V, Cout, _stream())
-            _hbm_end(t0, "heads_bwd_bn", B * V * (4.0 * Cout + 4.0 * (15 if nout == 6 else 3)))       # read y and the output gradients (+ eps, sigma)
-            head_dw, head_db = _heads_finish_rows(hpart, hslots, hparams, hblk, nout, Cout)
-            tiles = (part, hblk)
-        if tiles is None and pooled_src is None:
-            part = torch.empty(nblk * 2 * Cout, device=dev, dtype=torch.float32)
+        dims = (B, Cin, weight.shape[0], D, H, W)
+        nblk = lib.query("pulpo_bn_bwd_blocks", B * D * H * W, dims[2])
+        src = _bwd_dz_source(grads, ctx.head, ctx.pool_only, ctx.saved_tensors, y, dims)
+        if src is None:
+            return _unit_grads()
+        src, totd, slot_w, slot_b, dgamma, dbeta, head_dw, head_db = _bwd_bn_sums(
+            src, y, coef, dims, nblk, ctx.training, ctx.params, ctx.needs_input_grad, ctx.head)
+        # the data-gradient weights now (cached pack): their kernel family decides dy's layout
+        wpt = _pack_weight(weight, dgrad=True, shape=(B, D, H, W)) if need_dx else None
+        dy, bias_rows = _bwd_bn_apply(src, x, weight, y, coef, totd, wpt, dims, nblk, (need_dx, need_dw, need_db), ctx.params[1], slot_b)
+        dw, dbias, side_job = _bwd_param_grads(src, x, dy, bias_rows, y, coef, totd, dims, (need_dw, need_db), ctx.params, slot_w, slot_b)
+        dx = _bwd_data_grad(x, dy, wpt, ctx.bn_src, ctx.dx_blocked, dims, side_job)
+        return _unit_grads(dx, dw, dbias, dgamma, dbeta, head_dw, head_db)
+
+
+def _bwd_dz_source(grads, head, pool_only: bool, saved, y, dims) -> Optional[_DzSource]:
+    B, _, Cout, D, H, W = dims
+    dev = y.device
+    dz, dpool, dsample = (grads + (None, None))[:3]
+    if head is not None:                         # (the node's outputs are the head's: the field, or mu / sigma / sample)
+        g = [planar(t) if t is not None else None for t in (dz, dpool, dsample)]
+        if head[0] == 3 and g[0] is None:
+            g[0] = torch.zeros((B, 3, D, H, W), device=dev)
+        hw, heps, hsigma = saved[4:7]
+        return _DzSource(head=(head[0], (_ptr(hw), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(heps), _ptr(hsigma)), (hw, g, heps, hsigma)))
+    if pool_only:                                # (the node's only output is the pooled tensor)
+        dz, dpool = None, dz
+    dz_blk = is_blocked(dz)                      # the gradient of a blocked activation arrives blocked (the next unit's data-gradient kernel wrote it so)
+    if dz_blk and (dz.dtype != torch.float32 or not dz.is_contiguous() or tuple(blocked_shape(dz)) != (B, Cout, D, H, W)):
+        dz, dz_blk = blocked_to_cl(dz.float()), False
+    if dpool is None:
+        if dz is None:
+            return None
+        return _DzSource(dz if dz_blk else to_cl(dz), dz_blk)
+    gp = to_cl(dpool)
+    gz = dz
+    if gz is not None and gz.dtype != gp.dtype:
+        gz = gz.to(gp.dtype)
+    grp = 4 * int(_esize(gp))                    # bytes of a four-channel group
+    skip_ok = gz is None
+    if gz is not None:
+        sb, sp, _ = grid_strides(gz)
+        skip_ok = _dense_grid(gz) and sb == D * H * W * sp and _vec4(gz, align=grp, batch=False)
+    if (Cout // 4 <= 256 and skip_ok and _vec4(gp, Cout, align=grp, batch=False) and _vec4(y, align=4 * int(_esize(y)), batch=False)
+            and _dense_grid(y) and POOLED_BN_BACKWARD):
+        return _DzSource(pooled=(gp, gz))
+    # shapes the fused passes do not take: the gradient as a tensor, then the plain path
+    gin = new_cl(B, Cout, D, H, W, dev, gp.dtype)
+    add = skip_ok and gz is not None             # (the kernel adds the skip gradient where it can read it in four-channel groups)
+    lib.call("pulpo_avgpool2_bwd_t", _ptr(gp), gp.stride(4), _ptr(gz) if add else None, grid_strides(gz)[1] if add else 0, _ptr(gin), gin.stride(4), _dt(gp),
+             B, D, H, W, Cout, _stream())
+    return _DzSource(to_cl(gin if (add or gz is None) else gin + gz), False)
+
+
+def _bwd_bn_sums(src: _DzSource, y, coef, dims, nblk: int, training: bool, params, needs, head):
+    # -> (src, totd, slot_w, slot_b, dgamma, dbeta, head_dw, head_db)
+    B, _, Cout, D, H, W = dims
+    dev, npix = y.device, B * D * H * W
+    head_dw = head_db = None
+    if src.pooled is not None:
+        gp, gz = src.pooled
+        rows, nrow = torch.empty(nblk * 2 * Cout, device=dev, dtype=torch.float32), nblk
+        t0 = _hbm_begin("avgpool2_bwd_bnred")
+        lib.call("pulpo_avgpool2_bwd_bnred_t", _ptr(gp), gp.stride(4), _ptr(gz), grid_strides(gz)[1] if gz is not None else 0, None, 0, _dt(gp), _ptr(y), _dt(y),
+                 y.stride(4), _ptr(coef), LRELU_SLOPE, _ptr(rows), B, D, H, W, Cout, _stream())
+        # read the pooled gradient, the skip gradient and y (the summed gradient is not written)
+        _hbm_end(t0, "avgpool2_bwd_bnred", Cout * (_esize(gp) * (gp.numel() // Cout + (npix if gz is not None else 0)) + _esize(y) * npix))
+    elif src.head is not None:
+        # the head's backward and this unit's first BatchNorm-backward pass in one kernel over y: dz = W^T dpre is formed per element for the sums
+        # (and again by the second pass) and never written
+        (nout, hparams), V = head, D * H * W
+        nrow = lib.query("pulpo_heads_bwd_blocks", B, V, Cout)
+        hpart, hslots = _heads_part_rows(hparams, needs[5] and needs[6], nrow, nout, Cout, dev)
+        rows = torch.empty(nrow * 2 * Cout, device=dev, dtype=torch.float32)
+        t0 = _hbm_begin("heads_bwd_bn")
+        lib.call("pulpo_heads_bwd_bn_t", _ptr(y), y.stride(4), _ptr(coef), LRELU_SLOPE, *src.head[1], _ptr(hpart), _ptr(rows), nout, B, V, Cout, _stream())
+        _hbm_end(t0, "heads_bwd_bn", B * V * (4.0 * Cout + 4.0 * (15 if nout == 6 else 3)))       # read y and the output gradients (+ eps, sigma)
+        head_dw, head_db = _heads_finish_rows(hpart, hslots, hparams, nrow, nout, Cout)
+    else:
+        tiles = _take_bn_tile_parts(y, coef, src.dz)
+        if tiles is not None:
+            rows, nrow = tiles
+        else:
+            if src.blk:                          # (the separate reduction pass reads channels-last: autograd summed several gradients of z - a copy)
+                src = _DzSource(blocked_to_cl(src.dz), False)
+            dz = src.dz
+            rows, nrow = torch.empty(nblk * 2 * Cout, device=dev, dtype=torch.float32), nblk
             t0 = _hbm_begin("bn_lrelu_bwd_reduce")
             lib.call("pulpo_bn_lrelu_bwd_reduce_t", _ptr(dz), _dt(dz), dz.stride(4), _ptr(y), _dt(y), y.stride(4), _ptr(coef), npix, Cout, LRELU_SLOPE,
-                     _ptr(part), _stream())
+                     _ptr(rows), _stream())
             _hbm_end(t0, "bn_lrelu_bwd_reduce", (_esize(dz) + _esize(y)) * Cout * npix)                # read dz, y
-        w_p, b_p, g_p, be_p = ctx.params
-        win = COARSE_WINDOW
-        if win is not None:
-            win.visit(D * H * W)
-        slot_w, slot_b, slot_g, slot_be = (_grad_slot(t) if need else None
-                                           for t, need in zip((w_p, b_p, g_p, be_p), ctx.needs_input_grad[1:5]))
-        direct_bn = slot_g is not None and slot_be is not None
-        tot = None if direct_bn else torch.empty(2 * Cout, device=dev, dtype=torch.float32)           # dbeta | dgamma
-        totd = torch.empty(2 * Cout, device=dev, dtype=torch.float64)          # mean(dbn) | mean(dbn * xhat), kept in double
-        # eval-mode BatchNorm is a fixed affine map (dy = scale * dbn): the batch means do not enter
-        fin_out = (_ptr(slot_be if direct_bn else tot), _ptr(slot_g) if direct_bn else ctypes.c_void_p(tot.data_ptr() + 4 * Cout), int(direct_bn), _ptr(totd))
-        rows, nrow = (part, nblk) if tiles is None else tiles       # (pooled_src: `part` from the pooled first pass above)
-        nsd = lib.query("pulpo_bn_bwd_finalize_scratch_doubles", nrow, Cout)
-        scratch = torch.empty(nsd, device=dev, dtype=torch.float64) if nsd else None
-        lib.call("pulpo_bn_bwd_finalize", _ptr(rows), nrow, Cout, _ptr(coef), float(npix), int(ctx.training), *fin_out, _ptr(scratch), _stream())
-        # The input layer (image pair -> 32 channels at full resolution): nobody asks for its data gradient, so dy has ONE reader - the weight
-        # gradient, which then forms it per element while staging (pulpo_conv3d_k3_wgrad_bn) instead of a pass that reads dz and y and writes dy
-        # (0.29 ms at 160^3 x 32 channels).  PULPO_FUSE_INPUT_WGRAD=0: the separate pass (A/B switch).
-        if (FUSE_INPUT_WGRAD and pooled_src is None and heads_src is None and Cin <= 2 and not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not DETERMINISTIC and y.dtype == torch.float32
-                and Cout % 4 == 0 and is_cl(y) and (dz_blk or (is_cl(dz) and dz.stride(4) % 4 == 0)) and y.stride(4) % 4 == 0 and x.dtype == torch.float32):
-            return _ConvBNLReLU._backward_input_layer(ctx, dz, x, weight, y, coef, totd, tot, direct_bn, (slot_w, slot_b), (w_p, b_p))
-        # the data-gradient weights now (cached pack): their kernel family decides dy's layout
-        wpt = _pack_weight(weight, dgrad=True, shape=(B, D, H, W)) if ctx.needs_input_grad[0] else None
-        blocked = (_blocked_dy_ok(x, y, weight, wpt, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-                   and (pooled_src is not None or heads_src is not None or dz_blk or (is_cl(dz) and dz.stride(4) % 4 == 0)) and is_cl(y) and y.stride(4) % 4 == 0)
-        if blocked:
-            global BLOCKED_DY_HITS
-            BLOCKED_DY_HITS += 1
-            dy = _BlockedGrad(B, Cout, D, H, W, dev)
-        else:
-            dy = new_cl(B, Cout, D, H, W, dev, y.dtype)        # (the gradient of the pre-norm tensor is stored like the tensor)
-        defer_b = DIRECT_PARAM_GRADS and ctx.needs_input_grad[2] and slot_b is not None
-        part2 = _persistent_buffer(b_p, "_pulpo_dbias_part", nblk * Cout, zero=False) if defer_b else None
-        if defer_b and _pending_src(part2):          # this unit has already run a backward pass in this step: its partials are still waiting
-            defer_b = False                          # for flush_param_grads() - this pass takes the immediate path into the same slot
-        if not defer_b:
-            part2 = torch.empty(nblk * Cout, device=dev, dtype=torch.float32)
-        t0 = _hbm_begin("bn_lrelu_bwd_apply_heads" if heads_src is not None else "bn_lrelu_bwd_apply")
-        if heads_src is not None:
-            if blocked:
-                lib.call("pulpo_bn_lrelu_bwd_apply_heads_kb_t", _ptr(y), y.stride(4), _ptr(coef), _ptr(totd), LRELU_SLOPE, *heads_src, _ptr(dy.buf), dy.ps, dy.kb,
-                         _ptr(part2), nout, B, V, Cout, _stream())
-            else:
-                lib.call("pulpo_bn_lrelu_bwd_apply_heads_t", _ptr(y), y.stride(4), _ptr(coef), _ptr(totd), LRELU_SLOPE, *heads_src, _ptr(dy), dy.stride(4),
-                         _ptr(part2), nout, B, V, Cout, _stream())
-            _hbm_end(t0, "bn_lrelu_bwd_apply_heads", npix * (8.0 * Cout + 4.0 * (15 if nout == 6 else 3)))      # read y and the head's planar operands; write dy
-        elif pooled_src is not None:
-            gp, gz = pooled_src
-            if blocked:
-                lib.call("pulpo_bn_lrelu_bwd_apply_pooled_kb_t", _ptr(gp), gp.stride(4), _ptr(gz), grid_strides(gz)[1] if gz is not None else 0, _dt(gp), _ptr(y),
-                         y.stride(4), _ptr(coef), _ptr(totd), _ptr(dy.buf), dy.ps, dy.kb, LRELU_SLOPE, _ptr(part2), B, D, H, W, Cout, _stream())
-            else:
-                lib.call("pulpo_bn_lrelu_bwd_apply_pooled_t", _ptr(gp), gp.stride(4), _ptr(gz), grid_strides(gz)[1] if gz is not None else 0, _dt(gp), _ptr(y), _dt(y),
-                         y.stride(4), _ptr(coef), _ptr(totd), _ptr(dy), dy.stride(4), LRELU_SLOPE, _ptr(part2), B, D, H, W, Cout, _stream())
-            _hbm_end(t0, "bn_lrelu_bwd_apply", Cout * (_esize(gp) * (gp.numel() // Cout + (npix if gz is not None else 0)) + 2 * _esize(y) * npix))
-        else:
-            if blocked or dz_blk:
-                dzs = (8, npix * 8) if dz_blk else (dz.stride(4), 8)
-                dys = (_ptr(dy.buf), dy.ps, dy.kb) if blocked else (_ptr(dy), dy.stride(4), 8)
-                lib.call("pulpo_bn_lrelu_bwd_apply_kb_t", _ptr(dz), _dt(dz), *dzs, _ptr(y), y.stride(4), _ptr(coef), _ptr(totd), *dys, npix, Cout, LRELU_SLOPE,
-                         _ptr(part2), _stream())
-            else:
-                lib.call("pulpo_bn_lrelu_bwd_apply_t", _ptr(dz), _dt(dz), dz.stride(4), _ptr(y), _dt(y), y.stride(4), _ptr(coef), _ptr(totd), _ptr(dy), dy.stride(4),
-                         npix, Cout, LRELU_SLOPE, _ptr(part2), _stream())
-            _hbm_end(t0, "bn_lrelu_bwd_apply", (_esize(dz) + 2 * _esize(y)) * Cout * npix)                # read dz, y; write dy
-        defer_w = ctx.needs_input_grad[1] and slot_w is not None and ASYNC_WGRAD_STREAM is not None
-        if defer_b:
-            _PENDING_GRAD_JOBS.append((part2.data_ptr(), slot_b.data_ptr(), 1, nblk, Cout, 0))
-            _PENDING_KEEPALIVE.append(part2)
-        dbias = _colsum(part2, nblk, Cout, into=slot_b) if (ctx.needs_input_grad[2] and not defer_b) else None
-        dbeta, dgamma = (None, None) if direct_bn else (tot[:Cout], tot[Cout:])
-        if win is not None and ctx.needs_input_grad[1] and slot_w is not None and not defer_w:
-            win.wgrad(x, dy, Cin, Cout, slot_w, w_p)             # in line, held back for the coarse window, or on its side stream
-            dw = None
-        else:
-            dw = _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=w_p if slot_w is not None else None) if (ctx.needs_input_grad[1] and not defer_w) else None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            # (the bf16-operand kernel takes operand and result in one storage type; every other kernel is fp32)
-            dyc = dy if (wpt._pulpo_algo == "bf16" or dy.dtype == torch.float32) else dy.float()
-            dx_blk = ctx.dx_blocked and wpt._pulpo_algo == "wino3" and dyc.dtype == torch.float32
-            if dx_blk:                                   # the input was a blocked activation: its gradient in the same layout, straight from the kernel
-                dx = torch.empty((Cin // 8, B, D, H, W, 8), device=dev, dtype=torch.float32)
-            elif is_blocked(x) or not (x.is_contiguous() and Cin <= 3):
-                dx = new_cl(B, Cin, D, H, W, dev, dyc.dtype)
-            else:
-                dx = torch.empty_like(x, dtype=dyc.dtype)
-            if not _dgrad_with_bn_reduction(ctx.bn_src, x, dyc, wpt, dx, Cout, Cin):
-                _conv_raw(dyc, wpt, None, dx, Cout, Cin, None)
-            if ctx.dx_blocked and not dx_blk:
-                dx = cl_to_blocked(dx.float())
-        if defer_w:
-            _wgrad_on_side_stream(x, dy, Cin, Cout, slot_w, w_p)
-        return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, head_dw, head_db, None, None, None
+    if COARSE_WINDOW is not None:                # (the window opens between the two passes: what it held back is queued behind this unit's first pass)
+        COARSE_WINDOW.visit(D * H * W)
+    slot_w, slot_b, slot_g, slot_be = (_grad_slot(t) if need else None for t, need in zip(params, needs[1:5]))
+    direct_bn = slot_g is not None and slot_be is not None
+    tot = None if direct_bn else torch.empty(2 * Cout, device=dev, dtype=torch.float32)           # dbeta | dgamma
+    totd = torch.empty(2 * Cout, device=dev, dtype=torch.float64)          # mean(dbn) | mean(dbn * xhat), kept in double
+    # eval-mode BatchNorm is a fixed affine map (dy = scale * dbn): the batch means do not enter
+    fin_out = (_ptr(slot_be if direct_bn else tot), _ptr(slot_g) if direct_bn else ctypes.c_void_p(tot.data_ptr() + 4 * Cout), int(direct_bn), _ptr(totd))
+    nsd = lib.query("pulpo_bn_bwd_finalize_scratch_doubles", nrow, Cout)
+    scratch = torch.empty(nsd, device=dev, dtype=torch.float64) if nsd else None
+    lib.call("pulpo_bn_bwd_finalize", _ptr(rows), nrow, Cout, _ptr(coef), float(npix), int(training), *fin_out, _ptr(scratch), _stream())
+    dbeta, dgamma = (None, None) if direct_bn else (tot[:Cout], tot[Cout:])
+    return src, totd, slot_w, slot_b, dgamma, dbeta, head_dw, head_db
 
 
-def _backward_input_layer(ctx, dz, x, weight, y, coef, totd, tot, direct_bn, slots, params):
-    slot_w, slot_b = slots
-    w_p, b_p = params
-    B, Cin, D, H, W = x.shape
-    Cout = weight.shape[0]
+def _dbias_rows(b_p, slot_b, need_db: bool, name: str, nrow: int, Cout: int, dev):
+    """the [nrow][Cout] partial rows a kernel leaves the conv-bias gradient in -> (rows, deferred?)"""
+    rows = _persistent_buffer(b_p, name, nrow * Cout, zero=False) if (DIRECT_PARAM_GRADS and need_db and slot_b is not None) else None
+    # (inside the stepper: the parameter's persistent buffer, summed by flush_param_grads() - unless this unit has already run a backward pass
+    #  in this step and its partials are still waiting there: this pass then takes the immediate path into the same slot)
+    if rows is None or _pending_src(rows):
+        return torch.empty(nrow * Cout, device=dev, dtype=torch.float32), False
+    return rows, True
+
+
+def _finish_dbias(rows, defer_b: bool, need_db: bool, slot_b, nrow: int, Cout: int):
+    if defer_b:
+        _defer_grad_job(rows, slot_b, 1, nrow, Cout, 0)
+        return None
+    return _colsum(rows, nrow, Cout, into=slot_b) if need_db else None
+
+
+def _bn_apply_entry(src: _DzSource, blocked: bool, dy, y, coef, totd, rows, dims):
+    # -> (entry point, arguments, trace name, bytes moved)
+    B, _, Cout, D, H, W = dims
+    npix = B * D * H * W
+    dyo = (_ptr(dy.buf), dy.ps, dy.kb) if blocked else (_ptr(dy), dy.stride(4))
+    kb = "_kb" if blocked else ""
+    ydt = () if blocked else (_dt(y),)           # (the *_kb entries are fp32 only)
+    if src.head is not None:
+        nout = src.head[0]
+        return (f"pulpo_bn_lrelu_bwd_apply_heads{kb}_t", (_ptr(y), y.stride(4), _ptr(coef), _ptr(totd), LRELU_SLOPE, *src.head[1], *dyo, _ptr(rows), nout,
+                                                         B, D * H * W, Cout),
+                "bn_lrelu_bwd_apply_heads", npix * (8.0 * Cout + 4.0 * (15 if nout == 6 else 3)))       # read y and the head's planar operands; write dy
+    if src.pooled is not None:
+        gp, gz = src.pooled
+        return (f"pulpo_bn_lrelu_bwd_apply_pooled{kb}_t", (_ptr(gp), gp.stride(4), _ptr(gz), grid_strides(gz)[1] if gz is not None else 0, _dt(gp), _ptr(y), *ydt,
+                                                          y.stride(4), _ptr(coef), _ptr(totd), *dyo, LRELU_SLOPE, _ptr(rows), B, D, H, W, Cout),
+                "bn_lrelu_bwd_apply", Cout * (_esize(gp) * (gp.numel() // Cout + (npix if gz is not None else 0)) + 2 * _esize(y) * npix))
+    dz = src.dz
+    nbytes = (_esize(dz) + 2 * _esize(y)) * Cout * npix                # read dz, y; write dy
+    if blocked or src.blk:                       # (either side blocked: the entry that takes a block stride for both)
+        dzs = (8, npix * 8) if src.blk else (dz.stride(4), 8)
+        return ("pulpo_bn_lrelu_bwd_apply_kb_t", (_ptr(dz), _dt(dz), *dzs, _ptr(y), y.stride(4), _ptr(coef), _ptr(totd), *(dyo if blocked else (*dyo, 8)), npix, Cout,
+                                                  LRELU_SLOPE, _ptr(rows)), "bn_lrelu_bwd_apply", nbytes)
+    return ("pulpo_bn_lrelu_bwd_apply_t", (_ptr(dz), _dt(dz), dz.stride(4), _ptr(y), _dt(y), y.stride(4), _ptr(coef), _ptr(totd), *dyo, npix, Cout, LRELU_SLOPE,
+                                           _ptr(rows)), "bn_lrelu_bwd_apply", nbytes)
+
+
+def _bwd_bn_apply(src: _DzSource, x, weight, y, coef, totd, wpt, dims, nblk: int, needs, b_p, slot_b):
+    # -> (dy, (bias rows, their count, deferred?)), or (None, None): the input layer
+    B, Cin, Cout, D, H, W = dims
+    need_dx, need_dw, need_db = needs
+    dev = y.device
+    dz_rows4 = src.dz is None or src.blk or _cl_rows4(src.dz)
+    # The input layer (image pair -> 32 channels at full resolution): nobody asks for its data gradient, so dy has ONE reader - the weight
+    # gradient, which then forms it per element while staging (pulpo_conv3d_k3_wgrad_bn) instead of a pass that reads dz and y and writes dy
+    # (0.29 ms at 160^3 x 32 channels).
+    if (FUSE_INPUT_WGRAD and src.dz is not None and Cin <= 2 and not need_dx and need_dw and not DETERMINISTIC and y.dtype == torch.float32
+            and Cout % 4 == 0 and _cl_rows4(y) and dz_rows4 and x.dtype == torch.float32):
+        return None, None
+    blocked = _blocked_dy_ok(x, y, weight, wpt, need_dx, need_dw) and dz_rows4 and _cl_rows4(y)
+    if blocked:
+        global BLOCKED_DY_HITS
+        BLOCKED_DY_HITS += 1
+        dy = _BlockedGrad(B, Cout, D, H, W, dev)
+    else:
+        dy = new_cl(B, Cout, D, H, W, dev, y.dtype)        # (the gradient of the pre-norm tensor is stored like the tensor)
+    rows, defer_b = _dbias_rows(b_p, slot_b, need_db, "_pulpo_dbias_part", nblk, Cout, dev)
+    entry, args, tname, nbytes = _bn_apply_entry(src, blocked, dy, y, coef, totd, rows, dims)
+    t0 = _hbm_begin(tname)
+    lib.call(entry, *args, _stream())
+    _hbm_end(t0, tname, nbytes)
+    return dy, (rows, nblk, defer_b)
+
+
+def _input_layer_param_grads(dz, x, y, coef, totd, dims, need_db: bool, params, slot_w, slot_b):
+    # -> (dw, dbias)
+    B, Cin, Cout, D, H, W = dims
+    w_p, b_p = params[:2]
     dev = x.device
     nrow = lib.query("pulpo_conv3d_k3_wgrad_bn_rows", B, D, H, W, Cout)
-    defer_b = DIRECT_PARAM_GRADS and ctx.needs_input_grad[2] and slot_b is not None
-    part2 = _persistent_buffer(b_p, "_pulpo_dbias_part_in", nrow * Cout, zero=False) if defer_b else None
-    if defer_b and _pending_src(part2):
-        defer_b = False
-    if not defer_b:
-        part2 = torch.empty(nrow * Cout, device=dev, dtype=torch.float32)
-    deferred = slot_w is not None and w_p is not None
-    dw = slot_w if slot_w is not None else torch.empty((Cout, Cin, 3, 3, 3), device=dev, dtype=torch.float32)
-    nscr = lib.query("pulpo_conv3d_k3_wgrad_scratch_floats", Cin, Cout)
-    scratch = _persistent_buffer(w_p, "_pulpo_wgrad_scratch", nscr, zero=True) if deferred else torch.empty(nscr, device=dev, dtype=torch.float32)
+    rows, defer_b = _dbias_rows(b_p, slot_b, need_db, "_pulpo_dbias_part_in", nrow, Cout, dev)
+    dw, mode, scratch, deferred = _wgrad_target(Cin, Cout, slot_w, w_p, dev)
     xb, xp, xc = grid_strides(x)
+    if is_blocked(dz):                           # (the gradient of a blocked activation: the next unit's data-gradient kernel wrote it that way)
+        entry, dzo = "pulpo_conv3d_k3_wgrad_bn_kb", (_ptr(dz), D * H * W * 8, 8, B * D * H * W * 8)
+    else:
+        entry, dzo = "pulpo_conv3d_k3_wgrad_bn", (_ptr(dz), _dt(dz), dz.stride(0), dz.stride(4))
 
     def launch():
         t0 = _trace_begin()
-        if is_blocked(dz):                           # (the gradient of a blocked activation: the next unit's data-gradient kernel wrote it that way)
-            lib.call("pulpo_conv3d_k3_wgrad_bn_kb", _ptr(x), xb, xp, xc, _ptr(dz), D * H * W * 8, 8, B * D * H * W * 8, _ptr(y), y.stride(0), y.stride(4), _ptr(coef),
-                     _ptr(totd), LRELU_SLOPE, _ptr(dw), 2 if deferred else int(slot_w is not None), _ptr(scratch), _ptr(part2), B, D, H, W, Cin, Cout, _stream())
-        else:
-            lib.call("pulpo_conv3d_k3_wgrad_bn", _ptr(x), xb, xp, xc, _ptr(dz), _dt(dz), dz.stride(0), dz.stride(4), _ptr(y), y.stride(0), y.stride(4), _ptr(coef),
-                     _ptr(totd), LRELU_SLOPE, _ptr(dw), 2 if deferred else int(slot_w is not None), _ptr(scratch), _ptr(part2), B, D, H, W, Cin, Cout, _stream())
+        lib.call(entry, _ptr(x), xb, xp, xc, *dzo, _ptr(y), y.stride(0), y.stride(4), _ptr(coef), _ptr(totd), LRELU_SLOPE, _ptr(dw), mode, _ptr(scratch),
+                 _ptr(rows), B, D, H, W, Cin, Cout, _stream())
         _trace_end(t0, "conv3d_k3_wgrad_smallc(+bn backward)" + ("" if deferred else "(+memset,unpack)"), 54.0 * Cin * Cout * B * D * H * W,
                    (4.0 * Cin + (_esize(dz) + 4.0) * Cout) * B * D * H * W)
 
-    side = ASYNC_WGRAD_STREAM
-    if side is not None and deferred:
-        main = torch.cuda.current_stream()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            launch()
-        for t in (x, dz, y, coef, totd):
-            t.record_stream(side)
+    if ASYNC_WGRAD_STREAM is not None and deferred:
+        _on_side_stream(launch, (x, dz, y, coef, totd))
     else:
         launch()
-    if deferred and not _pending_src(scratch):
-        _PENDING_GRAD_JOBS.append((scratch.data_ptr(), dw.data_ptr(), 0, Cin, Cout, (Cout + 63) // 64 * 64))
-        _PENDING_KEEPALIVE.append(scratch)
-    if defer_b:
-        _PENDING_GRAD_JOBS.append((part2.data_ptr(), slot_b.data_ptr(), 1, nrow, Cout, 0))
-        _PENDING_KEEPALIVE.append(part2)
-    dbias = _colsum(part2, nrow, Cout, into=slot_b) if (ctx.needs_input_grad[2] and not defer_b) else None
-    dbeta, dgamma = (None, None) if direct_bn else (tot[:Cout], tot[Cout:])
-    return (None, (None if slot_w is not None else dw), dbias, dgamma, dbeta) + (None,) * 15
+    if deferred and not _pending_src(scratch):       # (one finishing job per scratch, as in _wgrad_raw)
+        _defer_grad_job(scratch, dw, 0, Cin, Cout, (Cout + 63) // 64 * 64)
+    return (None if slot_w is not None else dw), _finish_dbias(rows, defer_b, need_db, slot_b, nrow, Cout)
 
 
-_ConvBNLReLU._backward_input_layer = staticmethod(_backward_input_layer)
-FUSE_INPUT_WGRAD = os.environ.get("PULPO_FUSE_INPUT_WGRAD", "1") != "0"
-# the gradient of a pooled ConvUnit output formed inside both BatchNorm-backward passes instead of written (A/B switch: "0" materialises it)
-POOLED_BN_BACKWARD = os.environ.get("PULPO_POOLED_BN_BACKWARD", "1") != "0"
+def _bwd_param_grads(src: _DzSource, x, dy, bias_rows, y, coef, totd, dims, needs, params, slot_w, slot_b):
+    # -> (dw, dbias, side-stream job or None)
+    _, Cin, Cout, _, _, _ = dims
+    need_dw, need_db = needs
+    if dy is None:
+        return (*_input_layer_param_grads(src.dz, x, y, coef, totd, dims, need_db, params, slot_w, slot_b), None)
+    rows, nrow, defer_b = bias_rows
+    dbias = _finish_dbias(rows, defer_b, need_db, slot_b, nrow, Cout)
+    if not need_dw:
+        return None, dbias, None
+    w_p = params[0]
+    if slot_w is not None and ASYNC_WGRAD_STREAM is not None:
+        return None, dbias, (x, dy, Cin, Cout, slot_w, w_p)
+    if slot_w is not None and COARSE_WINDOW is not None:
+        COARSE_WINDOW.wgrad(x, dy, Cin, Cout, slot_w, w_p)
+        return None, dbias, None
+    return _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=w_p if slot_w is not None else None), dbias, None
+
+
+def _bwd_data_grad(x, dy, wpt, bn_src, dx_blocked: bool, dims, side_job):
+    # -> dx (wpt, the packed data-gradient weights, is None where x asks for none)
+    B, Cin, Cout, D, H, W = dims
+    dx = None
+    if wpt is not None:
+        # (the bf16-operand kernel takes operand and result in one storage type; every other kernel is fp32)
+        dyc = dy if (wpt._pulpo_algo == "bf16" or dy.dtype == torch.float32) else dy.float()
+        dx_blk = dx_blocked and wpt._pulpo_algo == "wino3" and dyc.dtype == torch.float32
+        if dx_blk:                                   # the input was a blocked activation: its gradient in the same layout, straight from the kernel
+            dx = torch.empty((Cin // 8, B, D, H, W, 8), device=x.device, dtype=torch.float32)
+        elif is_blocked(x) or not (x.is_contiguous() and Cin <= 3):
+            dx = new_cl(B, Cin, D, H, W, x.device, dyc.dtype)
+        else:
+            dx = torch.empty_like(x, dtype=dyc.dtype)
+        if not _dgrad_with_bn_reduction(bn_src, x, dyc, wpt, dx, Cout, Cin):
+            _conv_raw(dyc, wpt, None, dx, Cout, Cin, None)
+        if dx_blocked and not dx_blk:
+            dx = cl_to_blocked(dx.float())
+    if side_job is not None:
+        _wgrad_on_side_stream(*side_job)
+    return dx
 
 
 def conv_bn_lrelu(x, weight, bias, gamma, beta, running_mean, running_var, training=True, momentum=0.1, eps=1e-5, num_batches_tracked=None,
@@ -1307,42 +1393,33 @@ def conv_bn_lrelu(x, weight, bias, gamma, beta, running_mean, running_var, train
     if _is2d(x):
         return conv_bn_lrelu(_lift(x), _lift_w3(weight), bias, gamma, beta, running_mean, running_var, training, momentum, eps,
                              num_batches_tracked).squeeze(2)
-    _TLS.out_slot = out
     src = getattr(x, "_pulpo_bn_src", None)          # x is the untouched output of another ConvUnit: (y, coef, version at production)
     bn_src = src[:2] if (src is not None and src[2] == x._version and training and torch.is_grad_enabled()) else None
     # pool_only (with pool_after): the caller reads ONLY AvgPool(result) - where the fused pass is available the un-pooled tensor is not written and
     # the call returns (None, pooled); otherwise (result, None) as without the flag
-    want_tuple = bool(pool_only)
-    pool_only = bool(pool_only and pool_after and training and torch.is_grad_enabled())
-    _TLS.pool_only_done = False
-    z = _ConvBNLReLU.apply(x, weight, bias, gamma, beta, running_mean, running_var, num_batches_tracked, bool(training), float(momentum),
-                           float(eps), bn_src, bool(pool_after), pool_only, bool(blocked_out), None, None, None, 0, None)
+    call = _UnitCall(bn_src=bn_src, out=out, pool_after=pool_after, pool_only=pool_only and pool_after and training and torch.is_grad_enabled(),
+                     blocked_out=blocked_out, training=bool(training), momentum=float(momentum), eps=float(eps), running_mean=running_mean,
+                     running_var=running_var, num_batches_tracked=num_batches_tracked)
+    z = _ConvBNLReLU.apply(x, weight, bias, gamma, beta, None, None, call)
+    if call.pool_only_done:                              # the pooled tensor alone came back
+        return None, z
     pooled_out = None
     if isinstance(z, tuple):
         z, pooled_out = z
-    elif getattr(_TLS, "pool_only_done", False):         # the pooled tensor alone came back
-        _TLS.produced = None
-        _TLS.out_slot = None
-        _TLS.pool_only_done = False
-        return None, z
-    produced = getattr(_TLS, "produced", None)
-    _TLS.produced = None
-    _TLS.out_slot = None
-    if produced is not None:
-        z._pulpo_bn_src = (produced[0], produced[1], z._version)
+    if call.y is not None:
+        z._pulpo_bn_src = (call.y, call.coef, z._version)
         if pooled_out is not None:
             z._pulpo_pooled = (pooled_out, z._version, True)      # (an output of the same autograd node: avg_pool2_skip hands it out as it is)
     if out is not None and z.dim() == 5 and z.data_ptr() == out[0].data_ptr() + out[0].element_size() * out[1] and z.stride() == out[0].stride():
         z._pulpo_cat = (out[0], out[1])
-    return (z, None) if want_tuple else z
+    return (z, None) if pool_only else z
 
 
 # ---- ConvUnit + 1x1x1 head in one node.  The last ConvUnit in front of a head (PULPoEncoder.sample_merge_block -> mu_sigma, VelocityField's last
 # unit -> its 1x1x1 convolution) produces an activation that only the head reads, and the head returns a gradient that only this unit's BatchNorm
 # backward reads: the head kernels take the pre-norm tensor and the coefficient block and form both per element (pulpo_heads_fwd_bn_t,
 # pulpo_heads_bwd_bn_t, pulpo_bn_lrelu_bwd_apply_heads_t) - ten passes over a C-channel tensor become four, two tensors and two launches per head go.
-# PULPO_FUSE_HEAD_BN=0: the separate passes (A/B switch).
-FUSE_HEAD_BN = os.environ.get("PULPO_FUSE_HEAD_BN", "1") != "0"
+# ops.FUSE_HEAD_BN = False: the separate passes.
 HEAD_BN_HITS = 0                 # heads that ran on the pre-norm tensor so far (tests look at it)
 
 
@@ -1356,11 +1433,11 @@ def _conv_bn_lrelu_heads(x, unit_args, momentum, eps, Wt, hbias, heps, nout, hpa
     global HEAD_BN_HITS
     HEAD_BN_HITS += 1
     weight, bias, gamma, beta, running_mean, running_var, num_batches_tracked = unit_args
-    _TLS.out_slot = None
     src = getattr(x, "_pulpo_bn_src", None)
     bn_src = src[:2] if (src is not None and src[2] == x._version and torch.is_grad_enabled()) else None
-    return _ConvBNLReLU.apply(x, weight, bias, gamma, beta, running_mean, running_var, num_batches_tracked, True, float(momentum), float(eps), bn_src,
-                              False, False, False, Wt, hbias, heps, nout, hparams)
+    call = _UnitCall(bn_src=bn_src, training=True, momentum=float(momentum), eps=float(eps), running_mean=running_mean, running_var=running_var,
+                     num_batches_tracked=num_batches_tracked, head_nout=nout, head_eps=heps, head_params=hparams)
+    return _ConvBNLReLU.apply(x, weight, bias, gamma, beta, Wt, hbias, call)
 
 
 def conv_bn_lrelu_mu_sigma(x, unit_args, momentum, eps, w_mu, b_mu, w_sigma, b_sigma, noise):
@@ -1484,8 +1561,7 @@ def _heads_finish_rows(part, slots, params, nblk: int, nout: int, C: int):
         nw = len(params[0])
         for k, (sl, off, n) in enumerate(slots):
             col0, ncol = (off * C, n * C) if k < nw else (nout * C + off, n)
-            _PENDING_GRAD_JOBS.append((part.data_ptr() + 4 * col0, sl.data_ptr(), 1, nblk, ncol, rowlen))
-        _PENDING_KEEPALIVE.append(part)
+            _defer_grad_job(part, sl, 1, nblk, ncol, rowlen, byte_offset=4 * col0)
         return None, None
     tot = _colsum(part, nblk, rowlen)
     return tot[: nout * C].view(nout, C), tot[nout * C:]
@@ -1606,12 +1682,12 @@ class _AvgPool2Skip(torch.autograd.Function):
         grp = 4 * int(_esize(g))                      # bytes of a four-channel group
         skip_ok = False
         if gskip is not None:
-            sb, sp, sc = grid_strides(gskip)
-            skip_ok = _dense_grid(gskip) and sc == 1 and sb == D * H * W * sp and C > 1 and sp % 4 == 0 and gskip.data_ptr() % grp == 0
-        if ctx.bn is not None and C % 4 == 0 and C // 4 <= 256 and (gskip is None or skip_ok) and g.stride(4) % 4 == 0 and g.data_ptr() % grp == 0:
+            sb, sp, _ = grid_strides(gskip)
+            skip_ok = _dense_grid(gskip) and sb == D * H * W * sp and C > 1 and _vec4(gskip, align=grp, batch=False)
+        if ctx.bn is not None and C // 4 <= 256 and (gskip is None or skip_ok) and _vec4(g, C, align=grp, batch=False):
             # the producing ConvUnit's first BatchNorm-backward pass rides along: this kernel has every element of its gradient in registers
             y, coef = ctx.bn
-            if tuple(y.shape) == (B, C, D, H, W) and y.stride(1) == 1 and y.stride(4) % 4 == 0 and y.data_ptr() % (4 * int(_esize(y))) == 0 and _dense_grid(y):
+            if tuple(y.shape) == (B, C, D, H, W) and _vec4(y, align=4 * int(_esize(y)), batch=False) and _dense_grid(y):
                 nblk = lib.query("pulpo_bn_bwd_blocks", B * D * H * W, C)
                 part = torch.empty(nblk * 2 * C, device=g.device, dtype=torch.float32)
                 t0 = _hbm_begin("avgpool2_bwd_bnred")
@@ -1621,13 +1697,11 @@ class _AvgPool2Skip(torch.autograd.Function):
                 _hbm_end(t0, "avgpool2_bwd_bnred", C * (_esize(g) * (g.numel() // C + (2 if gskip is not None else 1) * B * D * H * W) + _esize(y) * B * D * H * W))
                 _BN_TILE_PARTS[y.data_ptr()] = (part, nblk, coef.data_ptr(), gin.data_ptr(), gin._version, tuple(gin.shape), tuple(gin.stride()))
                 return gin, None, None, None
-        if skip_ok:
-            t0 = _hbm_begin("avgpool2_bwd_add")
-            lib.call("pulpo_avgpool2_bwd_t", _ptr(g), g.stride(4), _ptr(gskip), grid_strides(gskip)[1], _ptr(gin), gin.stride(4), _dt(g), B, D, H, W, C, _stream())
-            _hbm_end(t0, "avgpool2_bwd_add", _esize(g) * C * (g.numel() // C + 2 * B * D * H * W))
-            return gin, None, None, None
-        lib.call("pulpo_avgpool2_bwd_t", _ptr(g), g.stride(4), None, 0, _ptr(gin), gin.stride(4), _dt(g), B, D, H, W, C, _stream())
-        return (gin if gskip is None else gskip + gin), None, None, None
+        t0 = _hbm_begin("avgpool2_bwd_add") if skip_ok else None
+        lib.call("pulpo_avgpool2_bwd_t", _ptr(g), g.stride(4), _ptr(gskip) if skip_ok else None, grid_strides(gskip)[1] if skip_ok else 0, _ptr(gin), gin.stride(4),
+                 _dt(g), B, D, H, W, C, _stream())
+        _hbm_end(t0, "avgpool2_bwd_add", _esize(g) * C * (g.numel() // C + 2 * B * D * H * W))
+        return (gin if (skip_ok or gskip is None) else gskip + gin), None, None, None
 
 
 def avg_pool2_skip(x):
