@@ -309,7 +309,8 @@ class Step:
 OUT_NAMES = ["mus", "sigmas", "samples", "velocity_fields", "individual_dfs", "combined_dfs", "final_dfs", "transformed"]
 
 
-def gen_step(name, T, L, size, n0, B, seed, with_grads=True, smooth=False, df_resolution="level_res", cp_depth=3):
+def gen_step(name, T, L, size, n0, B, seed, with_grads=True, smooth=False, df_resolution="level_res", cp_depth=3, keep=None):
+    """keep: a predicate on the array names - None stores everything (every fixture but the slice step, which has to stay a small file)"""
     st = Step(T, L, size, n0, seed, df_resolution, cp_depth)
     g = torch.Generator().manual_seed(seed + 2)
     if smooth:
@@ -360,6 +361,8 @@ def gen_step(name, T, L, size, n0, B, seed, with_grads=True, smooth=False, df_re
     for nme in ("individual_dfs", "final_dfs", "transformed"):
         d = outs_d[OUT_NAMES.index(nme)]
         out.update({f"det.{nme}.{l}": npy(v) for l, v in d.items()})
+    if keep is not None:
+        out = {k: v for k, v in out.items() if keep(k)}
     save(name, **out)
     return float(total)
 
@@ -587,6 +590,16 @@ def gen_2d():
     t = gen_step("step2d_T3L2_n4_32x24", T=3, L=2, size=[32, 24], n0=4, B=2, seed=210)
     print("   total loss", t)
 
+# --------------------------------------------------------------------------- 14. a 2-D step at a slice size that reaches the slice kernels
+def gen_slices():
+    """T = 4, L = 3 on 80x96 slices: large enough for the kernels a real slice runs (tests/test_gpu_slices.py asserts which), small enough to
+    stay below 1 MiB: n0 = 4 and one pair (the weights and their gradients at n0 = 8 alone are 1.2 MB), and of the eval / deterministic
+    forwards only the arrays the replay compares (losses, transformed images, individual fields)."""
+    drop = lambda k: (k.startswith("eval.") and k.split(".")[1] not in ("total", "kl", "rec", "reg", "transformed", "individual_dfs")) or k.startswith("det.final_dfs")
+    t = gen_step("step2d_T4L3_n4_80x96", T=4, L=3, size=[80, 96], n0=4, B=1, seed=220, keep=lambda k: not drop(k))
+    print("   total loss", t)
+
+
 # --------------------------------------------------------------------------- 15. the reference's own PULPo class (models.py), API level
 def _import_reference_models():
     """import /root/reference/src/models.py itself.  It needs pytorch_lightning and torchvision, which this image lacks: two stand-in
@@ -767,6 +780,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "2d":
         gen_2d()
+        raise SystemExit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "slices":
+        gen_slices()
         raise SystemExit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "evalmetrics":
         gen_evalmetrics()
