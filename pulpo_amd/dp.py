@@ -241,7 +241,7 @@ class DataParallelStepper:
         # freeze_gc: after the second step move everything alive to the garbage collector's permanent generation (see
         # _freeze_garbage_collector); None = the environment's PULPO_GC_FREEZE == "1" (off unless asked for)
         self.freeze_gc = (os.environ.get("PULPO_GC_FREEZE", "0") == "1") if freeze_gc is None else bool(freeze_gc)
-        # weight gradients on a second stream (ops.ASYNC_WGRAD_STREAM): overlaps them with the BatchNorm backward passes
+        # weight gradients on a second stream (the `side` of ops.backward_pass): overlaps them with the BatchNorm backward passes
         dev0 = next(model.parameters()).device
         self.async_wgrad = bool(async_wgrad) and dev0.type == "cuda" and os.environ.get("PULPO_ASYNC_WGRAD", "1") != "0"
         self._side = torch.cuda.Stream(device=dev0) if self.async_wgrad else None
@@ -314,31 +314,17 @@ class DataParallelStepper:
         DistributedDataParallel wrapper needs to see), everything else alike."""
         from . import ops
         self._works, self._launched = [], 0
-        ops._BN_TILE_PARTS.clear()                 # (BatchNorm-backward sums a data-gradient kernel left for a unit whose backward never ran)
-        ops.DIRECT_PARAM_GRADS = bool(direct)      # conv / BN backward kernels add straight into the arena's .grad views
-        ops.ASYNC_WGRAD_STREAM = self._side if (self.wgrad_on_side_stream() and direct) else None
-        ops.COARSE_WINDOW = self._window if (self.coarse_window() and direct) else None
-        if ops.COARSE_WINDOW is not None:
-            self._window.begin()
+        side = self._side if (self.wgrad_on_side_stream() and direct) else None
+        window = self._window if (self.coarse_window() and direct) else None
         self._in_backward = True
         try:
-            if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
-                self._one = torch.ones((), device=loss.device, dtype=loss.dtype)       # (backward() would fill a fresh one per step)
-            loss.backward(self._one)
-        except BaseException:
-            ops.reset_param_grad_buffers(self.model)        # deferred gradient sums of an interrupted backward pass are void
-            if self._window is not None:
-                self._window.held = []                      # (and so are the weight gradients still held back for the coarse window)
-            raise
+            with ops.backward_pass(direct, side, window, self.model):     # direct: the kernels add straight into the arena's .grad views
+                if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
+                    self._one = torch.ones((), device=loss.device, dtype=loss.dtype)       # (backward() would fill a fresh one per step)
+                loss.backward(self._one)
         finally:
             self._in_backward = False
             self._armed = False
-            ops.DIRECT_PARAM_GRADS = False
-            ops.join_async_wgrad()             # (also finishes the deferred weight / bias gradients in one launch)
-            ops.ASYNC_WGRAD_STREAM = None
-            if ops.COARSE_WINDOW is not None:
-                self._window.begin()           # (an interrupted pass: no operand stays referenced)
-            ops.COARSE_WINDOW = None
 
     def reduce_and_update(self, reduced_elsewhere: bool = False) -> None:
         """gradient exchange (what is left of it) + fused Adam.  reduced_elsewhere: a DistributedDataParallel wrapper has already averaged

@@ -9,9 +9,10 @@ wider buffer; 1- and 3-channel images / fields are plain contiguous (N,C,D,H,W) 
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -134,14 +135,54 @@ def _colsum(partials: torch.Tensor, nrow: int, ncol: int, scale: float = 1.0, in
     return out
 
 
-# When True (set by dp.DataParallelStepper, which always drives autograd through .backward() on arena-backed parameters),
-# the conv / BatchNorm backward kernels add parameter gradients straight into the parameters' existing .grad storage and
-# hand `None` to autograd: no per-parameter temporary, no AccumulateGrad add kernel (~170 tiny launches per step).
-DIRECT_PARAM_GRADS = False
+class _BackwardPass:
+    """what lives as long as one backward pass.  direct: the conv / BatchNorm backward kernels add parameter gradients straight into the parameters'
+    existing .grad storage and hand `None` to autograd (no per-parameter temporary, no AccumulateGrad add kernel: ~170 tiny launches per step);
+    side, window: the weight gradients' stream (_on_side_stream) and the CoarseWindow, None = in line; jobs, keep: the finishing jobs (src ptr, dst
+    ptr, kind, a, b, c) pending for flush_param_grads() and the buffers they read; bn_parts: see _dgrad_with_bn_reduction"""
+    __slots__ = ("direct", "side", "window", "jobs", "keep", "bn_parts")
+
+    def __init__(self, direct: bool = False, side=None, window=None):
+        self.direct, self.side, self.window = bool(direct), side, window
+        self.jobs, self.keep, self.bn_parts = [], [], {}
+
+
+# The current pass: a module global, not a thread-local, because autograd runs a device's backward functions on its own thread.  The default one
+# serves plain autograd use (gradients are returned to autograd on the caller's stream); backward_pass() installs dp.DataParallelStepper's.
+# (bench.py's all-ranks-failed fallback still assigns ops.ASYNC_WGRAD_STREAM / ops.DIRECT_PARAM_GRADS: attributes nobody reads, the pass is over by then)
+_DEFAULT_PASS = _PASS = _BackwardPass()
+
+
+@contextlib.contextmanager
+def backward_pass(direct: bool, side=None, window=None, module: Optional[torch.nn.Module] = None):
+    """install a pass of its own around one backward pass (the only way to).  Its exit, normal or not, joins the side stream and the window and
+    finishes the deferred parameter gradients in one launch; after an exception it first drops them, with `module`'s persistent scratch."""
+    global _PASS
+    if _PASS is not _DEFAULT_PASS:
+        raise PulpoHipError("backward_pass(): another backward pass is installed (passes neither nest nor run concurrently from two threads)")
+    _DEFAULT_PASS.bn_parts.clear()               # (sums left for a unit whose backward never ran)
+    _PASS = bp = _BackwardPass(direct, side, window)
+    if window is not None:
+        window.begin()
+    try:
+        yield bp
+    except BaseException:
+        reset_param_grad_buffers(module)         # deferred gradient sums of an interrupted backward pass are void
+        if window is not None:
+            window.held = []                     # (and so are the weight gradients still held back for the coarse window)
+        raise
+    finally:
+        bp.direct = False
+        try:
+            join_async_wgrad()                   # (also finishes the deferred weight / bias gradients in one launch)
+            if window is not None:
+                window.begin()                   # (an interrupted pass: no operand stays referenced)
+        finally:
+            _PASS = _DEFAULT_PASS
 
 
 def _grad_slot(p: torch.Tensor) -> Optional[torch.Tensor]:
-    if not DIRECT_PARAM_GRADS or not p.is_leaf:         # (lifted 2-D weights are derived tensors: their gradient goes through autograd)
+    if not _PASS.direct or not p.is_leaf:         # (lifted 2-D weights are derived tensors: their gradient goes through autograd)
         return None
     g = getattr(p, "grad", None)
     if g is None or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
@@ -489,9 +530,7 @@ def _conv_raw(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], o
 # the conv-bias gradients in their BatchNorm-backward partials until flush_param_grads() finishes ALL of them with one launch
 # (pulpo_grad_finish_multi) - instead of a memset + an unpack + a column-sum launch per layer, each of which has to find room on CUs the
 # persistent convolution kernels hold.  The scratch buffers persist on the parameter (they are returned all zero by the finishing kernel).
-_PENDING_GRAD_JOBS: List[Tuple[int, int, int, int, int, int]] = []      # (src ptr, dst ptr, kind, a, b, c)
-_PENDING_KEEPALIVE: List[torch.Tensor] = []
-_JOB_TABLES: dict = {}
+_JOB_TABLES: dict = {}                           # (the device copies of recent job lists: a process-wide cache keyed by pointers, not pass state)
 
 
 def _persistent_buffer(owner: torch.Tensor, name: str, numel: int, zero: bool) -> torch.Tensor:
@@ -506,40 +545,40 @@ def _persistent_buffer(owner: torch.Tensor, name: str, numel: int, zero: bool) -
 # (row length c, 0 = b) of `buf`, from `byte_offset` on, to `dst`
 def _defer_grad_job(buf: torch.Tensor, dst: torch.Tensor, kind: int, a: int, b: int, c: int, byte_offset: int = 0) -> None:
     """queue one finishing job for flush_param_grads() and keep its source buffer alive until then"""
-    _PENDING_GRAD_JOBS.append((buf.data_ptr() + byte_offset, dst.data_ptr(), kind, a, b, c))
-    if not (_PENDING_KEEPALIVE and _PENDING_KEEPALIVE[-1] is buf):
-        _PENDING_KEEPALIVE.append(buf)
+    _PASS.jobs.append((buf.data_ptr() + byte_offset, dst.data_ptr(), kind, a, b, c))
+    if not (_PASS.keep and _PASS.keep[-1] is buf):
+        _PASS.keep.append(buf)
 
 
 def _pending_src(buf: torch.Tensor) -> bool:
     """is this persistent buffer already the source of a deferred job of the current step?"""
     p_ = buf.data_ptr()
-    return any(job[0] == p_ for job in _PENDING_GRAD_JOBS)
+    return any(job[0] == p_ for job in _PASS.jobs)
 
 
 def flush_param_grads() -> None:
     """finish every deferred weight / bias gradient on the current stream (callers have joined the weight-gradient stream first)"""
-    if not _PENDING_GRAD_JOBS:
+    bp = _PASS
+    if not bp.jobs:
         return
-    key = tuple(_PENDING_GRAD_JOBS)
+    key = tuple(bp.jobs)
     table = _JOB_TABLES.get(key)
     if table is None:
         import struct
         raw = b"".join(struct.pack("<QQiiii", *job) for job in key)
-        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(_PENDING_KEEPALIVE[0].device)
+        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(bp.keep[0].device)
         if len(_JOB_TABLES) > 8:
             _JOB_TABLES.clear()
         _JOB_TABLES[key] = table
     lib.call("pulpo_grad_finish_multi", _ptr(table), len(key), _stream())
-    _PENDING_GRAD_JOBS.clear()
-    _PENDING_KEEPALIVE.clear()
+    bp.jobs.clear()
+    bp.keep.clear()
 
 
 def reset_param_grad_buffers(module: Optional[torch.nn.Module] = None) -> None:
     """after an interrupted step: forget the pending jobs and drop the persistent scratch buffers (they may hold partial sums)"""
-    _PENDING_GRAD_JOBS.clear()
-    _PENDING_KEEPALIVE.clear()
-    _BN_TILE_PARTS.clear()
+    for pending in (_PASS.jobs, _PASS.keep, _PASS.bn_parts):
+        pending.clear()
     if module is not None:
         for p_ in module.parameters():
             for name in ("_pulpo_wgrad_scratch", "_pulpo_dbias_part", "_pulpo_dbias_part_in", "_pulpo_heads_part"):
@@ -748,12 +787,9 @@ def _wgrad_raw(x: torch.Tensor, dy: torch.Tensor, Cin: int, Cout: int, into: Opt
 # nothing reads it before the all-reduce, so it need not finish before the backward pass moves on: it is queued on a second HIP
 # stream BEHIND this unit's data-gradient kernel, where the matrix-bound persistent kernel (one workgroup per CU) runs next to the
 # HBM-bound BatchNorm / LeakyReLU backward passes of the preceding unit on the main stream.  Joined before the gradient exchange
-# (dp.DataParallelStepper).  None = disabled (plain autograd use: gradients are returned on the caller's stream).
-ASYNC_WGRAD_STREAM = None
-
-
+# (dp.DataParallelStepper).  The stream is _PASS.side; None = disabled (plain autograd use: gradients are returned on the caller's stream).
 def _on_side_stream(launch, operands) -> None:
-    side = ASYNC_WGRAD_STREAM
+    side = _PASS.side
     side.wait_stream(torch.cuda.current_stream())        # after everything queued so far: dy, this unit's data gradient, zero_grad
     with torch.cuda.stream(side):
         launch()
@@ -767,10 +803,10 @@ def _wgrad_on_side_stream(x, dy, Cin, Cout, slot_w, owner):
 
 def join_async_wgrad():
     """make the current stream wait for every weight gradient queued on the side stream, then finish the deferred parameter gradients"""
-    if ASYNC_WGRAD_STREAM is not None:
-        torch.cuda.current_stream().wait_stream(ASYNC_WGRAD_STREAM)
-    if COARSE_WINDOW is not None:
-        COARSE_WINDOW.join()
+    if _PASS.side is not None:
+        torch.cuda.current_stream().wait_stream(_PASS.side)
+    if _PASS.window is not None:
+        _PASS.window.join()
     flush_param_grads()
 
 
@@ -786,10 +822,7 @@ def join_async_wgrad():
 # CUs per XCD and leaves the other 8 to the main stream's small kernels (measured: 192 is the best budget, 128 loses to in-line launches, and
 # the side stream may overrun the window - profiles/r6_window_ab.txt).  Which jobs to hold is learnt from the previous backward pass (the
 # sequence of weight gradients seen above the window; its last entries within the FLOP budget), so the first pass of a model holds nothing.
-# Set by dp.DataParallelStepper.backward (fp32, non-deterministic, direct parameter gradients); None = off (plain autograd use).
-COARSE_WINDOW = None
-
-
+# _PASS.window, from dp.DataParallelStepper.backward (fp32, non-deterministic, direct parameter gradients); None = off (plain autograd use).
 class CoarseWindow:
     ABOVE, INSIDE, BELOW = 0, 1, 2
 
@@ -880,10 +913,8 @@ class CoarseWindow:
 # unit u-1 would otherwise compute in a pass of its own over dz and y (pulpo_bn_lrelu_bwd_reduce).  The forward pass hands (y, coef) of
 # the producer to the consumer on the tensor z itself (`_pulpo_bn_src`); the backward pass of the consumer leaves the sums here, keyed by
 # the producer's y, and the producer takes them only if the gradient it is given IS that kernel's output, untouched (same storage, same
-# version: a gradient that autograd accumulated from several consumers is a different tensor or carries a bumped version).
-_BN_TILE_PARTS: dict = {}
-
-
+# version: a gradient that autograd accumulated from several consumers is a different tensor or carries a bumped version).  "Here" is
+# _PASS.bn_parts: what a unit whose backward never runs leaves there goes with its pass (the default pass's when backward_pass() is next entered).
 def _dgrad_with_bn_reduction(bn_src, x, dy, wpt, dx, K: int, N: int) -> bool:
     algo = getattr(wpt, "_pulpo_algo", "")
     if bn_src is None or not BN_REDUCE_IN_DGRAD or algo not in ("wino2", "wino3"):
@@ -914,12 +945,12 @@ def _dgrad_with_bn_reduction(bn_src, x, dy, wpt, dx, K: int, N: int) -> bool:
     if algo == "wino2" and t0 is not None and lib.query("pulpo_conv3d_k3_wino2_pipelined", D, H, W, K, dp):
         kname = "conv3d_k3_wino2p_mfma<true>"
     _trace_end(t0, kname, 54.0 * K * N * B * D * H * W, 4.0 * (K + 2 * N) * B * D * H * W)
-    _BN_TILE_PARTS[y_prev.data_ptr()] = (part, ntile, coef_prev.data_ptr(), dx.data_ptr(), dx._version, tuple(dx.shape), tuple(dx.stride()))
+    _PASS.bn_parts[y_prev.data_ptr()] = (part, ntile, coef_prev.data_ptr(), dx.data_ptr(), dx._version, tuple(dx.shape), tuple(dx.stride()))
     return True
 
 
 def _take_bn_tile_parts(y: torch.Tensor, coef: torch.Tensor, dz: torch.Tensor):
-    entry = _BN_TILE_PARTS.pop(y.data_ptr(), None)
+    entry = _PASS.bn_parts.pop(y.data_ptr(), None)
     if entry is None:
         return None
     part, ntile, coef_ptr, ptr, version, shape, stride = entry
@@ -980,7 +1011,7 @@ def cat_channels(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 #   1 _bwd_dz_source    the incoming gradients of the node's outputs -> where dz is read from (a _DzSource; None: no gradient arrived)
 #   2 _bwd_bn_sums      the first BatchNorm-backward pass - per-tile (sum dbn, sum dbn * xhat) - and its finalize.  The sums come from one of four
 #                       places: left behind by the data-gradient convolution (or pooling backward) that PRODUCED dz, if that was the operator behind
-#                       this unit (_BN_TILE_PARTS); the pooled pass; the head's backward; else a pass of its own over dz and y
+#                       this unit (_PASS.bn_parts); the pooled pass; the head's backward; else a pass of its own over dz and y
 #   3 _bwd_bn_apply     the second pass writes dy, blocked or channels-last (_bn_apply_entry: the entry point for the source and dy's layout), and the
 #                       conv-bias gradient's partial rows - except for the input layer, whose weight gradient forms dy itself (stage 4): no dy
 #   4 _bwd_param_grads  the conv-bias gradient (deferred, or column sums now) and the weight gradient, which goes ONE of four ways: fused with the
@@ -1105,7 +1136,7 @@ class _ConvBNLReLU(torch.autograd.Function):
                 return y
             _conv_raw(x, wp, bias, y, Cin, Cout, None)
         ctx.training = training
-        ctx.params = (weight, bias, gamma, beta)      # for DIRECT_PARAM_GRADS (their .grad slots)
+        ctx.params = (weight, bias, gamma, beta)      # for a direct pass (their .grad slots)
         ctx.pool_only = False
         ctx.head = (call.head_nout, call.head_params) if call.head_nout else None
         if call.head_nout:
@@ -1223,8 +1254,8 @@ def _bwd_bn_sums(src: _DzSource, y, coef, dims, nblk: int, training: bool, param
             lib.call("pulpo_bn_lrelu_bwd_reduce_t", _ptr(dz), _dt(dz), dz.stride(4), _ptr(y), _dt(y), y.stride(4), _ptr(coef), npix, Cout, LRELU_SLOPE,
                      _ptr(rows), _stream())
             _hbm_end(t0, "bn_lrelu_bwd_reduce", (_esize(dz) + _esize(y)) * Cout * npix)                # read dz, y
-    if COARSE_WINDOW is not None:                # (the window opens between the two passes: what it held back is queued behind this unit's first pass)
-        COARSE_WINDOW.visit(D * H * W)
+    if _PASS.window is not None:                 # (the window opens between the two passes: what it held back is queued behind this unit's first pass)
+        _PASS.window.visit(D * H * W)
     slot_w, slot_b, slot_g, slot_be = (_grad_slot(t) if need else None for t, need in zip(params, needs[1:5]))
     direct_bn = slot_g is not None and slot_be is not None
     tot = None if direct_bn else torch.empty(2 * Cout, device=dev, dtype=torch.float32)           # dbeta | dgamma
@@ -1240,7 +1271,7 @@ def _bwd_bn_sums(src: _DzSource, y, coef, dims, nblk: int, training: bool, param
 
 def _dbias_rows(b_p, slot_b, need_db: bool, name: str, nrow: int, Cout: int, dev):
     """the [nrow][Cout] partial rows a kernel leaves the conv-bias gradient in -> (rows, deferred?)"""
-    rows = _persistent_buffer(b_p, name, nrow * Cout, zero=False) if (DIRECT_PARAM_GRADS and need_db and slot_b is not None) else None
+    rows = _persistent_buffer(b_p, name, nrow * Cout, zero=False) if (_PASS.direct and need_db and slot_b is not None) else None
     # (inside the stepper: the parameter's persistent buffer, summed by flush_param_grads() - unless this unit has already run a backward pass
     #  in this step and its partials are still waiting there: this pass then takes the immediate path into the same slot)
     if rows is None or _pending_src(rows):
@@ -1330,7 +1361,7 @@ def _input_layer_param_grads(dz, x, y, coef, totd, dims, need_db: bool, params, 
         _trace_end(t0, "conv3d_k3_wgrad_smallc(+bn backward)" + ("" if deferred else "(+memset,unpack)"), 54.0 * Cin * Cout * B * D * H * W,
                    (4.0 * Cin + (_esize(dz) + 4.0) * Cout) * B * D * H * W)
 
-    if ASYNC_WGRAD_STREAM is not None and deferred:
+    if _PASS.side is not None and deferred:
         _on_side_stream(launch, (x, dz, y, coef, totd))
     else:
         launch()
@@ -1350,10 +1381,10 @@ def _bwd_param_grads(src: _DzSource, x, dy, bias_rows, y, coef, totd, dims, need
     if not need_dw:
         return None, dbias, None
     w_p = params[0]
-    if slot_w is not None and ASYNC_WGRAD_STREAM is not None:
+    if slot_w is not None and _PASS.side is not None:
         return None, dbias, (x, dy, Cin, Cout, slot_w, w_p)
-    if slot_w is not None and COARSE_WINDOW is not None:
-        COARSE_WINDOW.wgrad(x, dy, Cin, Cout, slot_w, w_p)
+    if slot_w is not None and _PASS.window is not None:
+        _PASS.window.wgrad(x, dy, Cin, Cout, slot_w, w_p)
         return None, dbias, None
     return _wgrad_raw(x, dy, Cin, Cout, into=slot_w, owner=w_p if slot_w is not None else None), dbias, None
 
@@ -1542,7 +1573,7 @@ def _heads_part_rows(params, need_wb: bool, nblk: int, nout: int, C: int, dev):
     adds their column sums to the parameters' .grad; a head applied twice in a step takes the immediate path"""
     rowlen = nout * C + nout
     slots = None
-    if params is not None and DIRECT_PARAM_GRADS and need_wb:
+    if params is not None and _PASS.direct and need_wb:
         wparts, bparts = params
         slots = [(_grad_slot(t), off, n) for t, off, n in wparts] + [(_grad_slot(t), off, n) for t, off, n in bparts]
         if not all(sl is not None for sl, _, _ in slots):
@@ -1653,7 +1684,7 @@ class _AvgPool2Skip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ready=None, bn_y=None, bn_coef=None):
         """bn_y / bn_coef: x is the untouched output of a ConvUnit, these are its pre-norm tensor and coefficient block - the backward pass then
-        also delivers that unit's BatchNorm-backward partial sums (see _BN_TILE_PARTS)"""
+        also delivers that unit's BatchNorm-backward partial sums (see _dgrad_with_bn_reduction)"""
         _require_gpu(x, act=True)
         ctx.set_materialize_grads(False)
         ctx.bn = (bn_y, bn_coef) if (bn_y is not None and BN_REDUCE_IN_DGRAD) else None
@@ -1695,7 +1726,7 @@ class _AvgPool2Skip(torch.autograd.Function):
                          gin.stride(4), _dt(g), _ptr(y), _dt(y), y.stride(4), _ptr(coef), LRELU_SLOPE, _ptr(part), B, D, H, W, C, _stream())
                 # read the pooled gradient, the skip gradient and y, write the summed gradient
                 _hbm_end(t0, "avgpool2_bwd_bnred", C * (_esize(g) * (g.numel() // C + (2 if gskip is not None else 1) * B * D * H * W) + _esize(y) * B * D * H * W))
-                _BN_TILE_PARTS[y.data_ptr()] = (part, nblk, coef.data_ptr(), gin.data_ptr(), gin._version, tuple(gin.shape), tuple(gin.stride()))
+                _PASS.bn_parts[y.data_ptr()] = (part, nblk, coef.data_ptr(), gin.data_ptr(), gin._version, tuple(gin.shape), tuple(gin.stride()))
                 return gin, None, None, None
         t0 = _hbm_begin("avgpool2_bwd_add") if skip_ok else None
         lib.call("pulpo_avgpool2_bwd_t", _ptr(g), g.stride(4), _ptr(gskip) if skip_ok else None, grid_strides(gskip)[1] if skip_ok else 0, _ptr(gin), gin.stride(4),

@@ -38,9 +38,8 @@ s.wait_stream(torch.cuda.current_stream())
 with torch.cuda.stream(s):
     for _ in range(2):
         stepper.arena.zero_grad()
-        ops.DIRECT_PARAM_GRADS = True; ops.ASYNC_WGRAD_STREAM = side
-        loss = model.training_step(batch, 0); loss.backward(); ops.join_async_wgrad()
-        ops.DIRECT_PARAM_GRADS = False; ops.ASYNC_WGRAD_STREAM = None
+        with ops.backward_pass(True, side):      # (its exit joins the side stream and finishes the deferred gradients)
+            loss = model.training_step(batch, 0); loss.backward()
         del loss
 torch.cuda.current_stream().wait_stream(s)
 torch.cuda.synchronize()
@@ -48,14 +47,12 @@ MODE = os.environ.get("PROBE", "full")
 print("capturing", MODE, flush=True)
 with torch.cuda.graph(g):
     stepper.arena.grad.zero_()
-    ops.DIRECT_PARAM_GRADS = True; ops.ASYNC_WGRAD_STREAM = side if MODE == "full" else None
-    print(" fwd", flush=True)
-    static_loss = model.training_step(batch, 0)
-    if MODE != "fwd":
-        print(" bwd", flush=True)
-        static_loss.backward()
-        ops.join_async_wgrad()
-    ops.DIRECT_PARAM_GRADS = False; ops.ASYNC_WGRAD_STREAM = None
+    with ops.backward_pass(True, side if MODE == "full" else None):
+        print(" fwd", flush=True)
+        static_loss = model.training_step(batch, 0)
+        if MODE != "fwd":
+            print(" bwd", flush=True)
+            static_loss.backward()
 print("captured")
 def gstep():
     g.replay()

@@ -21,10 +21,9 @@ for i in range(14):
     st.arena.zero_grad(); st._works, st._launched = [], 0
     loss = model.training_step(batch, 0)
     t1 = time.perf_counter()
-    ops.DIRECT_PARAM_GRADS = True; ops.ASYNC_WGRAD_STREAM = st._side
-    loss.backward()
-    t2 = time.perf_counter()
-    ops.DIRECT_PARAM_GRADS = False; ops.join_async_wgrad(); ops.ASYNC_WGRAD_STREAM = None
+    with ops.backward_pass(True, st._side):      # (its exit joins the side stream and finishes the deferred gradients: "join")
+        loss.backward()
+        t2 = time.perf_counter()
     st.opt.step(1.0)
     t3 = time.perf_counter()
     rows.append((t1 - t0, t2 - t1, t3 - t2))

@@ -3,6 +3,8 @@
   (2) the CPU oracle (oracle/pulpo_oracle.py) on seeded random inputs, including ragged / odd sizes.
 Stated fp32 tolerances: fields / warped volumes atol 1e-4, loss terms rtol 1e-4,
 gradients relative-L2 <= 1e-3 (<= 32^3 cases)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -1034,13 +1036,148 @@ def test_unit_and_head_applied_twice_in_one_stepper_step(ops, pooled_second, mod
     for rep in range(2):                                 # twice: the persistent scratch buffers must come back zeroed
         stepper.step((x, z))
         torch.cuda.synchronize()
-        assert not ops._PENDING_GRAD_JOBS and not ops._BN_TILE_PARTS
+        assert not ops._PASS.jobs and not ops._PASS.bn_parts
         for k, p in net.named_parameters():
             if k.endswith("_op.0.bias") and not k.endswith("head._op.2.bias"):
                 wmax = float(want[k[:-4] + "weight"].abs().max())       # bias in front of a BatchNorm: rounding noise on both sides
                 assert float((p.grad - want[k]).abs().max()) <= 1e-4 * max(wmax, 1e-6), (rep, k)
                 continue
             assert rel_l2(p.grad, want[k]) < 2e-5, (rep, k, rel_l2(p.grad, want[k]))
+
+
+# ---- the state of a backward pass (ops._BackwardPass) has one owner, ops.backward_pass: steppers of several models alternate in one process, a
+# ---- stepper alternates with plain autograd, and an interrupted pass leaves nothing behind
+_SCRATCH_NAMES = ("_pulpo_wgrad_scratch", "_pulpo_dbias_part", "_pulpo_dbias_part_in", "_pulpo_heads_part")
+
+
+def _default_pass_installed_and_empty(ops) -> bool:
+    d = ops._PASS
+    return d is ops._DEFAULT_PASS and (d.direct, d.side, d.window) == (False, None, None) and not d.jobs and not d.keep and not d.bn_parts
+
+
+@functools.lru_cache(maxsize=None)
+def _twice_case(pooled_second: bool):
+    """inputs, model factory and plain autograd's gradients of test_unit_and_head_applied_twice_in_one_stepper_step (computed once, never written to)"""
+    import src.network_blocks as nb
+    gen = torch.Generator().manual_seed(11)
+    x = torch.randn(1, 8, 16, 16, 16, generator=gen).cuda().contiguous(memory_format=torch.channels_last_3d)
+    z = torch.randn(1, 3, 16, 16, 16, generator=gen).cuda()
+
+    def make():
+        torch.manual_seed(4)
+        return _TwiceNet(nb, pooled_second).cuda().train()
+
+    ref = make()
+    ref.training_step((x, z), 0).backward()
+    return (x, z), make, {k: p.grad.detach().clone() for k, p in ref.named_parameters()}
+
+
+def _assert_twice_grads(net, want, tag):
+    """the bounds of test_unit_and_head_applied_twice_in_one_stepper_step"""
+    for k, p in net.named_parameters():
+        if k.endswith("_op.0.bias") and not k.endswith("head._op.2.bias"):
+            wmax = float(want[k[:-4] + "weight"].abs().max())           # bias in front of a BatchNorm: rounding noise on both sides
+            assert float((p.grad - want[k]).abs().max()) <= 1e-4 * max(wmax, 1e-6), (tag, k)
+            continue
+        assert rel_l2(p.grad, want[k]) < 2e-5, (tag, k, rel_l2(p.grad, want[k]))
+
+
+def test_two_steppers_alternate_in_one_process(ops, monkeypatch):
+    """A (weight gradients on its side stream, the shared unit's second application pooled) and B (in line, not pooled) step A, B, A, B: each
+    model's gradients are plain autograd's, and between any two steps the default pass is installed and empty - nothing of A's pass (its stream,
+    its pending jobs, its persistent scratch) reaches B's."""
+    from pulpo_amd import dp
+    monkeypatch.setenv("PULPO_WGRAD_SIDE_STREAM", "1")
+    cases = {name: _twice_case(pooled) for name, pooled in (("A", True), ("B", False))}
+    nets = {name: cases[name][1]() for name in cases}
+    steppers = {name: dp.DataParallelStepper(nets[name], lr=0.0, async_wgrad=(name == "A")) for name in cases}
+    assert steppers["A"].wgrad_on_side_stream() and not steppers["B"].wgrad_on_side_stream()
+    for st in steppers.values():
+        st.opt.step = lambda scale: None                 # keep the weights: the gradients are what is compared
+    for rep in range(2):
+        for name in ("A", "B"):
+            steppers[name].step(cases[name][0])
+            torch.cuda.synchronize()
+            assert _default_pass_installed_and_empty(ops), (rep, name)
+            _assert_twice_grads(nets[name], cases[name][2], (rep, name))
+
+
+def test_coarse_window_stepper_alternates_with_plain_autograd(ops):
+    """the window stepper of tests/test_gpu_wgrad_budget.py on the T3 / L2 model at 32^3, n0 = 8 (levels of 32^3, 16^3 and 8^3 voxels; 8^3 is
+    "coarse") alternating with plain-autograd backward passes of a second model: W, P, W, P.  The second window step holds weight gradients back.
+    (32^3 is the smallest size that does: at 16^3 both latent levels, 8^3 and 4^3, are coarse, the backward pass enters the window before it has
+    seen a weight gradient above it and deferred_last stays 0 - measured.)  Both models' gradients match their solo runs - two steps of a window
+    stepper alone, one plain backward alone - within the bounds of test_stepper_coarse_window_matches_the_inline_stepper."""
+    import launch_log
+    from pulpo_amd import dp
+    make, batch = launch_log._step_case(32, 8)
+    kw = dict(lr=0.0, coarse_window=True, coarse_voxels=8 ** 3, max_workgroups=64, defer_flop=1e30, exit_wait=True)
+
+    def grads(model):
+        return {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
+
+    def close(got, want, tag):
+        assert got.keys() == want.keys() and len(got) > 60
+        for k in want:
+            if k.endswith("_op.0.bias") and "velocity_field._op.2" not in k:
+                wmax = float(want[k[:-4] + "weight"].abs().max())
+                assert float((got[k] - want[k]).abs().max()) <= 1e-4 * max(wmax, 1e-6), (tag, k)
+                continue
+            assert rel_l2(got[k], want[k]) < 2e-5, (tag, k, rel_l2(got[k], want[k]))
+
+    solo_w = make()
+    solo = dp.DataParallelStepper(solo_w, **kw)
+    for _ in range(2):
+        solo.step(batch)
+    solo_p = make()
+    solo_p.training_step(batch, 0).backward()
+    torch.cuda.synchronize()
+    want_w, want_p = grads(solo_w), grads(solo_p)
+    assert solo.coarse_window() and solo._window.deferred_last > 0
+
+    w, p = make(), make()
+    stepper = dp.DataParallelStepper(w, **kw)
+    for rep in range(2):
+        stepper.step(batch)
+        torch.cuda.synchronize()
+        assert _default_pass_installed_and_empty(ops) and not stepper._window.held and not stepper._window.keep, rep
+        close(grads(w), want_w, ("window", rep))
+        p.zero_grad(set_to_none=True)
+        p.training_step(batch, 0).backward()
+        torch.cuda.synchronize()
+        assert ops._PASS is ops._DEFAULT_PASS and not ops._PASS.jobs and not ops._PASS.keep, rep
+        close(grads(p), want_p, ("plain", rep))
+    assert stepper._window.deferred_last > 0
+
+
+def test_interrupted_stepper_pass_leaves_nothing_behind(ops, monkeypatch):
+    """a tensor hook raises a Python RuntimeError between the two backward passes of the shared unit, with its first weight gradient on the side
+    stream and finishing jobs pending: the error propagates, the default pass is installed and empty, no parameter keeps persistent scratch (it
+    may hold partial sums), and the next full step of the same stepper gives plain autograd's gradients."""
+    from pulpo_amd import dp
+    monkeypatch.setenv("PULPO_WGRAD_SIDE_STREAM", "1")
+    batch, make, want = _twice_case(True)
+    net = make()
+    stepper = dp.DataParallelStepper(net, lr=0.0, async_wgrad=True)
+    stepper.opt.step = lambda scale: None
+    seen = []
+
+    def interrupt(g):
+        seen.append((ops._PASS is not ops._DEFAULT_PASS and ops._PASS.direct and ops._PASS.side is stepper._side, len(ops._PASS.jobs)))
+        raise RuntimeError("interrupted on purpose")
+
+    net.mid_hook = interrupt
+    with pytest.raises(RuntimeError, match="interrupted on purpose"):
+        stepper.step(batch)
+    torch.cuda.synchronize()
+    assert seen and seen[0][0] and seen[0][1] > 0, seen     # (the stepper's pass was installed and had jobs pending where it was interrupted)
+    assert _default_pass_installed_and_empty(ops) and not stepper._in_backward
+    assert not any(hasattr(p, n) for p in net.parameters() for n in _SCRATCH_NAMES)
+    net.mid_hook = None
+    stepper.step(batch)
+    torch.cuda.synchronize()
+    assert _default_pass_installed_and_empty(ops)
+    _assert_twice_grads(net, want, "after the interrupted pass")
 
 
 def _load_block(block, g, tag):

@@ -182,7 +182,7 @@ def test_stepper_coarse_window_matches_the_inline_stepper(ops):
     for step in range(1, 5):
         la, lb = inline.step(batch), window.step(batch)
         torch.cuda.synchronize()
-        assert ops.COARSE_WINDOW is None and not ops._PENDING_GRAD_JOBS and not window._window.held and not window._window.keep
+        assert ops._PASS.window is None and not ops._PASS.jobs and not window._window.held and not window._window.keep
         assert abs(float(la) - float(lb)) <= 2e-5 * abs(float(la)), (step, float(la), float(lb))
         ga, gb = _grads(a), _grads(b)
         assert ga.keys() == gb.keys() and len(ga) > 60
