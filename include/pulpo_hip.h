@@ -394,6 +394,29 @@ int pulpo_labels_from_onehot(const float* seg, void* labels, int ldt, int B, int
 int pulpo_map_ncc_blocks(int64_t n);
 int pulpo_map_ncc(const float* a, const float* b, int64_t n, double* partial, double* out, void* stream);
 
+/* ------------------------------------------------------------------------- boundary metrics: distance transform, HD / HD95 / ASSD (added within ABI 8: nothing else changed)
+ * No counterpart in the reference; DESIGN.md section 3l holds the definitions.  All distances are in voxels.  Integer arithmetic up to the
+ * final square roots: exact, and bit-identical from run to run.
+ * pulpo_edt_sq: out[p] = min over the non-zero voxels q of mask of |p - q|^2, exact, for mask (B,1,D,H,W) uint8 and out int32 of the same
+ *   shape; an item without a non-zero voxel gets PULPO_EDT_INF everywhere.  Extents 1 ... 1024 per axis; depth 1 is the 2-D form.  Needs no
+ *   workspace: the passes along H and D run in place on out.
+ * pulpo_surface_distances: for label maps lab_a, lab_b (B,1,D,H,W) (ldt 0 uint8, 1 int32) on one grid and every class c in [0, C), with
+ *   S_c(L) = the voxels of class c that have a face neighbour (6 for nd = 3, 4 for nd = 2, which needs D = 1) outside the class or the volume:
+ *   hist (B, C, 2, bins) int32, bins = pulpo_surface_distances_bins(D, H, W) = (D-1)^2 + (H-1)^2 + (W-1)^2 + 1: [b][c][0][k] = the number of
+ *   voxels of S_c(a) whose squared distance to S_c(b) is k, [b][c][1][k] the mirror (nullable: then it lives in ws);
+ *   out (B, C, 5) fp32 = HD, HDq (q in [0, 100], linear interpolation between order statistics, in double), ASSD, |S_c(a)|, |S_c(b)|;
+ *   HD, HDq, ASSD are NaN where either surface is empty (the counts in out are fp32: exact up to 2^24).  ws:
+ *   pulpo_surface_distances_ws_bytes(B, C, D, H, W) bytes, in this order - the counts (B, C, 2) int32 = |S_c(a)|, |S_c(b)|, exact, left there for
+ *   the caller; the distance planes of one chunk of classes (a size fixed by B and the volume, not by C); the histograms, which a caller
+ *   that passes hist may leave off (ws shorter by 8 B C bins bytes).
+ *   *flag = 1 when a label lies outside [0, C) (zeroed here). */
+#define PULPO_EDT_INF (1 << 29)
+int pulpo_edt_sq(const void* mask, int* out, int B, int D, int H, int W, void* stream);
+int64_t pulpo_surface_distances_bins(int D, int H, int W);
+size_t pulpo_surface_distances_ws_bytes(int B, int C, int D, int H, int W);
+int pulpo_surface_distances(const void* lab_a, const void* lab_b, int ldt, int C, double q, float* out, int* hist /*nullable*/, void* ws, int* flag,
+                            int B, int D, int H, int W, int nd, void* stream);
+
 /* --------------------------------------------------------------------------------------------------- optimizer
  * torch.optim.Adam(lr) defaults (src/models.py:398-400) over a flat fp32 arena; gscale pre-multiplies the gradient.  beta1, beta2 are doubles
  * (since ABI 8): 1 - beta and 1 - beta^step are formed in double. */

@@ -27,6 +27,8 @@ INVERSE_METRICS = ("InvCons", "InvConsMax", "LM_MAE_inv", "LM_Euclid_inv")
 MASK_METRICS = ("RMSE_masked", "MaskFrac")
 # the row level_scores adds with mind=True: the cross-contrast counterpart of RMSE, which means nothing between contrasts
 MIND_METRICS = ("MIND",)
+# the rows level_scores adds with surface=True: the boundary metrics beside Dice, in voxels
+SURFACE_METRICS = ("HD95", "ASSD")
 
 
 def _zero(ref: torch.Tensor) -> torch.Tensor:
@@ -38,7 +40,7 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
                  seg_y: Optional[torch.Tensor] = None, lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
                  num_classes: Optional[int] = None, final_dfs_inv: Optional[Dict[int, torch.Tensor]] = None,
                  mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
-                 mind_eps: float = 1e-5) -> Dict[str, Dict[int, torch.Tensor]]:
+                 mind_eps: float = 1e-5, surface: bool = False, include_background: bool = False) -> Dict[str, Dict[int, torch.Tensor]]:
     """The level losses of evaluate.py:1433-1474 for one pair: {metric: {level: 0-d device tensor}}.
 
     outputs[l], final_dfs[l]: the warped image and the final field of level l (predict_deterministic + combine_dfs); y: the fixed image.
@@ -63,7 +65,13 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
       MaskFrac[l]      mean of m_l
     mind=True (3-D only; no counterpart in the reference) adds, beside the rows above, which do not change,
       MIND[l]          mean over batch, voxels and the 12 channels of the squared difference of the MIND-SSC descriptors of outputs[l] and
-                       the target = mind_loss(outputs[l], target, mind_dilation, mind_eps) / num_pixels_l"""
+                       the target = mind_loss(outputs[l], target, mind_dilation, mind_eps) / num_pixels_l
+    surface=True (needs the segmentations; no counterpart in the reference) adds, beside the rows above, which do not change, at every level
+    whose field lies on seg_y's own grid (level 0, and every level under df_resolution="full_res"), from
+    ops.surface_distances(ops.warp_labels(final_dfs[l], seg_x, argmax=True), seg_y), in voxels,
+      HD95[l]          mean over the batch and the classes present in both maps of the 95th-percentile Hausdorff distance
+      ASSD[l]          the same mean of the average symmetric surface distance
+    class 0 is left out unless include_background; 0 when no class qualifies and at the other levels (PerformanceTable reads 0 as missing)."""
     levels = sorted(outputs.keys())
     if sorted(final_dfs.keys()) != levels:
         raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs {sorted(final_dfs.keys())}")
@@ -71,6 +79,8 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
         raise ValueError("level_scores: seg_x and seg_y go together")
     if (lm_x is None) != (lm_y is None):
         raise ValueError("level_scores: lm_x and lm_y go together")
+    if surface and seg_x is None:
+        raise ValueError("level_scores: surface=True needs seg_x and seg_y")
     if final_dfs_inv is not None and sorted(final_dfs_inv.keys()) != levels:
         raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs_inv {sorted(final_dfs_inv.keys())}")
     res: Dict[str, Dict[int, torch.Tensor]] = {"RMSE": {}, "JDetStd": {}, "JDetLeq0": {}}
@@ -100,6 +110,20 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
         lab_x, C = _as_labels(seg_x, num_classes, "level_scores")
         lab_y, _ = _as_labels(seg_y, C, "level_scores")
         res["Dice"] = {l: ops.warp_labels_soft_dice(final_dfs[l], lab_x, C, lab_y)[1] for l in levels}
+        if surface:
+            res["HD95"] = {l: _zero(y) for l in levels}
+            res["ASSD"] = {l: _zero(y) for l in levels}
+            first = 0 if include_background else 1
+            for l in levels:
+                if tuple(final_dfs[l].shape[2:]) != tuple(lab_y.shape[2:]):
+                    continue
+                # both maps passed the Dice row's range check and the arg-max writes classes only: no further host read
+                warped = ops._warp_labels(final_dfs[l], lab_x, C, None, False, True, False)
+                sd = ops._surface_distances(warped, lab_y, C, 95.0, False, False)
+                for name, key in (("HD95", "hd_pct"), ("ASSD", "assd")):
+                    v = sd[key][:, first:]
+                    ok = ~torch.isnan(v)
+                    res[name][l] = torch.where(ok, v, torch.zeros_like(v)).sum() / ok.sum().clamp(min=1)
     if lm_x is not None:
         res["LM_MAE"] = {l: _zero(y) for l in levels}
         res["LM_Euclid"] = {l: _zero(y) for l in levels}
@@ -128,16 +152,19 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
                 lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None,
                 num_classes: Optional[int] = None, inverse: bool = False, mask_x: Optional[torch.Tensor] = None,
                 mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
-                mind_eps: float = 1e-5, refine: Optional[Dict[str, object]] = None) -> Dict[str, Dict[int, torch.Tensor]]:
+                mind_eps: float = 1e-5, refine: Optional[Dict[str, object]] = None, surface: bool = False,
+                include_background: bool = False) -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
     unless the samplers are pinned (network_blocks.FixedNoiseSampler).  inverse=True also integrates the inverse fields
     (model.combine_dfs_bidirectional: one integration call per level for both directions) and adds the INVERSE_METRICS rows; mask_x / mask_y
-    add the MASK_METRICS rows, mind=True the MIND_METRICS row.  refine (a dict of pulpo_amd.refine.refine's keyword arguments, {} for its
+    add the MASK_METRICS rows, mind=True the MIND_METRICS row, surface=True (with segmentations) the SURFACE_METRICS rows.  refine (a dict of pulpo_amd.refine.refine's keyword arguments, {} for its
     defaults; no counterpart in the reference): the same rows for the fields of model.refine(x, y, **refine) instead of the prediction's
     (DESIGN.md section 3k); the masks given here score, they reach the refinement only through the dict."""
     final_dfs_inv = None
+    if surface and seg_x is None:
+        raise ValueError("performance: surface=True needs seg_x and seg_y")
     if refine is not None:
         res = model.refine(x, y, **refine)
         outputs, individual_dfs, final_dfs = res["outputs"], res["individual_dfs"], res["final_dfs"]
@@ -150,7 +177,8 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
         else:
             _, final_dfs = model.combine_dfs(individual_dfs)
     return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv,
-                        mask_x=mask_x, mask_y=mask_y, mind=mind, mind_dilation=mind_dilation, mind_eps=mind_eps)
+                        mask_x=mask_x, mask_y=mask_y, mind=mind, mind_dilation=mind_dilation, mind_eps=mind_eps,
+                        surface=surface, include_background=include_background)
 
 
 @torch.no_grad()

@@ -2691,8 +2691,8 @@ def _require_labels(*ts: Optional[torch.Tensor]):
             raise PulpoHipError(f"label maps are uint8 or int32 (got {t.dtype})")
 
 
-def _int_ptr(t: torch.Tensor, i: int = 0):
-    return ctypes.cast(t.data_ptr() + 4 * i, ctypes.POINTER(ctypes.c_int))
+def _int_ptr(t: Optional[torch.Tensor], i: int = 0):
+    return None if t is None else ctypes.cast(t.data_ptr() + 4 * i, ctypes.POINTER(ctypes.c_int))
 
 
 def _check_labels(labels: torch.Tensor, num_classes: int, flag: torch.Tensor, i: int) -> None:
@@ -2737,6 +2737,11 @@ def warp_labels(df, labels, num_classes: int, target=None, onehot: bool = False,
     [0, num_classes) raises IndexError (one host read).  Evaluation only: no autograd."""
     if not (onehot or argmax or target is not None):
         raise ValueError("warp_labels: request at least one of onehot, argmax, target")
+    return _warp_labels(df, labels, num_classes, target, onehot, argmax, True)
+
+
+def _warp_labels(df, labels, num_classes: int, target, onehot: bool, argmax: bool, check: bool):
+    """warp_labels; check=False skips the label-range pass and its host read (for maps the caller has range-checked already)"""
     _require_gpu(df)
     _require_labels(labels, target)
     is2d = _is2d(df)
@@ -2748,11 +2753,13 @@ def warp_labels(df, labels, num_classes: int, target=None, onehot: bool = False,
     am = torch.empty((B, 1) + grid, device=dev, dtype=labels.dtype) if argmax else None
     dice = torch.empty((B, C), device=dev, dtype=torch.float32) if target is not None else None
     flag = torch.zeros(3, device=dev, dtype=torch.int32)
-    _check_labels(labels, C, flag, 1)
-    if target is not None:
-        _check_labels(target, C, flag, 2)
+    if check:
+        _check_labels(labels, C, flag, 1)
+        if target is not None:
+            _check_labels(target, C, flag, 2)
     _warp_labels_raw(df, labels, C, target, oh, am, dice, None, None, 1, flag, 0)
-    _raise_on_flag(flag, "warp_labels")
+    if check:
+        _raise_on_flag(flag, "warp_labels")
     out = [t.squeeze(2) if is2d else t for t in (oh, am) if t is not None] + ([dice] if dice is not None else [])
     return out[0] if len(out) == 1 else tuple(out)
 
@@ -2859,3 +2866,79 @@ def map_ncc(a, b):
     out = torch.empty((), device=x.device, dtype=torch.float64)
     lib.call("pulpo_map_ncc", _ptr(x), _ptr(y), n, _ptr(part), _ptr(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ boundary metrics
+EDT_INF = 1 << 29          # edt_sq of an item without a feature voxel (PULPO_EDT_INF)
+
+
+@torch.no_grad()
+def edt_sq(mask):
+    """Exact squared Euclidean distance transform, in voxels: out[p] = min over the set voxels q of |p - q|^2 as int32 of the mask's shape.
+    mask (B, 1, D, H, W) or (B, 1, H, W), bool or uint8 (non-zero = set).  A batch item without a set voxel gets EDT_INF everywhere.
+    Extents up to 1024 per axis.  Evaluation only: no autograd."""
+    if not mask.is_cuda:
+        raise PulpoHipError("pulpo_amd operators run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise PulpoHipError(f"edt_sq: the mask is bool or uint8 (got {mask.dtype})")
+    if mask.dim() not in (4, 5) or mask.shape[1] != 1:
+        raise PulpoHipError(f"edt_sq: mask (B, 1, D, H, W) or (B, 1, H, W) expected, got {tuple(mask.shape)}")
+    m = mask.detach().contiguous()
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    m5 = _lift(m) if _is2d(m) else m
+    out = torch.empty(m5.shape, device=m.device, dtype=torch.int32)
+    B, _, D, H, W = (int(v) for v in m5.shape)
+    lib.call("pulpo_edt_sq", _ptr(m5), _int_ptr(out), B, D, H, W, _stream())
+    return out.squeeze(2) if _is2d(m) else out
+
+
+def _surface_distances(lab_a, lab_b, C: int, percentile: float, return_hist: bool, check: bool):
+    """surface_distances; check=False skips the host read of the label-range flag (for maps the caller has range-checked already)"""
+    _require_labels(lab_a, lab_b)
+    if tuple(lab_a.shape) != tuple(lab_b.shape) or lab_a.dim() not in (4, 5) or lab_a.shape[1] != 1:
+        raise PulpoHipError(f"surface_distances: two label maps (B, 1, ...) on one grid expected, got {tuple(lab_a.shape)} and {tuple(lab_b.shape)}")
+    nd = 2 if _is2d(lab_a) else 3
+    if nd == 2:
+        lab_a, lab_b = _lift(lab_a), _lift(lab_b)
+    a = lab_a.detach().contiguous()
+    B, _, D, H, W = (int(v) for v in a.shape)
+    dev = a.device
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    b = lab_b.detach().contiguous()
+    if b.dtype != a.dtype:                            # mixed dtypes run as int32: narrowing would wrap a label above 255 into range
+        a, b = a.to(torch.int32), b.to(torch.int32)
+    bins = int(lib.query("pulpo_surface_distances_bins", D, H, W))
+    nbytes = int(lib.query("pulpo_surface_distances_ws_bytes", B, C, D, H, W))
+    if bins <= 0 or nbytes <= 0:
+        raise PulpoHipError(f"surface_distances: num_classes >= 1 and extents 1 ... 1024 per axis expected, got C = {C}, grid {(D, H, W)}")
+    out = torch.empty((B, C, 5), device=dev, dtype=torch.float32)
+    hist = torch.empty((B, C, 2, bins), device=dev, dtype=torch.int32) if return_hist else None
+    # the workspace ends with room for the histograms, which a caller that passes its own leaves off
+    ws = torch.empty(nbytes - (hist.numel() * 4 if return_hist else 0), device=dev, dtype=torch.uint8)
+    lib.call("pulpo_surface_distances", _ptr(a), _ptr(b), _LABEL_DT[a.dtype], C, float(percentile), _ptr(out), _int_ptr(hist), _ptr(ws),
+             _int_ptr(flag), B, D, H, W, nd, _stream())
+    if check:
+        _raise_on_flag(flag, "surface_distances")
+    counts = ws[:8 * B * C].view(torch.int32).view(B, C, 2).clone()          # the exact int32 counts the workspace starts with
+    res = {"hd": out[..., 0], "hd_pct": out[..., 1], "assd": out[..., 2], "n_a": counts[..., 0], "n_b": counts[..., 1]}
+    if return_hist:
+        res["hist"] = hist
+    return res
+
+
+@torch.no_grad()
+def surface_distances(lab_a, lab_b, num_classes: int, percentile: float = 95.0, return_hist: bool = False):
+    """Boundary distances between two label maps (B, 1, ...) uint8 / int32 on one grid, per batch item and class, in voxels.  The surface
+    S_c(L) of class c is the set of its voxels with a face neighbour (6 in 3-D, 4 in 2-D) outside the class, the outside of the volume
+    included; d_AB = the distances of the voxels of S_c(A) to S_c(B), d_BA the mirror.  Returns a dict of (B, C) tensors:
+      hd      max(max d_AB, max d_BA)                                         (Hausdorff distance)
+      hd_pct  max(percentile(d_AB), percentile(d_BA)), numpy's linear rule    (HD95 for percentile = 95)
+      assd    (sum d_AB + sum d_BA) / (n_a + n_b)                             (average symmetric surface distance)
+      n_a, n_b  the surface voxel counts (int32)
+    hd, hd_pct and assd are NaN for a class absent from either map.  return_hist adds hist (B, C, 2, bins) int32, the counts of d_AB^2
+    ([:, :, 0]) and d_BA^2, bins = (D-1)^2 + (H-1)^2 + (W-1)^2 + 1.  Exact integer arithmetic up to the final square roots: bit-identical
+    from call to call.  A label outside [0, num_classes) raises IndexError (one host read).  Evaluation only: no autograd."""
+    if not 0.0 <= float(percentile) <= 100.0:
+        raise ValueError(f"surface_distances: percentile {percentile} outside [0, 100]")
+    return _surface_distances(lab_a, lab_b, int(num_classes), float(percentile), return_hist, True)
+
