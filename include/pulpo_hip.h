@@ -353,6 +353,34 @@ int pulpo_inverse_consistency(const float* a, const float* b, float* out /* 2 fl
 int pulpo_transport_points(const float* pts /*(npts,nd)*/, const float* field /*(nsamp,nd,D,H,W)*/, float* out /*(nsamp,npts,nd)*/, int npts,
                            int nsamp, int nd, int D, int H, int W, int* flag, void* stream);
 
+/* ------------------------------------------------------------------------- affine pre-alignment (added within ABI 8: nothing else changed)
+ * No counterpart in the reference, whose pairs arrive affinely aligned; DESIGN.md section 3m holds the conventions.
+ * theta: (B,3,4) fp32 row-major [M | t] in voxel units of a stated grid (D,H,W), about that grid's centre c = ((D-1)/2, (H-1)/2, (W-1)/2):
+ *   voxel v is sent to p = c + M (v - c) + t, and the displacement the affine stands for is d(v) = p - v under SpatialTransformer's convention
+ *   (pulpo_warp3d_fwd(d, img) samples img at the coordinate of v + d(v)).  One fp32 expression with a fixed operation order (csrc/affine_core.h)
+ *   serves every kernel below: they agree bit for bit, and [I | 0] gives d = 0 exactly.  A depth-1 grid is the 2-D form: theta's depth row and
+ *   column are the identity's (the depth displacement is written as 0 whatever they hold).  Arguments are checked before any launch: non-null
+ *   pointers, 1 <= B <= 65535, C >= 1, extents >= 1, fewer than 2^31 voxels.
+ * pulpo_affine_field: out (B,3,D,H,W) planar = d.
+ * pulpo_affine_warp_fwd: out (B,C,Dg,Hg,Wg) = pulpo_warp3d_fwd(pulpo_affine_field(theta on (Dg,Hg,Wg)), img (B,C,Di,Hi,Wi)) bit for bit, without the
+ *   field: 8 bytes per voxel and channel instead of 32.  A depth-1 grid needs a depth-1 image.
+ * pulpo_affine_warp_bwd: gtheta (B,3,4) = the gradient with respect to theta given gout (B,C,Dg,Hg,Wg); the image is data.  Per voxel
+ *   gpos_a = dscale_a sum_c gout_c d interp / d coord_a (pulpo_warp3d_bwd's displacement gradient, dscale_a = 0 where the coordinate was clamped);
+ *   gtheta[a][b] = sum_v gpos_a (v_b - c_b), gtheta[a][3] = sum_v gpos_a.  Sums in double: per thread, wave shuffles, LDS, one row of 12
+ *   doubles per block in ws, a second launch adds the rows in a fixed order (lane t of a wave rows t, t + 64, ..., then a butterfly).
+ *   No float atomics: two calls give the same bits.
+ *   ws: pulpo_affine_warp_bwd_ws_bytes(B, Dg, Hg, Wg) bytes, required.
+ * pulpo_affine_compose: "affine first, deformable second" as one field out (B,3,Dg,Hg,Wg) on df's grid; theta is in the frame of the image grid
+ *   (Di,Hi,Wi).  Per axis q = the clamped coordinate at which pulpo_warp3d_fwd(df, .) samples an image of that size, p = A(q), and
+ *   out = p (Sg-1)/(Si-1) - v, the displacement whose sample index is p Si/(Si-1) - 0.5: warp3d(out, img) = warp3d(df, warp3d(affine_field(theta), img))
+ *   up to the second interpolation of the two-step route.  H, W > 1 on both grids; depth 1 on both or on neither. */
+int pulpo_affine_field(const float* theta, float* out, int B, int D, int H, int W, void* stream);
+int pulpo_affine_warp_fwd(const float* theta, const float* img, float* out, int B, int C, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, void* stream);
+size_t pulpo_affine_warp_bwd_ws_bytes(int B, int Dg, int Hg, int Wg);
+int pulpo_affine_warp_bwd(const float* theta, const float* img, const float* gout, float* gtheta /*(B,3,4)*/, void* ws, int B, int C, int Dg, int Hg,
+                          int Wg, int Di, int Hi, int Wi, void* stream);
+int pulpo_affine_compose(const float* theta, const float* df, float* out, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, void* stream);
+
 /* ------------------------------------------------------------------------------- Monte-Carlo uncertainty statistics
  * evaluate.py:222-251 stacks N sampled volumes / fields per level and takes torch.std(axis=0) (unbiased) then torch.mean over the
  * channel axis.  Streaming form: fold sample k (1-based count) into running (mean, M2) images of the sample's shape, then

@@ -17,6 +17,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import affine as affine_mod
 from . import eval_metrics, ops
 from .uncertainty import _as_labels
 
@@ -153,7 +154,7 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
                 num_classes: Optional[int] = None, inverse: bool = False, mask_x: Optional[torch.Tensor] = None,
                 mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
                 mind_eps: float = 1e-5, refine: Optional[Dict[str, object]] = None, surface: bool = False,
-                include_background: bool = False) -> Dict[str, Dict[int, torch.Tensor]]:
+                include_background: bool = False, affine=None) -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
@@ -161,10 +162,22 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
     (model.combine_dfs_bidirectional: one integration call per level for both directions) and adds the INVERSE_METRICS rows; mask_x / mask_y
     add the MASK_METRICS rows, mind=True the MIND_METRICS row, surface=True (with segmentations) the SURFACE_METRICS rows.  refine (a dict of pulpo_amd.refine.refine's keyword arguments, {} for its
     defaults; no counterpart in the reference): the same rows for the fields of model.refine(x, y, **refine) instead of the prediction's
-    (DESIGN.md section 3k); the masks given here score, they reach the refinement only through the dict."""
+    (DESIGN.md section 3k); the masks given here score, they reach the refinement only through the dict.
+    affine (no counterpart in the reference): None - the pair is taken as affinely aligned, today's path; a (B,3,4)
+    ((B,2,3) for slices) tensor theta in voxels of x's grid, or a dict of pulpo_amd.affine.fit's keyword arguments ({} for its defaults) that
+    fits one.  The model (and a refinement) then sees ops.affine_warp(theta, x), and every row that reads a field reads
+    ops.affine_compose(theta, final_dfs[l], x's size) - "affine first, deformable second" as one field - together with the ORIGINAL seg_x /
+    lm_x / mask_x: one interpolation carries them through both transforms.  With inverse=True it raises NotImplementedError (the inverse of
+    the composition is not built)."""
     final_dfs_inv = None
     if surface and seg_x is None:
         raise ValueError("performance: surface=True needs seg_x and seg_y")
+    theta = None
+    if affine is not None:
+        if inverse:
+            raise NotImplementedError("performance: inverse=True together with affine= (the inverse of the composed transform) is not implemented")
+        theta = affine_mod.fit(x, y, **affine)["theta"] if isinstance(affine, dict) else affine
+        x = ops.affine_warp(theta, x)
     if refine is not None:
         res = model.refine(x, y, **refine)
         outputs, individual_dfs, final_dfs = res["outputs"], res["individual_dfs"], res["final_dfs"]
@@ -176,6 +189,8 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
             _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
         else:
             _, final_dfs = model.combine_dfs(individual_dfs)
+    if theta is not None:
+        final_dfs = {l: ops.affine_compose(theta, df, x.shape[2:]) for l, df in final_dfs.items()}
     return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv,
                         mask_x=mask_x, mask_y=mask_y, mind=mind, mind_dilation=mind_dilation, mind_eps=mind_eps,
                         surface=surface, include_background=include_background)
@@ -183,9 +198,17 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
 
 @torch.no_grad()
 def affine_scores(x: torch.Tensor, y: torch.Tensor, seg_x: Optional[torch.Tensor] = None, seg_y: Optional[torch.Tensor] = None,
-                  lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                  lm_x: Optional[torch.Tensor] = None, lm_y: Optional[torch.Tensor] = None, theta: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """The naive baseline of Evaluate.performance_affine (evaluate.py:1190-1204), the scores of the unregistered pair: RMSE = rmse(x, y);
-    with (one-hot or soft) segmentation maps Dice = dsc(seg_x, seg_y); with landmarks LM_MAE / LM_Euclid of the unwarped landmarks."""
+    with (one-hot or soft) segmentation maps Dice = dsc(seg_x, seg_y); with landmarks LM_MAE / LM_Euclid of the unwarped landmarks.
+    theta ((B,3,4) in voxels of x's grid, (B,2,3) for slices): the scores of the affinely aligned pair instead - x and
+    the channels of seg_x under ops.affine_warp(theta, .), the landmarks under warp_landmarks by ops.affine_field(theta)."""
+    if theta is not None:
+        x = ops.affine_warp(theta, x)
+        if seg_x is not None and seg_y is not None:
+            seg_x = ops.affine_warp(theta, seg_x.float())
+        if lm_x is not None and lm_y is not None and lm_x.numel():
+            lm_x = ops.warp_landmarks(lm_x, ops.affine_field(theta, x.shape[2:])[:1])
     res = {"RMSE": eval_metrics.rmse(x, y)}
     if seg_x is not None and seg_y is not None:
         res["Dice"] = eval_metrics.dsc(seg_x, seg_y)

@@ -2942,3 +2942,110 @@ def surface_distances(lab_a, lab_b, num_classes: int, percentile: float = 95.0, 
         raise ValueError(f"surface_distances: percentile {percentile} outside [0, 100]")
     return _surface_distances(lab_a, lab_b, int(num_classes), float(percentile), return_hist, True)
 
+
+
+# ------------------------------------------------------------------------------------------------ affine pre-alignment
+def _theta3(theta, name: str):
+    """(theta as (B,3,4), was 2-D): a (B,2,3) slice transform is lifted with an identity depth row and column, by differentiable torch ops on
+    its six entries"""
+    if theta.dim() != 3 or tuple(theta.shape[1:]) not in ((3, 4), (2, 3)):
+        raise ValueError(f"{name}: theta (B,3,4) or, for slices, (B,2,3) expected, got {tuple(theta.shape)}")
+    if theta.shape[1] == 3:
+        return theta, False
+    lifted = torch.nn.functional.pad(theta, (1, 0, 1, 0))
+    corner = torch.zeros(3, 4, device=theta.device, dtype=theta.dtype)
+    corner[0, 0] = 1.0
+    return lifted + corner, True
+
+
+def _size3(size, two_d: bool, name: str):
+    size = tuple(int(s) for s in size)
+    if len(size) != (2 if two_d else 3) or min(size) < 1:
+        raise ValueError(f"{name}: a size of {2 if two_d else 3} extents >= 1 expected for this theta, got {size}")
+    return ((1,) + size) if two_d else size
+
+
+@torch.no_grad()
+def affine_field(theta, size):
+    """the displacement field an affine stands for: theta (B,3,4) = [M | t] in voxel units of the grid `size` = (D,H,W), about the grid's
+    centre c = (size - 1) / 2, sends voxel v to p = c + M (v - c) + t; the result (B,3,D,H,W) is d = p - v under SpatialTransformer's
+    convention (warp3d(d, img) samples img where v + d(v) points).  (B,2,3) with size (H,W) gives (B,2,H,W).  The bridge to every operator
+    that takes a field (warp_labels, warp_mask, warp_landmarks, field_quality, ...).  No autograd: affine_warp carries theta's gradient."""
+    theta, two_d = _theta3(theta.detach(), "affine_field")
+    D, H, W = _size3(size, two_d, "affine_field")
+    _require_gpu(theta)
+    theta = theta.contiguous()
+    B = theta.shape[0]
+    out = torch.empty((B, 3, D, H, W), device=theta.device, dtype=torch.float32)
+    t0 = _hbm_begin("affine_field")
+    lib.call("pulpo_affine_field", _ptr(theta), _ptr(out), B, D, H, W, _stream())
+    _hbm_end(t0, "affine_field", 4.0 * out.numel())
+    return _unlift_field(out) if two_d else out
+
+
+class _AffineWarp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, theta, img, size):
+        _require_gpu(theta, img)
+        theta, img = theta.contiguous(), planar(img)
+        B, C, Di, Hi, Wi = img.shape
+        Dg, Hg, Wg = size
+        out = torch.empty((B, C, Dg, Hg, Wg), device=img.device, dtype=torch.float32)
+        t0 = _hbm_begin("affine_warp_fwd")
+        lib.call("pulpo_affine_warp_fwd", _ptr(theta), _ptr(img), _ptr(out), B, C, Dg, Hg, Wg, Di, Hi, Wi, _stream())
+        _hbm_end(t0, "affine_warp_fwd", 4.0 * (img.numel() + out.numel()))                   # the image read once, the result written: no field
+        ctx.save_for_backward(theta, img)
+        ctx.size = size
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        theta, img = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        g = planar(g)
+        B, C, Di, Hi, Wi = img.shape
+        Dg, Hg, Wg = ctx.size
+        ws = torch.empty(lib.query("pulpo_affine_warp_bwd_ws_bytes", B, Dg, Hg, Wg), device=img.device, dtype=torch.uint8)
+        gtheta = torch.empty((B, 3, 4), device=img.device, dtype=torch.float32)
+        t0 = _hbm_begin("affine_warp_bwd")
+        lib.call("pulpo_affine_warp_bwd", _ptr(theta), _ptr(img), _ptr(g), _ptr(gtheta), _ptr(ws), B, C, Dg, Hg, Wg, Di, Hi, Wi, _stream())
+        _hbm_end(t0, "affine_warp_bwd", 4.0 * (img.numel() + g.numel()))                     # the image and the upstream gradient read once
+        return gtheta, None, None
+
+
+def affine_warp(theta, img, size=None):
+    """warp3d(affine_field(theta, size), img) in one kernel that never writes the field: bit-identical to that route, a quarter of its
+    bytes.  theta (B,3,4) on the output grid `size` (default: img's own), img (B,C,Di,Hi,Wi); slices: theta (B,2,3), img (B,C,H,W).
+    Differentiable with respect to theta only (deterministic: ordered double sums, no float atomics); the image is data - an img that
+    requires grad raises ValueError."""
+    if img.requires_grad:
+        raise ValueError("affine_warp: the image is data here (no gradient with respect to img); detach it, or use warp3d(affine_field(theta, size), img)")
+    theta3, two_d = _theta3(theta, "affine_warp")
+    if two_d != _is2d(img) or img.dim() not in (4, 5) or img.shape[0] != theta.shape[0]:
+        raise ValueError(f"affine_warp: theta {tuple(theta.shape)} and img {tuple(img.shape)} do not go together")
+    img5 = _lift(img) if two_d else img
+    size3 = _size3(img.shape[2:] if size is None else size, two_d, "affine_warp")
+    out = _AffineWarp.apply(theta3, img5, size3)
+    return out.squeeze(2) if two_d else out
+
+
+@torch.no_grad()
+def affine_compose(theta, df, image_size=None):
+    """"affine first, deformable second" as one field on df's grid: warp3d(affine_compose(theta, df), img) equals
+    warp3d(df, affine_warp(theta, img)) up to the second interpolation of that two-step route, so a segmentation, a mask or landmarks of
+    the original moving image are carried through both transforms with one interpolation.  theta (B,3,4) in the frame of the image grid
+    `image_size` (default: df's own grid), df (B,3,Dg,Hg,Wg); slices: theta (B,2,3), df (B,2,H,W).  No autograd."""
+    theta, two_d = _theta3(theta.detach(), "affine_compose")
+    if two_d != _is2d(df) or df.dim() not in (4, 5) or df.shape[0] != theta.shape[0] or df.shape[1] != df.dim() - 2:
+        raise ValueError(f"affine_compose: theta {tuple(theta.shape)} and df {tuple(df.shape)} do not go together")
+    Di, Hi, Wi = _size3(df.shape[2:] if image_size is None else image_size, two_d, "affine_compose")
+    df5 = planar(_lift_field(df.detach()) if two_d else df.detach())
+    _require_gpu(theta, df5)
+    theta = theta.contiguous()
+    B, _, Dg, Hg, Wg = df5.shape
+    out = torch.empty_like(df5)
+    t0 = _hbm_begin("affine_compose")
+    lib.call("pulpo_affine_compose", _ptr(theta), _ptr(df5), _ptr(out), B, Dg, Hg, Wg, Di, Hi, Wi, _stream())
+    _hbm_end(t0, "affine_compose", 8.0 * out.numel())
+    return _unlift_field(out) if two_d else out
