@@ -421,6 +421,27 @@ int pulpo_warp_labels_soft_dice(const float* df, const void* labels, const void*
 int pulpo_labels_from_onehot(const float* seg, void* labels, int ldt, int B, int C, int64_t V, void* stream);
 int pulpo_map_ncc_blocks(int64_t n);
 int pulpo_map_ncc(const float* a, const float* b, int64_t n, double* partial, double* out, void* stream);
+/* The Dice term of the training step from label maps (added within ABI 8: nothing else changed).
+ * pulpo_label_dice_fwd: loss (1 float) = mean_(b,c)(1 - dice_bc) * Vg / dice_factor, Vg = Dg*Hg*Wg: Soft_dice_loss (src/losses.py:137-145) of
+ *   SpatialTransformer(df, one_hot(labels)) against F.interpolate(one_hot(target), size = grid) from the fixed-point sums of
+ *   pulpo_warp_labels_soft_dice (the same kernel; same arguments, ws and flag).  dice (B,C): that entry point's values bit for bit.
+ *   coef (B,C,2) = (a, b) with dL/dp_c(v) = a t_c(v) + b p_c(v): a = -2 S / den, b = 2 S num / den^2, num = 2 sum(p t) + 1e-6,
+ *   den = sum(t^2) + sum(p^2) + 1e-6, S = Vg / (dice_factor B C); formed in double.
+ * pulpo_label_dice_bwd: ddf (B,3,Dg,Hg,Wg) planar = gup[0] * dL/d df (gup: one float on the device), one thread per grid voxel:
+ *   ddf_axis = gup dscale_axis sum_i G_i dw_i/dcoord_axis over the 8 corners, G_i = a[c_i] t_{c_i} + b[c_i] p_{c_i}; dscale is 0 where the
+ *   coordinate was clamped and on the depth axis of a depth-1 grid.  No atomics: two calls give the same bits.  A label outside [0, C)
+ *   counts for no class.
+ * pulpo_labels_pool2: out (B,C,ceil(D/2),ceil(H/2),ceil(W/2)) planar = avg_pool3d(one_hot(labels), 2, 2, ceil_mode=True), edge windows divided
+ *   by their in-bounds count (exact: counts over powers of two).
+ * pulpo_labels_resize: out (B,C,Do,Ho,Wo) planar = F.interpolate(one_hot(labels (B,1,Dt,Ht,Wt)), size, trilinear, align_corners=False): the tap
+ *   weights of pulpo_warp_labels_soft_dice's target summed per class.  Depth 1 is the 2-D form in both. */
+int pulpo_label_dice_fwd(const float* df, const void* labels, const void* target, int ldt, int C, float dice_factor, float* loss, float* dice,
+                         float* coef, void* ws, int* flag, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, int Dt, int Ht, int Wt,
+                         void* stream);
+int pulpo_label_dice_bwd(const float* df, const void* labels, const void* target, int ldt, int C, const float* coef, const float* gup, float* ddf,
+                         int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, int Dt, int Ht, int Wt, void* stream);
+int pulpo_labels_pool2(const void* labels, int ldt, int C, float* out, int B, int D, int H, int W, void* stream);
+int pulpo_labels_resize(const void* labels, int ldt, int C, float* out, int B, int Dt, int Ht, int Wt, int Do, int Ho, int Wo, void* stream);
 
 /* ------------------------------------------------------------------------- boundary metrics: distance transform, HD / HD95 / ASSD (added within ABI 8: nothing else changed)
  * No counterpart in the reference; DESIGN.md section 3l holds the definitions.  All distances are in voxels.  Integer arithmetic up to the

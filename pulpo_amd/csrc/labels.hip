@@ -374,6 +374,182 @@ __global__ void ncc_finalize_kernel(const double* __restrict__ part2, int nblk, 
     out[0] = sab / ((sa * (double)n + 1e-15) * (sb + 1e-15));
 }
 
+// ------------------------------------------------------------------------------------------------ Dice term of the training step from label maps
+// Soft_dice_loss (src/losses.py:137-145) of warp3d(df, one_hot(labels)) against the resized one-hot target, with its gradient with respect
+// to the field.  The forward sums are warp_labels_soft_dice_kernel's; this finisher turns them into the loss
+// mean_(b,c)(1 - dice_bc) * scale (scale = Vg / dice_factor), the per-class Dice (the expression of soft_dice_from_sums_kernel) and, per
+// (b, c), the two coefficients of dL/dp_c(v) = a t_c(v) + b p_c(v): a = -2 S / den, b = 2 S num / den^2, S = scale / n.  One wave, in double.
+__global__ void label_dice_finish_kernel(const unsigned long long* __restrict__ sums, int n, double scale, float* __restrict__ dice,
+                                         float* __restrict__ coef, float* __restrict__ loss) {
+    double acc = 0.0;
+    const double S = scale / n;
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const double s0 = (double)sums[3 * i] / kFix, s1 = (double)sums[3 * i + 1] / kFix, s2 = (double)sums[3 * i + 2] / kFix;
+        const double num = 2.0 * s0 + 1e-6, den = s1 + s2 + 1e-6;
+        const double d = num / den;
+        dice[i] = (float)d;
+        coef[2 * i] = (float)(-2.0 * S / den);
+        coef[2 * i + 1] = (float)(2.0 * S * num / (den * den));
+        acc += 1.0 - d;
+    }
+    acc = pulpo::wave_sum_d(acc);
+    if (threadIdx.x == 0) loss[0] = (float)(acc / n * scale);
+}
+
+// grid (ceil(Vg / 256), B), one thread per grid voxel, x fastest: the three displacement planes read and the three gradient planes written
+// coalesced.  The coordinate, the 8 corner labels and weights and the 8 resize taps are warp_labels_soft_dice_kernel's expressions in its
+// order, so p_c and t_c are the forward's to the bit.  For corner i of class c_i, G_i = a[c_i] t_{c_i} + b[c_i] p_{c_i} is dL/dw_i; the
+// weights are products of (1 - f) and f per axis, so d w_i / d coord_z = -/+ wy wx for the low / high corner, likewise y and x.
+// A label outside [0, C) counts for no class and never indexes the table.  No atomics, no reduction: each voxel's gradient is its own.
+template <typename LT>
+__global__ __launch_bounds__(256) void label_dice_bwd_kernel(const float* __restrict__ df, const LT* __restrict__ lab, const LT* __restrict__ tgt,
+                                                               int C, const float* __restrict__ coef, const float* __restrict__ gup,
+                                                               float* __restrict__ ddf, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, int Dt, int Ht,
+                                                               int Wt) {
+    __shared__ float tab[2 * kMaxClasses];          // (a, b) per class of this block's batch element
+    const int b = blockIdx.y;
+    for (int j = threadIdx.x; j < 2 * C; j += 256) tab[j] = coef[(long)b * 2 * C + j];
+    __syncthreads();
+    const long Vg = (long)Dg * Hg * Wg, Vi = (long)Di * Hi * Wi, Vt = (long)Dt * Ht * Wt;
+    const long v = (long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= Vg) return;
+    const LT* lb = lab + b * Vi;
+    const LT* tb = tgt + b * Vt;
+    const float sd = (float)Dt / (float)Dg, shh = (float)Ht / (float)Hg, sw = (float)Wt / (float)Wg;
+    const int vi = (int)v;
+    const int x = vi % Wg, y = (vi / Wg) % Hg, z = vi / (Wg * Hg);
+    const float* d = df + (long)b * 3 * Vg + v;
+    const Corner cz = sample_coord((float)z, d[0], Dg, Di);
+    const Corner cy = sample_coord((float)y, d[Vg], Hg, Hi);
+    const Corner cx = sample_coord((float)x, d[2 * Vg], Wg, Wi);
+    const long o00 = ((long)cz.i0 * Hi + cy.i0) * Wi, o01 = ((long)cz.i0 * Hi + cy.i1) * Wi;
+    const long o10 = ((long)cz.i1 * Hi + cy.i0) * Wi, o11 = ((long)cz.i1 * Hi + cy.i1) * Wi;
+    const float wz0 = 1.f - cz.f, wy0 = 1.f - cy.f, wx0 = 1.f - cx.f;
+    int cl[8], tl[8];
+    float w[8], u[8];
+    w[0] = wz0 * wy0 * wx0; w[1] = wz0 * wy0 * cx.f; w[2] = wz0 * cy.f * wx0; w[3] = wz0 * cy.f * cx.f;
+    w[4] = cz.f * wy0 * wx0; w[5] = cz.f * wy0 * cx.f; w[6] = cz.f * cy.f * wx0; w[7] = cz.f * cy.f * cx.f;
+    cl[0] = load_label(lb, o00 + cx.i0); cl[1] = load_label(lb, o00 + cx.i1);
+    cl[2] = load_label(lb, o01 + cx.i0); cl[3] = load_label(lb, o01 + cx.i1);
+    cl[4] = load_label(lb, o10 + cx.i0); cl[5] = load_label(lb, o10 + cx.i1);
+    cl[6] = load_label(lb, o11 + cx.i0); cl[7] = load_label(lb, o11 + cx.i1);
+    int z0, z1, y0, y1, x0, x1;
+    float lz, ly, lx;
+    resize_src_index(z, sd, Dt, z0, z1, lz);
+    resize_src_index(y, shh, Ht, y0, y1, ly);
+    resize_src_index(x, sw, Wt, x0, x1, lx);
+    const long t00 = ((long)z0 * Ht + y0) * Wt, t01 = ((long)z0 * Ht + y1) * Wt;
+    const long t10 = ((long)z1 * Ht + y0) * Wt, t11 = ((long)z1 * Ht + y1) * Wt;
+    const float uz0 = 1.f - lz, uy0 = 1.f - ly, ux0 = 1.f - lx;
+    u[0] = uz0 * uy0 * ux0; u[1] = uz0 * uy0 * lx; u[2] = uz0 * ly * ux0; u[3] = uz0 * ly * lx;
+    u[4] = lz * uy0 * ux0; u[5] = lz * uy0 * lx; u[6] = lz * ly * ux0; u[7] = lz * ly * lx;
+    tl[0] = load_label(tb, t00 + x0); tl[1] = load_label(tb, t00 + x1);
+    tl[2] = load_label(tb, t01 + x0); tl[3] = load_label(tb, t01 + x1);
+    tl[4] = load_label(tb, t10 + x0); tl[5] = load_label(tb, t10 + x1);
+    tl[6] = load_label(tb, t11 + x0); tl[7] = load_label(tb, t11 + x1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (cl[i] < 0 || cl[i] >= C) cl[i] = -1;
+        if (tl[i] < 0 || tl[i] >= C) tl[i] = -2;                 // (never equal to a corner's class, valid or not)
+    }
+    float G[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        float pc = 0.f, tc = 0.f;                                 // matching weights added in corner / tap order, starting from 0, as the forward does
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            pc += cl[j] == cl[i] ? w[j] : 0.f;
+            tc += tl[j] == cl[i] ? u[j] : 0.f;
+        }
+        const int c = cl[i] < 0 ? 0 : cl[i];
+        const float g = tab[2 * c] * tc + tab[2 * c + 1] * pc;
+        G[i] = cl[i] < 0 ? 0.f : g;
+    }
+    const float gz = (G[4] - G[0]) * (wy0 * wx0) + (G[5] - G[1]) * (wy0 * cx.f) + (G[6] - G[2]) * (cy.f * wx0) + (G[7] - G[3]) * (cy.f * cx.f);
+    const float gy = (G[2] - G[0]) * (wz0 * wx0) + (G[3] - G[1]) * (wz0 * cx.f) + (G[6] - G[4]) * (cz.f * wx0) + (G[7] - G[5]) * (cz.f * cx.f);
+    const float gx = (G[1] - G[0]) * (wz0 * wy0) + (G[3] - G[2]) * (wz0 * cy.f) + (G[5] - G[4]) * (cz.f * wy0) + (G[7] - G[6]) * (cz.f * cy.f);
+    const float k0 = gup[0];
+    float* o = ddf + (long)b * 3 * Vg + v;
+    o[0] = k0 * cz.dscale * gz;
+    o[Vg] = k0 * cy.dscale * gy;
+    o[2 * Vg] = k0 * cx.dscale * gx;
+}
+
+// avg_pool3d(one_hot(labels), kernel 2, stride 2, ceil_mode) without the one-hot map: per output voxel the share of each class among the
+// in-bounds voxels of its 2x2x2 window (1, 2, 4 or 8 of them: the values are counts over powers of two, exact).  grid (nblk, B); out planar
+// (B, C, Do, Ho, Wo).  A label outside [0, C) counts for no class.
+template <typename LT>
+__global__ __launch_bounds__(256) void labels_pool2_kernel(const LT* __restrict__ lab, float* __restrict__ out, int C, int D, int H, int W, int Do,
+                                                             int Ho, int Wo) {
+    const int b = blockIdx.y;
+    const long Vo = (long)Do * Ho * Wo;
+    const LT* lb = lab + (long)b * D * H * W;
+    for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < Vo; v += (long)gridDim.x * 256) {
+        const int vi = (int)v;
+        const int ox = vi % Wo, oy = (vi / Wo) % Ho, oz = vi / (Wo * Ho);
+        const int z0 = 2 * oz, y0 = 2 * oy, x0 = 2 * ox;
+        const bool hz = z0 + 1 < D, hy = y0 + 1 < H, hx = x0 + 1 < W;
+        const int z1 = hz ? z0 + 1 : z0, y1 = hy ? y0 + 1 : y0, x1 = hx ? x0 + 1 : x0;
+        const long o00 = ((long)z0 * H + y0) * W, o01 = ((long)z0 * H + y1) * W, o10 = ((long)z1 * H + y0) * W, o11 = ((long)z1 * H + y1) * W;
+        int cl[8];
+        cl[0] = load_label(lb, o00 + x0);
+        cl[1] = hx ? load_label(lb, o00 + x1) : -1;
+        cl[2] = hy ? load_label(lb, o01 + x0) : -1;
+        cl[3] = hy && hx ? load_label(lb, o01 + x1) : -1;
+        cl[4] = hz ? load_label(lb, o10 + x0) : -1;
+        cl[5] = hz && hx ? load_label(lb, o10 + x1) : -1;
+        cl[6] = hz && hy ? load_label(lb, o11 + x0) : -1;
+        cl[7] = hz && hy && hx ? load_label(lb, o11 + x1) : -1;
+        const float inv = 1.f / (float)((hz ? 2 : 1) * (hy ? 2 : 1) * (hx ? 2 : 1));
+        float* o = out + (long)b * C * Vo + v;
+        for (int c = 0; c < C; ++c) {
+            int n = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) n += cl[i] == c ? 1 : 0;
+            o[(long)c * Vo] = (float)n * inv;
+        }
+    }
+}
+
+// F.interpolate(one_hot(labels), size, trilinear, align_corners=False) without the one-hot map: per output voxel and class the sum of the
+// tap weights that carry the class - the taps, weights and summation order of t_c in warp_labels_soft_dice_kernel.  grid (nblk, B); out
+// planar (B, C, Do, Ho, Wo).  A label outside [0, C) counts for no class.
+template <typename LT>
+__global__ __launch_bounds__(256) void labels_resize_kernel(const LT* __restrict__ lab, float* __restrict__ out, int C, int Dt, int Ht, int Wt, int Do,
+                                                              int Ho, int Wo) {
+    const int b = blockIdx.y;
+    const long Vo = (long)Do * Ho * Wo;
+    const LT* tb = lab + (long)b * Dt * Ht * Wt;
+    const float sd = (float)Dt / (float)Do, shh = (float)Ht / (float)Ho, sw = (float)Wt / (float)Wo;
+    for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < Vo; v += (long)gridDim.x * 256) {
+        const int vi = (int)v;
+        const int x = vi % Wo, y = (vi / Wo) % Ho, z = vi / (Wo * Ho);
+        int z0, z1, y0, y1, x0, x1;
+        float lz, ly, lx;
+        resize_src_index(z, sd, Dt, z0, z1, lz);
+        resize_src_index(y, shh, Ht, y0, y1, ly);
+        resize_src_index(x, sw, Wt, x0, x1, lx);
+        const long t00 = ((long)z0 * Ht + y0) * Wt, t01 = ((long)z0 * Ht + y1) * Wt;
+        const long t10 = ((long)z1 * Ht + y0) * Wt, t11 = ((long)z1 * Ht + y1) * Wt;
+        const float uz0 = 1.f - lz, uy0 = 1.f - ly, ux0 = 1.f - lx;
+        float u[8];
+        int tl[8];
+        u[0] = uz0 * uy0 * ux0; u[1] = uz0 * uy0 * lx; u[2] = uz0 * ly * ux0; u[3] = uz0 * ly * lx;
+        u[4] = lz * uy0 * ux0; u[5] = lz * uy0 * lx; u[6] = lz * ly * ux0; u[7] = lz * ly * lx;
+        tl[0] = load_label(tb, t00 + x0); tl[1] = load_label(tb, t00 + x1);
+        tl[2] = load_label(tb, t01 + x0); tl[3] = load_label(tb, t01 + x1);
+        tl[4] = load_label(tb, t10 + x0); tl[5] = load_label(tb, t10 + x1);
+        tl[6] = load_label(tb, t11 + x0); tl[7] = load_label(tb, t11 + x1);
+        float* o = out + (long)b * C * Vo + v;
+        for (int c = 0; c < C; ++c) {
+            float tc = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) tc += tl[i] == c ? u[i] : 0.f;
+            o[(long)c * Vo] = tc;
+        }
+    }
+}
+
 }  // namespace
 
 PULPO_API size_t pulpo_warp_labels_ws_bytes(int B, int C) { return sizeof(unsigned long long) * 3 * (size_t)std::max(B, 0) * std::max(C, 0); }
@@ -431,6 +607,77 @@ PULPO_API int pulpo_warp_labels_soft_dice(const float* df, const void* labels, c
     if (rc) return rc;
     hipLaunchKernelGGL(soft_dice_from_sums_kernel, dim3(1), dim3(64), 0, st, sums, B * C, dice, mean);
     return pulpo::check_launch("warp_labels_soft_dice finish");
+}
+
+// The Dice term of the training step from label maps: the sums of pulpo_warp_labels_soft_dice, finished into the loss,
+// the per-class Dice and the (B, C, 2) coefficient table of pulpo_label_dice_bwd
+PULPO_API int pulpo_label_dice_fwd(const float* df, const void* labels, const void* target, int ldt, int C, float dice_factor, float* loss, float* dice,
+                                   float* coef, void* ws, int* flag, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, int Dt, int Ht, int Wt,
+                                   void* stream) {
+    PULPO_REQUIRE(df && labels && target && loss && dice && coef && ws && flag && B > 0 && B <= 65535 && (ldt == 0 || ldt == 1) && C >= 1 &&
+                      C <= kMaxClasses && dice_factor != 0.f,
+                  "label_dice_fwd: bad arguments (1 <= C <= 256, B <= 65535)");
+    PULPO_REQUIRE(Dg >= 1 && Hg > 1 && Wg > 1 && Di > 0 && Hi > 0 && Wi > 0 && Dt > 0 && Ht > 0 && Wt > 0 && (Dg > 1 || (Di == 1 && Dt == 1)),
+                  "label_dice_fwd: grid H, W must be > 1 (depth 1 = 2-D form, with depth-1 label maps)");
+    PULPO_REQUIRE((long)Dg * Hg * Wg < (1L << 31), "label_dice_fwd: grids of 2^31 voxels and more are not supported");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st);
+    if (e == hipSuccess) e = hipMemsetAsync(ws, 0, pulpo_warp_labels_ws_bytes(B, C), st);
+    if (e != hipSuccess) return pulpo::fail((int)e, "label_dice_fwd memset: %s", hipGetErrorString(e));
+    const long Vg = (long)Dg * Hg * Wg;
+    const dim3 grid(eblocks(Vg, std::max(1, 2048 / B)), B);
+    unsigned long long* sums = (unsigned long long*)ws;
+    if (ldt == 0)
+        hipLaunchKernelGGL(warp_labels_soft_dice_kernel<uint8_t>, grid, dim3(256), 0, st, df, (const uint8_t*)labels, (const uint8_t*)target, C, sums,
+                           flag, Dg, Hg, Wg, Di, Hi, Wi, Dt, Ht, Wt);
+    else
+        hipLaunchKernelGGL(warp_labels_soft_dice_kernel<int32_t>, grid, dim3(256), 0, st, df, (const int32_t*)labels, (const int32_t*)target, C, sums,
+                           flag, Dg, Hg, Wg, Di, Hi, Wi, Dt, Ht, Wt);
+    int rc = pulpo::check_launch("label_dice_fwd");
+    if (rc) return rc;
+    hipLaunchKernelGGL(label_dice_finish_kernel, dim3(1), dim3(64), 0, st, sums, B * C, (double)Vg / (double)dice_factor, dice, coef, loss);
+    return pulpo::check_launch("label_dice_fwd finish");
+}
+
+PULPO_API int pulpo_label_dice_bwd(const float* df, const void* labels, const void* target, int ldt, int C, const float* coef, const float* gup,
+                                   float* ddf, int B, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, int Dt, int Ht, int Wt, void* stream) {
+    PULPO_REQUIRE(df && labels && target && coef && gup && ddf && B > 0 && B <= 65535 && (ldt == 0 || ldt == 1) && C >= 1 && C <= kMaxClasses,
+                  "label_dice_bwd: bad arguments (1 <= C <= 256, B <= 65535)");
+    PULPO_REQUIRE(Dg >= 1 && Hg > 1 && Wg > 1 && Di > 0 && Hi > 0 && Wi > 0 && Dt > 0 && Ht > 0 && Wt > 0 && (Dg > 1 || (Di == 1 && Dt == 1)),
+                  "label_dice_bwd: grid H, W must be > 1 (depth 1 = 2-D form, with depth-1 label maps)");
+    PULPO_REQUIRE((long)Dg * Hg * Wg < (1L << 31), "label_dice_bwd: grids of 2^31 voxels and more are not supported");
+    hipStream_t st = (hipStream_t)stream;
+    const long Vg = (long)Dg * Hg * Wg;
+    const dim3 grid((unsigned)((Vg + 255) / 256), B);
+    if (ldt == 0)
+        hipLaunchKernelGGL(label_dice_bwd_kernel<uint8_t>, grid, dim3(256), 0, st, df, (const uint8_t*)labels, (const uint8_t*)target, C, coef, gup, ddf,
+                           Dg, Hg, Wg, Di, Hi, Wi, Dt, Ht, Wt);
+    else
+        hipLaunchKernelGGL(label_dice_bwd_kernel<int32_t>, grid, dim3(256), 0, st, df, (const int32_t*)labels, (const int32_t*)target, C, coef, gup, ddf,
+                           Dg, Hg, Wg, Di, Hi, Wi, Dt, Ht, Wt);
+    return pulpo::check_launch("label_dice_bwd");
+}
+
+PULPO_API int pulpo_labels_pool2(const void* labels, int ldt, int C, float* out, int B, int D, int H, int W, void* stream) {
+    PULPO_REQUIRE(labels && out && B > 0 && B <= 65535 && (ldt == 0 || ldt == 1) && C >= 1 && D > 0 && H > 0 && W > 0, "labels_pool2: bad arguments");
+    PULPO_REQUIRE((long)D * H * W < (1L << 31), "labels_pool2: maps of 2^31 voxels and more are not supported");
+    const int Do = (D + 1) / 2, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+    const dim3 grid(eblocks((long)Do * Ho * Wo, std::max(1, 4096 / B)), B);
+    hipStream_t st = (hipStream_t)stream;
+    if (ldt == 0) hipLaunchKernelGGL(labels_pool2_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t*)labels, out, C, D, H, W, Do, Ho, Wo);
+    else hipLaunchKernelGGL(labels_pool2_kernel<int32_t>, grid, dim3(256), 0, st, (const int32_t*)labels, out, C, D, H, W, Do, Ho, Wo);
+    return pulpo::check_launch("labels_pool2");
+}
+
+PULPO_API int pulpo_labels_resize(const void* labels, int ldt, int C, float* out, int B, int Dt, int Ht, int Wt, int Do, int Ho, int Wo, void* stream) {
+    PULPO_REQUIRE(labels && out && B > 0 && B <= 65535 && (ldt == 0 || ldt == 1) && C >= 1 && Dt > 0 && Ht > 0 && Wt > 0 && Do > 0 && Ho > 0 && Wo > 0,
+                  "labels_resize: bad arguments");
+    PULPO_REQUIRE((long)Do * Ho * Wo < (1L << 31), "labels_resize: outputs of 2^31 voxels and more are not supported");
+    const dim3 grid(eblocks((long)Do * Ho * Wo, std::max(1, 4096 / B)), B);
+    hipStream_t st = (hipStream_t)stream;
+    if (ldt == 0) hipLaunchKernelGGL(labels_resize_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t*)labels, out, C, Dt, Ht, Wt, Do, Ho, Wo);
+    else hipLaunchKernelGGL(labels_resize_kernel<int32_t>, grid, dim3(256), 0, st, (const int32_t*)labels, out, C, Dt, Ht, Wt, Do, Ho, Wo);
+    return pulpo::check_launch("labels_resize");
 }
 
 PULPO_API int pulpo_labels_check(const void* labels, int ldt, int64_t n, int C, int* flag, void* stream) {

@@ -196,9 +196,12 @@ class HierarchicalReconstructionLoss(nn.Module):
         return MIND_loss_masked(y_hat_l, y_target, pair[0], pair[1], self.mind_dilation, self.mind_eps)
 
     def forward(self, y_hat, y, y_hat_seg=None, seg_y=None, gamma: float = 0.05, dice_factor: int = 1,
-                masks: Optional[Dict[int, Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]] = None):
+                masks: Optional[Dict[int, Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]] = None,
+                dice_terms: Optional[Dict[int, torch.Tensor]] = None):
         """masks (not in the reference): {level: (mask_a, mask_b)}, weight volumes at the level's size, either of a pair may be None; a level
-        with a pair uses the masked NCC / MSE / MIND term (cost weighted by mask_a * mask_b), the Dice term is unchanged"""
+        with a pair uses the masked NCC / MSE / MIND term (cost weighted by mask_a * mask_b), the Dice term is unchanged.
+        dice_terms (not in the reference): {level: the level's Dice term}, computed by the caller (PULPo.label_dice_terms, from label maps);
+        dice_terms[l] stands in for Soft_dice_loss(y_hat_seg[l], ...), and y_hat_seg / seg_y are not read"""
         single = len(self.recon_loss) == 1 and self.recon_loss[0] in ("mse", "ncc", "dice", "mind")
         loss = 0.0
         all_levels, terms = {}, {}
@@ -224,7 +227,9 @@ class HierarchicalReconstructionLoss(nn.Module):
                 term = term + w * self._ncc(l, y_hat[l], y_target, pair, gamma)
             if "mind" in self.recon_loss:
                 term = term + w * self._mind(y_hat[l], y_target, pair)
-            if "dice" in self.recon_loss:
+            if "dice" in self.recon_loss and dice_terms is not None:
+                term = term + w * dice_terms[l]
+            elif "dice" in self.recon_loss:
                 seg_size = y_hat_seg[l].shape[2:]
                 seg_target = seg_y if tuple(seg_size) == tuple(seg_y.shape[2:]) else ops.resize_trilinear(seg_y, seg_size)
                 term = term + w * Soft_dice_loss(y_hat_seg[l], seg_target, dice_factor=dice_factor)

@@ -54,6 +54,7 @@ class PULPo(ABC, LightningModule):
         mask: bool = False,
         nondiagonal: bool = False,
         cp_depth: int = 3,
+        num_classes: Optional[int] = None,
         mind_dilation: int = 2,
         mind_eps: float = 1e-5,
     ) -> None:
@@ -70,6 +71,7 @@ class PULPo(ABC, LightningModule):
         self.input_size = input_size
         self.ndims = len(input_size)
         self.cp_depth = cp_depth
+        self.num_classes = None if num_classes is None else int(num_classes)      # classes of integer segmentation maps (label_dice_terms)
         # floor division here, ceil in Autoencoder.level_sizes: reference quirk (models.py:69 vs pulpo.py:95)
         self.level_sizes = {l: torch.tensor(self.input_size) // (2 ** (l + self.lk_offset)) for l in range(latent_levels)}
 
@@ -149,14 +151,19 @@ class PULPo(ABC, LightningModule):
         outs = self.autoencoder(x, acts)
         mus, sigmas, samples, velocity_fields, individual_dfs, combined_dfs, final_dfs, y_hat = outs
         prior_mus, prior_sigmas = self.prior(mus, sigmas)
-        if "dice" in self.hparams.recon_loss:
+        dice_terms = None
+        if "dice" in self.hparams.recon_loss and self._label_maps(seg_x, seg_y):
+            dice_terms = self.label_dice_terms(final_dfs, seg_x, seg_y)        # integer label maps: no one-hot volume
+            y_hat_seg = {k: None for k in final_dfs}
+        elif "dice" in self.hparams.recon_loss:
             y_hat_seg = self.transform_segmentation(final_dfs, seg_x)
         else:
             y_hat_seg = {k: None for k in final_dfs}
         kl, kl_levels = self.hierarchical_kl_loss(prior_mus, prior_sigmas, mus, sigmas, scale=self.beta)       # (kl * beta, beta * levels: models.py:161-162)
         masks = self.level_masks(final_dfs, mask_x, mask_y)
         rec, rec_levels = self.hierarchical_recon_loss(y_hat, y, y_hat_seg, seg_y, gamma=self.hparams.gamma, dice_factor=self.hparams.dice_factor,
-                                                       **({} if masks is None else {"masks": masks}))
+                                                       **({} if masks is None else {"masks": masks}),
+                                                       **({} if dice_terms is None else {"dice_terms": dice_terms}))
         reg, reg_levels = self.hierarchical_regularization(final_dfs, lamb=self.hparams.lamb)
         total = kl + rec + reg
         return outs, (prior_mus, prior_sigmas), (total, kl, rec, reg), (kl_levels, rec_levels, reg_levels)
@@ -339,6 +346,45 @@ class PULPo(ABC, LightningModule):
                 level_seg[l] = ops.avg_pool2(level_seg[l - 1])
             level_seg[0] = seg
         return {k: self.autoencoder.decoders[k].spatial_transform(dfs[k], level_seg[k]) for k in dfs}
+
+    @staticmethod
+    def _label_maps(seg_x, seg_y) -> bool:
+        """do the batch's segmentations arrive as integer label maps (B, 1, ...)?  Float (B, C, ...) one-hot maps take transform_segmentation"""
+        integer = [torch.is_tensor(s) and s.numel() > 0 and not s.is_floating_point() and s.dtype != torch.bool for s in (seg_x, seg_y)]
+        if integer[0] != integer[1]:
+            raise ValueError("segmentations: seg_x and seg_y must both be integer label maps (B, 1, ...) or both float one-hot maps (B, C, ...)")
+        return integer[0]
+
+    def label_dice_terms(self, final_dfs: Dict[int, torch.Tensor], seg_x: torch.Tensor, seg_y: torch.Tensor) -> Dict[int, torch.Tensor]:
+        """{level: Soft_dice_loss(transform_segmentation(final_dfs, one_hot(seg_x))[level], one_hot(seg_y) resized to the level)} from integer
+        label maps (B, 1, ...), without a full-resolution one-hot volume and without a host read.  A level whose moving map is the
+        full-resolution segmentation - level 0, and every level of df_resolution "full_res" - is one ops.label_dice_loss; the coarse levels
+        of "level_res" warp transform_segmentation's pooled chain, started from the label map by ops.labels_soft_map(pool2=True), against
+        ops.labels_soft_map(size=level).  Labels outside [0, num_classes) count for no class: range-check the maps once where they are loaded."""
+        if self.num_classes is None:
+            raise ValueError("integer segmentation maps need the number of classes: build the model with PULPo(num_classes=...)")
+        C = self.num_classes
+        maps = []
+        for name, s in (("seg_x", seg_x), ("seg_y", seg_y)):
+            if s.dim() != self.ndims + 2 or s.shape[1] != 1:
+                raise ValueError(f"{name}: an integer label map (B, 1, ...) expected, got {tuple(s.shape)}")
+            maps.append(s if s.dtype in (torch.uint8, torch.int32) else s.to(torch.int32))
+        seg_x, seg_y = maps
+        dice_factor = self.hparams.dice_factor
+        full = [l for l in final_dfs if l == 0 or self.df_resolution == "full_res"]
+        terms = {l: ops.label_dice_loss(final_dfs[l], seg_x, C, seg_y, dice_factor, check=False) for l in full}
+        coarse = sorted(l for l in final_dfs if l not in terms)
+        if coarse:
+            # transform_segmentation's chain: level l >= 1 is the map pooled lk_offset + l times (level 0 itself uses the unpooled map)
+            soft, pooled = ops.labels_soft_map(seg_x, C, pool2=True), 1
+            for l in range(1, max(coarse) + 1):
+                while pooled < self.lk_offset + l:
+                    soft, pooled = ops.avg_pool2(soft), pooled + 1
+                if l in final_dfs:
+                    warped = self.autoencoder.decoders[l].spatial_transform(final_dfs[l], soft)
+                    target = ops.labels_soft_map(seg_y, C, size=tuple(final_dfs[l].shape[2:]))
+                    terms[l] = ops.soft_dice_loss(warped, target, dice_factor)
+        return terms
 
     # ------------------------------------------------------------------------------------------------ optimizer + Lightning's backward hooks
     # The reference leaves the step to Lightning: `return total_loss` (models.py:196) -> Lightning's closure runs optimizer_zero_grad,

@@ -2868,6 +2868,105 @@ def map_ncc(a, b):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ Dice term from label maps
+def _label_map5(t: torch.Tensor, B: int, name: str) -> torch.Tensor:
+    if t.dim() != 5 or t.shape[1] != 1 or t.shape[0] != B:
+        raise PulpoHipError(f"{name} map (B, 1, ...) with B = {B} expected, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+class _LabelDice(torch.autograd.Function):
+    """(loss, dice (B, C)) of a field (B,3,Dg,Hg,Wg) or (B,2,H,W) and two contiguous (B,1,D,H,W) label maps of one dtype; saves the planar field,
+    the maps and the (B, C, 2) coefficient table - nothing C times the volume.  The gradient has the caller's channel count, contiguous."""
+
+    @staticmethod
+    def forward(ctx, df, labels, target, C: int, dice_factor: float, flag):
+        ctx.two_d = _is2d(df)
+        df = planar(_lift_field(df) if ctx.two_d else df)
+        B = df.shape[0]
+        dev = df.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        dice = torch.empty((B, C), device=dev, dtype=torch.float32)
+        coef = torch.empty((B, C, 2), device=dev, dtype=torch.float32)
+        ws = torch.empty(lib.query("pulpo_warp_labels_ws_bytes", B, C), device=dev, dtype=torch.uint8)
+        dims = [int(v) for v in (*df.shape[2:], *labels.shape[2:], *target.shape[2:])]
+        lib.call("pulpo_label_dice_fwd", _ptr(df), _ptr(labels), _ptr(target), _LABEL_DT[labels.dtype], C, dice_factor, _ptr(loss), _ptr(dice),
+                 _ptr(coef), _ptr(ws), _int_ptr(flag, 0), B, *dims, _stream())
+        ctx.save_for_backward(df, labels, target, coef)
+        ctx.meta = (C, dims)
+        ctx.mark_non_differentiable(dice)
+        return loss, dice
+
+    @staticmethod
+    def backward(ctx, g, _gdice):
+        df, labels, target, coef = ctx.saved_tensors
+        C, dims = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        ddf = torch.empty_like(df)
+        gup = g.detach().to(torch.float32).contiguous()                 # read on the device, like pulpo_dice_bwd's gscale: no host synchronisation
+        t0 = _hbm_begin("label_dice_bwd")
+        lib.call("pulpo_label_dice_bwd", _ptr(df), _ptr(labels), _ptr(target), _LABEL_DT[labels.dtype], C, _ptr(coef), _ptr(gup), _ptr(ddf),
+                 df.shape[0], *dims, _stream())
+        # the field read and its gradient written once; a label byte per voxel of either map when the grids agree
+        _hbm_end(t0, "label_dice_bwd", 4.0 * 2 * df.numel() + labels.element_size() * (labels.numel() + target.numel()))
+        return (_unlift_field(ddf).contiguous() if ctx.two_d else ddf), None, None, None, None, None
+
+
+def label_dice_loss(df, labels, num_classes: int, target, dice_factor=1, check: bool = True, return_dice: bool = False):
+    """Soft_dice_loss(warp3d(df, one_hot(labels)), F.interpolate(one_hot(target), size = df's grid), dice_factor) (src/losses.py:137-145, the Dice
+    term of HierarchicalReconstructionLoss) from integer label maps: no one-hot tensor in the forward pass, the backward pass or the saved
+    state.  df (B,3,D,H,W) fp32 (2-D: (B,2,H,W)); labels and target (B,1,...) uint8 / int32, each on a grid of its own.  Differentiable with
+    respect to df only; the gradient is one gather per grid voxel, without atomics: two calls give the same bits.  check=True range-checks both
+    maps (one host read) and raises IndexError for a label outside [0, num_classes); check=False reads nothing back (a label out of range then
+    counts for no class) and can be captured into a HIP graph.  return_dice: also the per-class Dice (B, C), ops.warp_labels_soft_dice's values."""
+    _require_gpu(df)
+    _require_labels(labels, target)
+    if target is None or labels is None:
+        raise ValueError("label_dice_loss: a moving and a target label map are required")
+    if df.dim() not in (4, 5) or df.shape[1] != df.dim() - 2:
+        raise PulpoHipError(f"label_dice_loss: field (B,3,D,H,W) or (B,2,H,W) expected, got {tuple(df.shape)}")
+    if _is2d(df):
+        labels, target = _lift(labels), _lift(target)
+    B, C = int(df.shape[0]), int(num_classes)
+    labels = _label_map5(labels.detach(), B, "label")
+    target = _label_map5(target.detach().to(labels.dtype), B, "target")
+    flag = torch.zeros(3, device=df.device, dtype=torch.int32)
+    if check:
+        _check_labels(labels, C, flag, 1)
+        _check_labels(target, C, flag, 2)
+    loss, dice = _LabelDice.apply(df, labels, target, C, float(dice_factor), flag)
+    if check:
+        _raise_on_flag(flag, "label_dice_loss")
+    return (loss, dice) if return_dice else loss
+
+
+@torch.no_grad()
+def labels_soft_map(labels, num_classes: int, pool2: bool = False, size=None):
+    """A pooled or resized one-hot map from an integer label map, without the full-resolution one-hot volume.  labels (B,1,...) uint8 / int32.
+    pool2=True: (B, C, ceil(S / 2)) fp32 equal to avg_pool2(one_hot(labels)) bit for bit; size=(...): (B, C, size) fp32 =
+    F.interpolate(one_hot(labels), size, tri/bilinear, align_corners=False).  Exactly one of the two.  A label outside [0, num_classes) counts
+    for no class.  No autograd, no host read."""
+    if bool(pool2) == (size is not None):
+        raise ValueError("labels_soft_map: give exactly one of pool2=True and size=")
+    _require_labels(labels)
+    two_d = _is2d(labels)
+    lab = _label_map5(_lift(labels) if two_d else labels, int(labels.shape[0]), "label")
+    B, C = int(lab.shape[0]), int(num_classes)
+    D, H, W = (int(v) for v in lab.shape[2:])
+    if pool2:
+        out = torch.empty((B, C, (D + 1) // 2, (H + 1) // 2, (W + 1) // 2), device=lab.device, dtype=torch.float32)
+        lib.call("pulpo_labels_pool2", _ptr(lab), _LABEL_DT[lab.dtype], C, _ptr(out), B, D, H, W, _stream())
+    else:
+        size = tuple(int(s) for s in size)
+        if len(size) != (2 if two_d else 3) or min(size) < 1:
+            raise ValueError(f"labels_soft_map: a size of {2 if two_d else 3} extents >= 1 expected, got {size}")
+        Do, Ho, Wo = ((1,) + size) if two_d else size
+        out = torch.empty((B, C, Do, Ho, Wo), device=lab.device, dtype=torch.float32)
+        lib.call("pulpo_labels_resize", _ptr(lab), _LABEL_DT[lab.dtype], C, _ptr(out), B, D, H, W, Do, Ho, Wo, _stream())
+    return out.squeeze(2) if two_d else out
+
+
 # ------------------------------------------------------------------------------------------------ boundary metrics (DESIGN.md section 3l)
 EDT_INF = 1 << 29          # edt_sq of an item without a feature voxel (PULPO_EDT_INF)
 
