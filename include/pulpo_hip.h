@@ -245,6 +245,8 @@ int pulpo_ncc_bwd(const float* I, const float* J, const float* S, float* T /*6N 
  *   out[1] = d out[0] / d sum0  (0 when M == 0, or when root and q == 0): the backward entry points take  upstream * out[1]  as gscale
  *   out[2] = M / count,  out[3] = M
  * ncc_masked:    scale = -gamma * V                   -> -gamma * V * sum(m cc) / M;     bwd: gJ = coef * gscale * (box(m a) + 2 J box(m b) + I box(m c))
+ *                the launch sequences of pulpo_ncc_fwd / pulpo_ncc_bwd with the MASKED instantiation of the one kernel m enters: the last (D) pass
+ *                (box_march_kernel<5, PAD, 1, true> / ncc_final_kernel<true>) forward, ncc_abc_kernel<true> backward
  * sqdiff_masked: a, b planar (B,C,V), m broadcast over the C channels, sum of m counted once per voxel;
  *                scale = V / C -> L2_masked, scale = 1 / C with root -> RMSE_masked;  bwd: ga = coef * gscale * 2 m (a - b) */
 int pulpo_ncc_masked_fwd(const float* I, const float* J, const float* wa, const float* wb /*nullable*/, float* S /*5N, saved*/,

@@ -134,15 +134,6 @@ def _params_of(theta: torch.Tensor, r: float, dof: int, nd: int) -> torch.Tensor
     return torch.cat([torch.where(s > 1e-12, w * ang / s.clamp_min(1e-300), w), t], dim=1).float()
 
 
-def _similarity(loss: str, pred, true, wx, wy, win: int) -> torch.Tensor:
-    pair = None if wx is None and wy is None else ((wx, wy) if wx is not None else (wy, None))
-    if loss == "ncc":
-        return ops.ncc_loss(pred, true, win, 1.0) if pair is None else ops.ncc_loss_masked(pred, true, pair[0], pair[1], win, 1.0)
-    if loss == "mse":
-        return ops.l2_loss(pred, true) if pair is None else ops.l2_loss_masked(pred, true, pair[0], pair[1])
-    return ops.mind_loss(pred, true) if pair is None else ops.mind_loss_masked(pred, true, pair[0], pair[1])
-
-
 def _per_level(given, default, levels: int):
     """one entry per level, coarsest first: the given ones, or the default's last `levels` (its first repeated for deeper pyramids)"""
     if given is not None:
@@ -209,7 +200,7 @@ def fit(x: torch.Tensor, y: torch.Tensor, *, dof: int = 12, levels: int = 3, ite
         xl, yl, mxl, myl = pyr[lvl]
         theta = _theta_of(P, r0 / 2 ** lvl, dof, nd)
         wx = ops.warp_mask(ops.affine_field(theta, xl.shape[2:]), mxl) if mxl is not None else None
-        return _similarity(loss, ops.affine_warp(theta, xl), yl, wx, myl, int(win[k]))
+        return ops.similarity(loss, ops.affine_warp(theta, xl), yl, wx, myl, gamma=1.0, win=int(win[k]))
 
     row = 0
     for k, lvl in enumerate(reversed(range(levels))):

@@ -21,6 +21,37 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
     return t;   // valid in thread 0
 }
 
+// the squared local correlation coefficient of a voxel from its five window sums s = box of (I, J, I*I, J*J, I*J): losses.py:125-132, same
+// expression order
+__device__ __forceinline__ float ncc_cc(const float* s, float nwin) {
+    const float uI = s[0] / nwin, uJ = s[1] / nwin;
+    const float cross = s[4] - uJ * s[0] - uI * s[1] + uI * uJ * nwin;
+    const float Iv = s[2] - 2.f * uI * s[0] + uI * uI * nwin;
+    const float Jv = s[3] - 2.f * uJ * s[1] + uJ * uJ * nwin;
+    return cross * cross / (Iv * Jv + 1e-8f);
+}
+
+// ---- cost-function mask, the MASKED option of the NCC kernels below: a voxel's weight is m = wa * wb (wb nullable).  Every kernel of the family
+// has the two plane pointers among its arguments; the unmasked instantiations never read them
+__device__ __forceinline__ float mask_weight(const float* __restrict__ wa, const float* __restrict__ wb, long e) {
+    return wb != nullptr ? wa[e] * wb[e] : wa[e];
+}
+
+// a block's partial sums: partial[block] = sum of local; MASKED: partial[2 block] = sum of local (m cc), partial[2 block + 1] = sum of msum (m)
+template <bool MASKED>
+__device__ __forceinline__ void store_block_partials(float local, float msum, float* sh, float* __restrict__ partial) {
+    const float t = block_sum_256(local, sh);
+    if constexpr (MASKED) {
+        const float tm = block_sum_256(msum, sh);
+        if (threadIdx.x == 0) {
+            partial[2 * blockIdx.x] = t;
+            partial[2 * blockIdx.x + 1] = tm;
+        }
+    } else {
+        if (threadIdx.x == 0) partial[blockIdx.x] = t;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ box sums
 // W-axis pass.  MODE 0: in = (I, J) -> out = box_x of (I, J, I*I, J*J, I*J) [5 channels, planar stride N]
 //               MODE 1: in = nch planes (stride N) -> out = box_x of each
@@ -78,11 +109,14 @@ __global__ __launch_bounds__(256) void box_axis_kernel(const float* __restrict__
     }
 }
 
-// last (D) pass fused with the correlation coefficient and its block reduction.  S (5 channels) is kept for backward.
+// last (D) pass fused with the correlation coefficient and its block reduction.  S (5 channels) is kept for backward.  MASKED: the window
+// sums are the same, the voxel's cc is weighted by m (two reduced columns, store_block_partials)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void ncc_final_kernel(const float* __restrict__ in, float* __restrict__ S, long N, int extent, long stride, int pad,
-                                                          float nwin, float* __restrict__ partial) {
+                                                          float nwin, const float* __restrict__ wa, const float* __restrict__ wb, float* __restrict__ partial) {
     __shared__ float sh[4];
     float local = 0.f;
+    [[maybe_unused]] float msum = 0.f;
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < N; e += (long)gridDim.x * blockDim.x) {
         const int pos = (int)((e / stride) % extent);
         const int lo = max(-pad, -pos), hi = min(pad, extent - 1 - pos);
@@ -95,50 +129,15 @@ __global__ __launch_bounds__(256) void ncc_final_kernel(const float* __restrict_
             s[c] = acc;
             S[c * N + e] = acc;
         }
-        // losses.py:125-132, same expression order
-        const float uI = s[0] / nwin, uJ = s[1] / nwin;
-        const float cross = s[4] - uJ * s[0] - uI * s[1] + uI * uJ * nwin;
-        const float Iv = s[2] - 2.f * uI * s[0] + uI * uI * nwin;
-        const float Jv = s[3] - 2.f * uJ * s[1] + uJ * uJ * nwin;
-        local += cross * cross / (Iv * Jv + 1e-8f);
-    }
-    const float t = block_sum_256(local, sh);
-    if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
-
-// ncc_final_kernel with a cost-function mask (m = wa * wb, wb nullable): the window sums are those of the unmasked kernel, the voxel's
-// cc is weighted by m; partial[2 blk] = sum of m * cc, partial[2 blk + 1] = sum of m
-__global__ __launch_bounds__(256) void ncc_masked_final_kernel(const float* __restrict__ in, float* __restrict__ S, long N, int extent, long stride, int pad,
-                                                                 float nwin, const float* __restrict__ wa, const float* __restrict__ wb,
-                                                                 float* __restrict__ partial) {
-    __shared__ float sh[4];
-    float local = 0.f, msum = 0.f;
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < N; e += (long)gridDim.x * blockDim.x) {
-        const int pos = (int)((e / stride) % extent);
-        const int lo = max(-pad, -pos), hi = min(pad, extent - 1 - pos);
-        float s[5];
-#pragma unroll
-        for (int c = 0; c < 5; ++c) {
-            const float* q = in + c * N + e;
-            float acc = 0.f;
-            for (int k = lo; k <= hi; ++k) acc += q[k * stride];
-            s[c] = acc;
-            S[c * N + e] = acc;
+        if constexpr (MASKED) {
+            const float m = mask_weight(wa, wb, e);
+            local += m * ncc_cc(s, nwin);
+            msum += m;
+        } else {
+            local += ncc_cc(s, nwin);
         }
-        const float uI = s[0] / nwin, uJ = s[1] / nwin;
-        const float cross = s[4] - uJ * s[0] - uI * s[1] + uI * uJ * nwin;
-        const float Iv = s[2] - 2.f * uI * s[0] + uI * uI * nwin;
-        const float Jv = s[3] - 2.f * uJ * s[1] + uJ * uJ * nwin;
-        const float m = wb != nullptr ? wa[e] * wb[e] : wa[e];
-        local += m * (cross * cross / (Iv * Jv + 1e-8f));
-        msum += m;
     }
-    const float t = block_sum_256(local, sh);
-    const float tm = block_sum_256(msum, sh);
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = t;
-        partial[2 * blockIdx.x + 1] = tm;
-    }
+    store_block_partials<MASKED>(local, msum, sh, partial);
 }
 
 // ---- marching form of the strided passes (windows up to 11): a thread walks a segment of one line along the axis and keeps the window's
@@ -146,16 +145,14 @@ __global__ __launch_bounds__(256) void ncc_masked_final_kernel(const float* __re
 // at 160^3 the D pass's working set - 9 planes x 5 channels, 4.6 MB - exceeds an XCD's L2 and the pass ran at 0.9 TB/s).  The window
 // is summed in ascending position order with zeros outside the volume: bit-identical to the tap loops above.
 //   MODE 0: out = box(in)                                  (nch = NCH channels)
-//   MODE 1: S = box(in), partial[block] = sum of cc        (ncc_final_kernel)
-//   MODE 2: gJ = k0 (box(a) + 2 J box(b) + I box(c))       (ncc_bwd_final_kernel)
-//   MODE 3: MODE 1 with a mask: partial[2 block] = sum of m cc, partial[2 block + 1] = sum of m   (ncc_masked_final_kernel);
-//           the mask planes wa and wb (nullable) arrive in the I and J arguments, which MODE 1 leaves unused
+//   MODE 1: S = box(in), partial = the block sums of cc    (ncc_final_kernel<MASKED>; the only mode that reads MASKED, wa and wb)
+//   MODE 2: gJ = k0 (box(a) + 2 J box(b) + I box(c))       (ncc_bwd_final_kernel; the only mode that reads I, J, gscale and coef)
 // Work items = (segment, group of 256 lines), distributed over the workgroups in a strided loop.
-template <int NCH, int PAD, int MODE>
+template <int NCH, int PAD, int MODE, bool MASKED>
 __global__ __launch_bounds__(256) void box_march_kernel(const float* __restrict__ in, float* __restrict__ out, long N, long nlines, int extent,
                                                           long stride, int seglen, int nseg, float nwin, float* __restrict__ partial,
                                                           const float* __restrict__ I, const float* __restrict__ J, const float* __restrict__ gscale,
-                                                          float coef) {
+                                                          float coef, const float* __restrict__ wa, const float* __restrict__ wb) {
     constexpr int WIN = 2 * PAD + 1;
     __shared__ float sh[4];
     const long nlg = (nlines + 255) / 256;
@@ -203,22 +200,13 @@ __global__ __launch_bounds__(256) void box_march_kernel(const float* __restrict_
                     } else if constexpr (MODE == 1) {
 #pragma unroll
                         for (int c = 0; c < NCH; ++c) out[c * N + e] = sum[c];
-                        // losses.py:125-132, same expression order
-                        const float uI = sum[0] / nwin, uJ = sum[1] / nwin;
-                        const float cross = sum[4] - uJ * sum[0] - uI * sum[1] + uI * uJ * nwin;
-                        const float Iv = sum[2] - 2.f * uI * sum[0] + uI * uI * nwin;
-                        const float Jv = sum[3] - 2.f * uJ * sum[1] + uJ * uJ * nwin;
-                        local += cross * cross / (Iv * Jv + 1e-8f);
-                    } else if constexpr (MODE == 3) {
-#pragma unroll
-                        for (int c = 0; c < NCH; ++c) out[c * N + e] = sum[c];
-                        const float uI = sum[0] / nwin, uJ = sum[1] / nwin;
-                        const float cross = sum[4] - uJ * sum[0] - uI * sum[1] + uI * uJ * nwin;
-                        const float Iv = sum[2] - 2.f * uI * sum[0] + uI * uI * nwin;
-                        const float Jv = sum[3] - 2.f * uJ * sum[1] + uJ * uJ * nwin;
-                        const float m = J != nullptr ? I[e] * J[e] : I[e];
-                        local += m * (cross * cross / (Iv * Jv + 1e-8f));
-                        msum += m;
+                        if constexpr (MASKED) {
+                            const float m = mask_weight(wa, wb, e);
+                            local += m * ncc_cc(sum, nwin);
+                            msum += m;
+                        } else {
+                            local += ncc_cc(sum, nwin);
+                        }
                     } else {
                         out[e] = k0 * (sum[0] + 2.f * J[e] * sum[1] + I[e] * sum[2]);
                     }
@@ -226,18 +214,7 @@ __global__ __launch_bounds__(256) void box_march_kernel(const float* __restrict_
             }
         }
     }
-    if constexpr (MODE == 1) {
-        const float t = block_sum_256(local, sh);
-        if (threadIdx.x == 0) partial[blockIdx.x] = t;
-    }
-    if constexpr (MODE == 3) {
-        const float t = block_sum_256(local, sh);
-        const float tm = block_sum_256(msum, sh);
-        if (threadIdx.x == 0) {
-            partial[2 * blockIdx.x] = t;
-            partial[2 * blockIdx.x + 1] = tm;
-        }
-    }
+    if constexpr (MODE == 1) store_block_partials<MASKED>(local, msum, sh, partial);
 }
 
 // segment length for the marching kernels: about 1024 work items where the lines allow, segments of at least 2 PAD positions
@@ -249,13 +226,14 @@ static inline void march_segments(long nlines, int extent, int pad, int& seglen,
     nseg = (extent + seglen - 1) / seglen;
 }
 
-template <int NCH, int MODE>
-static int launch_march(int pad, int grid, hipStream_t st, const float* in, float* out, long N, int extent, long stride, float nwin, float* partial,
-                        const float* I, const float* J, const float* gscale, float coef) {
+template <int NCH, int MODE, bool MASKED = false>
+static int launch_march(int pad, int grid, hipStream_t st, const float* in, float* out, long N, int extent, long stride, float nwin = 0.f,
+                        float* partial = nullptr, const float* I = nullptr, const float* J = nullptr, const float* gscale = nullptr, float coef = 0.f,
+                        const float* wa = nullptr, const float* wb = nullptr) {
     const long nlines = N / extent;
     int seglen, nseg;
     march_segments(nlines, extent, pad, seglen, nseg);
-#define PULPO_MARCH(P) hipLaunchKernelGGL((box_march_kernel<NCH, P, MODE>), dim3(grid), dim3(256), 0, st, in, out, N, nlines, extent, stride, seglen, nseg, nwin, partial, I, J, gscale, coef)
+#define PULPO_MARCH(P) hipLaunchKernelGGL((box_march_kernel<NCH, P, MODE, MASKED>), dim3(grid), dim3(256), 0, st, in, out, N, nlines, extent, stride, seglen, nseg, nwin, partial, I, J, gscale, coef, wa, wb)
     switch (pad) {
         case 1: PULPO_MARCH(1); break;
         case 2: PULPO_MARCH(2); break;
@@ -268,8 +246,11 @@ static int launch_march(int pad, int grid, hipStream_t st, const float* in, floa
     return pulpo::check_launch("ncc box march");
 }
 
-// backward stage 1: from the saved box sums form the three fields that get box-filtered again
-__global__ __launch_bounds__(256) void ncc_abc_kernel(const float* __restrict__ S, float* __restrict__ A, long N, float nwin) {
+// backward stage 1: from the saved box sums form the three fields that get box-filtered again.  MASKED: each weighted by the voxel's m,
+// d(sum m cc) = box(m a) + 2 J box(m b) + I box(m c)
+template <bool MASKED>
+__global__ __launch_bounds__(256) void ncc_abc_kernel(const float* __restrict__ S, float* __restrict__ A, long N, float nwin,
+                                                        const float* __restrict__ wa, const float* __restrict__ wb) {
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < N; e += (long)gridDim.x * blockDim.x) {
         const float SI = S[e], SJ = S[N + e], SII = S[2 * N + e], SJJ = S[3 * N + e], SIJ = S[4 * N + e];
         const float cross = SIJ - SI * SJ / nwin;
@@ -277,26 +258,14 @@ __global__ __launch_bounds__(256) void ncc_abc_kernel(const float* __restrict__ 
         const float Jv = SJJ - SJ * SJ / nwin;
         const float Dn = Iv * Jv + 1e-8f;
         const float r = cross / Dn;                       // cross / D
-        A[e] = -2.f * r * SI / nwin + 2.f * r * r * Iv * SJ / nwin;
-        A[N + e] = -r * r * Iv;
-        A[2 * N + e] = 2.f * r;
-    }
-}
-
-// ncc_abc_kernel with the voxel's three fields weighted by the mask m = wa * wb (wb nullable): d(sum m cc) = box(m a) + 2 J box(m b) + I box(m c)
-__global__ __launch_bounds__(256) void ncc_masked_abc_kernel(const float* __restrict__ S, float* __restrict__ A, long N, float nwin,
-                                                               const float* __restrict__ wa, const float* __restrict__ wb) {
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < N; e += (long)gridDim.x * blockDim.x) {
-        const float SI = S[e], SJ = S[N + e], SII = S[2 * N + e], SJJ = S[3 * N + e], SIJ = S[4 * N + e];
-        const float cross = SIJ - SI * SJ / nwin;
-        const float Iv = SII - SI * SI / nwin;
-        const float Jv = SJJ - SJ * SJ / nwin;
-        const float Dn = Iv * Jv + 1e-8f;
-        const float r = cross / Dn;
-        const float m = wb != nullptr ? wa[e] * wb[e] : wa[e];
-        A[e] = m * (-2.f * r * SI / nwin + 2.f * r * r * Iv * SJ / nwin);
-        A[N + e] = m * (-r * r * Iv);
-        A[2 * N + e] = m * (2.f * r);
+        float a = -2.f * r * SI / nwin + 2.f * r * r * Iv * SJ / nwin, b = -r * r * Iv, c = 2.f * r;
+        if constexpr (MASKED) {
+            const float m = mask_weight(wa, wb, e);
+            a = m * a, b = m * b, c = m * c;
+        }
+        A[e] = a;
+        A[N + e] = b;
+        A[2 * N + e] = c;
     }
 }
 
@@ -506,51 +475,58 @@ PULPO_API int pulpo_loss_blocks(int64_t n) { return eblocks(n, 1024); }
 // win^ndims of losses.py:124: a depth-1 volume is the reference's 2-D case (conv2d with a win x win window)
 static inline float ncc_window_count(int win, int D) { return D == 1 ? (float)(win * win) : (float)(win * win * win); }
 
-// I = y_true, J = y_pred, planar (B,1,D,H,W).  S: 5*N floats (saved for backward), T: 10*N floats scratch (N = B*D*H*W).
-// partial: pulpo_loss_blocks(N) floats.  loss = -gamma/B * sum(partial)  (finish with pulpo_colsum(scale = -gamma/B)).
-PULPO_API int pulpo_ncc_fwd(const float* I, const float* J, float* S, float* T, float* partial, int B, int D, int H, int W, int win, void* stream) {
-    PULPO_REQUIRE(I && J && S && T && partial && B > 0 && D > 0 && H > 0 && W > 0, "ncc_fwd: bad arguments");
-    PULPO_REQUIRE(win >= 1 && (win & 1) && win <= 31, "ncc_fwd: window must be odd and <= 31");
-    hipStream_t st = (hipStream_t)stream;
+// ---- NCC launch sequences.  I = y_true, J = y_pred, planar (B,1,D,H,W); N = B*D*H*W; wa == nullptr: unmasked, else the cost-function mask
+// m = wa * wb (wb nullable).  The mask enters one kernel of each sequence: the last (D) pass of the forward one, the abc kernel of the backward one.
+// (the entry points' argument check, each under its own name)
+#define PULPO_NCC_REQUIRE(name, pointers)                                                  \
+    PULPO_REQUIRE((pointers) && B > 0 && D > 0 && H > 0 && W > 0, name ": bad arguments"); \
+    PULPO_REQUIRE(win >= 1 && (win & 1) && win <= 31, name ": window must be odd and <= 31")
+
+// S: 5*N floats (saved for backward), T: 10*N floats scratch, partial: pulpo_loss_blocks(N) floats, masked twice as many (two columns)
+static int ncc_forward(const float* I, const float* J, const float* wa, const float* wb, float* S, float* T, float* partial, int B, int D, int H, int W,
+                       int win, hipStream_t st) {
     const long N = (long)B * D * H * W;
     const int pad = win / 2, span = 64 - 2 * pad, segs = pulpo::cdiv(W, span);
     const long nrows = (long)B * D * H;
+    const float nwin = ncc_window_count(win, D);
     float* T1 = T;
     float* T2 = T + 5 * N;
     hipLaunchKernelGGL(box_x_kernel<0>, dim3(eblocks(nrows * segs * 64)), dim3(256), 0, st, I, J, T1, N, nrows, W, pad, 5, segs);
     int rc = pulpo::check_launch("ncc box_x");
     if (rc) return rc;
     const bool march = pad >= 1 && pad <= 5;            // windows 3 .. 11 (the model's: 9, 7, 5, 3 from the finest level down)
-    if (march && H > 1) rc = launch_march<5, 0>(pad, eblocks(N, 1024), st, T1, T2, N, H, (long)W, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f);
+    if (march && H > 1) rc = launch_march<5, 0>(pad, eblocks(N, 1024), st, T1, T2, N, H, (long)W);
     else {
         hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N)), dim3(256), 0, st, T1, T2, N, 5, H, (long)W, pad);
         rc = pulpo::check_launch("ncc box_y");
     }
     if (rc) return rc;
-    if (march) return launch_march<5, 1>(pad, pulpo_loss_blocks(N), st, T2, S, N, D, (long)H * W, ncc_window_count(win, D), partial, nullptr, nullptr, nullptr, 0.f);
-    hipLaunchKernelGGL(ncc_final_kernel, dim3(pulpo_loss_blocks(N)), dim3(256), 0, st, T2, S, N, D, (long)H * W, pad, ncc_window_count(win, D), partial);
+    const int grid = pulpo_loss_blocks(N);
+    const long stride = (long)H * W;
+    if (march && wa) return launch_march<5, 1, true>(pad, grid, st, T2, S, N, D, stride, nwin, partial, nullptr, nullptr, nullptr, 0.f, wa, wb);
+    if (march) return launch_march<5, 1>(pad, grid, st, T2, S, N, D, stride, nwin, partial);
+    if (wa) hipLaunchKernelGGL(ncc_final_kernel<true>, dim3(grid), dim3(256), 0, st, T2, S, N, D, stride, pad, nwin, wa, wb, partial);
+    else hipLaunchKernelGGL(ncc_final_kernel<false>, dim3(grid), dim3(256), 0, st, T2, S, N, D, stride, pad, nwin, wa, wb, partial);
     return pulpo::check_launch("ncc final");
 }
 
-// gJ = gscale[0] * (-gamma/B) * d(sum cc)/dJ.   T: 6*N floats scratch.
-PULPO_API int pulpo_ncc_bwd(const float* I, const float* J, const float* S, float* T, const float* gscale, float coef, float* gJ, int B, int D, int H,
-                            int W, int win, void* stream) {
-    PULPO_REQUIRE(I && J && S && T && gJ && B > 0 && D > 0 && H > 0 && W > 0, "ncc_bwd: bad arguments");
-    PULPO_REQUIRE(win >= 1 && (win & 1) && win <= 31, "ncc_bwd: window must be odd and <= 31");
-    hipStream_t st = (hipStream_t)stream;
+// gJ = coef * gscale[0] * d(sum m cc)/dJ.  T: 6*N floats scratch
+static int ncc_backward(const float* I, const float* J, const float* S, const float* wa, const float* wb, float* T, const float* gscale, float coef,
+                        float* gJ, int B, int D, int H, int W, int win, hipStream_t st) {
     const long N = (long)B * D * H * W;
     const int pad = win / 2, span = 64 - 2 * pad, segs = pulpo::cdiv(W, span);
     const long nrows = (long)B * D * H;
     float* T1 = T;
     float* T2 = T + 3 * N;
-    hipLaunchKernelGGL(ncc_abc_kernel, dim3(eblocks(N)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D));
+    if (wa) hipLaunchKernelGGL(ncc_abc_kernel<true>, dim3(eblocks(N)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D), wa, wb);
+    else hipLaunchKernelGGL(ncc_abc_kernel<false>, dim3(eblocks(N)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D), wa, wb);
     int rc = pulpo::check_launch("ncc abc");
     if (rc) return rc;
     hipLaunchKernelGGL(box_x_kernel<1>, dim3(eblocks(nrows * segs * 64)), dim3(256), 0, st, T1, nullptr, T2, N, nrows, W, pad, 3, segs);
     rc = pulpo::check_launch("ncc bwd box_x");
     if (rc) return rc;
     const bool march = pad >= 1 && pad <= 5;
-    if (march && H > 1) rc = launch_march<3, 0>(pad, eblocks(N, 1024), st, T2, T1, N, H, (long)W, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f);
+    if (march && H > 1) rc = launch_march<3, 0>(pad, eblocks(N, 1024), st, T2, T1, N, H, (long)W);
     else {
         hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N)), dim3(256), 0, st, T2, T1, N, 3, H, (long)W, pad);
         rc = pulpo::check_launch("ncc bwd box_y");
@@ -561,62 +537,32 @@ PULPO_API int pulpo_ncc_bwd(const float* I, const float* J, const float* S, floa
     return pulpo::check_launch("ncc bwd final");
 }
 
-// pulpo_ncc_fwd with a cost-function mask: the W and H passes are the unmasked ones, the last (D) pass weights cc by m = wa * wb and
-// reduces two columns (sum of m cc, sum of m).  partial: 2 * pulpo_loss_blocks(N) floats; finish with pulpo_masked_finish(scale = -gamma V).
-PULPO_API int pulpo_ncc_masked_fwd(const float* I, const float* J, const float* wa, const float* wb, float* S, float* T, float* partial, int B, int D,
-                                   int H, int W, int win, void* stream) {
-    PULPO_REQUIRE(I && J && wa && S && T && partial && B > 0 && D > 0 && H > 0 && W > 0, "ncc_masked_fwd: bad arguments");
-    PULPO_REQUIRE(win >= 1 && (win & 1) && win <= 31, "ncc_masked_fwd: window must be odd and <= 31");
-    hipStream_t st = (hipStream_t)stream;
-    const long N = (long)B * D * H * W;
-    const int pad = win / 2, span = 64 - 2 * pad, segs = pulpo::cdiv(W, span);
-    const long nrows = (long)B * D * H;
-    float* T1 = T;
-    float* T2 = T + 5 * N;
-    hipLaunchKernelGGL(box_x_kernel<0>, dim3(eblocks(nrows * segs * 64)), dim3(256), 0, st, I, J, T1, N, nrows, W, pad, 5, segs);
-    int rc = pulpo::check_launch("ncc masked box_x");
-    if (rc) return rc;
-    const bool march = pad >= 1 && pad <= 5;
-    if (march && H > 1) rc = launch_march<5, 0>(pad, eblocks(N, 1024), st, T1, T2, N, H, (long)W, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f);
-    else {
-        hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N)), dim3(256), 0, st, T1, T2, N, 5, H, (long)W, pad);
-        rc = pulpo::check_launch("ncc masked box_y");
-    }
-    if (rc) return rc;
-    if (march) return launch_march<5, 3>(pad, pulpo_loss_blocks(N), st, T2, S, N, D, (long)H * W, ncc_window_count(win, D), partial, wa, wb, nullptr, 0.f);
-    hipLaunchKernelGGL(ncc_masked_final_kernel, dim3(pulpo_loss_blocks(N)), dim3(256), 0, st, T2, S, N, D, (long)H * W, pad, ncc_window_count(win, D), wa, wb,
-                       partial);
-    return pulpo::check_launch("ncc masked final");
+// loss = -gamma/B * sum(partial)  (finish with pulpo_colsum(scale = -gamma/B))
+PULPO_API int pulpo_ncc_fwd(const float* I, const float* J, float* S, float* T, float* partial, int B, int D, int H, int W, int win, void* stream) {
+    PULPO_NCC_REQUIRE("ncc_fwd", I && J && S && T && partial);
+    return ncc_forward(I, J, nullptr, nullptr, S, T, partial, B, D, H, W, win, (hipStream_t)stream);
 }
 
-// gJ = coef * gscale[0] * d(sum m cc)/dJ: the masked ncc_abc kernel, then the three box passes and the combine of pulpo_ncc_bwd.  T: 6*N floats.
+// gJ = gscale[0] * (-gamma/B) * d(sum cc)/dJ
+PULPO_API int pulpo_ncc_bwd(const float* I, const float* J, const float* S, float* T, const float* gscale, float coef, float* gJ, int B, int D, int H,
+                            int W, int win, void* stream) {
+    PULPO_NCC_REQUIRE("ncc_bwd", I && J && S && T && gJ);
+    return ncc_backward(I, J, S, nullptr, nullptr, T, gscale, coef, gJ, B, D, H, W, win, (hipStream_t)stream);
+}
+
+// pulpo_ncc_fwd with a cost-function mask; finish with pulpo_masked_finish(scale = -gamma V)
+PULPO_API int pulpo_ncc_masked_fwd(const float* I, const float* J, const float* wa, const float* wb, float* S, float* T, float* partial, int B, int D,
+                                   int H, int W, int win, void* stream) {
+    PULPO_NCC_REQUIRE("ncc_masked_fwd", I && J && wa && S && T && partial);
+    return ncc_forward(I, J, wa, wb, S, T, partial, B, D, H, W, win, (hipStream_t)stream);
+}
+
 PULPO_API int pulpo_ncc_masked_bwd(const float* I, const float* J, const float* S, const float* wa, const float* wb, float* T, const float* gscale,
                                    float coef, float* gJ, int B, int D, int H, int W, int win, void* stream) {
-    PULPO_REQUIRE(I && J && S && wa && T && gJ && B > 0 && D > 0 && H > 0 && W > 0, "ncc_masked_bwd: bad arguments");
-    PULPO_REQUIRE(win >= 1 && (win & 1) && win <= 31, "ncc_masked_bwd: window must be odd and <= 31");
-    hipStream_t st = (hipStream_t)stream;
-    const long N = (long)B * D * H * W;
-    const int pad = win / 2, span = 64 - 2 * pad, segs = pulpo::cdiv(W, span);
-    const long nrows = (long)B * D * H;
-    float* T1 = T;
-    float* T2 = T + 3 * N;
-    hipLaunchKernelGGL(ncc_masked_abc_kernel, dim3(eblocks(N)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D), wa, wb);
-    int rc = pulpo::check_launch("ncc masked abc");
-    if (rc) return rc;
-    hipLaunchKernelGGL(box_x_kernel<1>, dim3(eblocks(nrows * segs * 64)), dim3(256), 0, st, T1, nullptr, T2, N, nrows, W, pad, 3, segs);
-    rc = pulpo::check_launch("ncc masked bwd box_x");
-    if (rc) return rc;
-    const bool march = pad >= 1 && pad <= 5;
-    if (march && H > 1) rc = launch_march<3, 0>(pad, eblocks(N, 1024), st, T2, T1, N, H, (long)W, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f);
-    else {
-        hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N)), dim3(256), 0, st, T2, T1, N, 3, H, (long)W, pad);
-        rc = pulpo::check_launch("ncc masked bwd box_y");
-    }
-    if (rc) return rc;
-    if (march) return launch_march<3, 2>(pad, eblocks(N, 1024), st, T1, gJ, N, D, (long)H * W, 0.f, nullptr, I, J, gscale, coef);
-    hipLaunchKernelGGL(ncc_bwd_final_kernel, dim3(eblocks(N)), dim3(256), 0, st, T1, I, J, gscale, coef, gJ, N, D, (long)H * W, pad);
-    return pulpo::check_launch("ncc masked bwd final");
+    PULPO_NCC_REQUIRE("ncc_masked_bwd", I && J && S && wa && T && gJ);
+    return ncc_backward(I, J, S, wa, wb, T, gscale, coef, gJ, B, D, H, W, win, (hipStream_t)stream);
 }
+#undef PULPO_NCC_REQUIRE
 
 // the scalars of a masked loss from its two-column block partials (include/pulpo_hip.h); out: 4 floats
 PULPO_API int pulpo_masked_finish(const float* partial, int nblk, double scale, int root, double count, float* out, void* stream) {

@@ -35,6 +35,7 @@ __global__ __launch_bounds__(256) void sqdiff_bwd_kernel(const float* __restrict
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) ga[e] = k0 * (a[e] - b[e]);
 }
 
+// (a kernel pair of its own, not a MASKED option of the pair above as in losses.hip: its (B,C,V) index arithmetic is what the flat pair, also run by pulpo_rmse, must not pay for)
 // L2_loss with a cost-function mask m = wa * wb (wb nullable) of shape (B,1,V), broadcast over the C channels of a, b (B,C,V):
 // partial[2 blk] = sum of m (a - b)^2, partial[2 blk + 1] = sum of m, every voxel's m counted once (at channel 0)
 __global__ __launch_bounds__(256) void sqdiff_masked_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ wa,

@@ -180,21 +180,6 @@ class HierarchicalReconstructionLoss(nn.Module):
         self.ndims = ndims
         self.mode = "trilinear" if ndims == 3 else "bilinear"
 
-    def _ncc(self, l, y_hat_l, y_target, pair, gamma):
-        if pair is None:
-            return NCC_loss(y_hat_l, y_target, gamma=gamma, win_size=self.window_size[l])
-        return NCC_loss_masked(y_hat_l, y_target, pair[0], pair[1], gamma=gamma, win_size=self.window_size[l])
-
-    @staticmethod
-    def _mse(y_hat_l, y_target, pair):
-        return L2_loss(y_hat_l, y_target) if pair is None else L2_loss_masked(y_hat_l, y_target, pair[0], pair[1])
-
-    def _mind(self, y_hat_l, y_target, pair):
-        """no gamma: the term is on MSE's scale already"""
-        if pair is None:
-            return MIND_loss(y_hat_l, y_target, self.mind_dilation, self.mind_eps)
-        return MIND_loss_masked(y_hat_l, y_target, pair[0], pair[1], self.mind_dilation, self.mind_eps)
-
     def forward(self, y_hat, y, y_hat_seg=None, seg_y=None, gamma: float = 0.05, dice_factor: int = 1,
                 masks: Optional[Dict[int, Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]] = None,
                 dice_terms: Optional[Dict[int, torch.Tensor]] = None):
@@ -209,24 +194,16 @@ class HierarchicalReconstructionLoss(nn.Module):
             size = y_hat[l].shape[2:]
             # F.interpolate(y, size) of the reference; the identity resize at full resolution is skipped
             y_target = y if tuple(size) == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
-            pair = masks.get(l) if masks is not None else None
-            if pair is not None:
-                pair = tuple(m for m in pair if m is not None)
-                pair = None if not pair else (pair[0], pair[1] if len(pair) > 1 else None)
+            ma, mb = (masks.get(l) if masks is not None else None) or (None, None)
+            how = dict(win=self.window_size[l], gamma=gamma, dilation=self.mind_dilation, eps=self.mind_eps)
             if single and self.recon_loss[0] != "dice":
                 # one term per level (the default, ["ncc"]): weighting and summation of all levels in one launch; x / 1 is x
-                if self.recon_loss[0] == "mind":
-                    terms[l] = self._mind(y_hat[l], y_target, pair)
-                else:
-                    terms[l] = self._ncc(l, y_hat[l], y_target, pair, gamma) if self.recon_loss[0] == "ncc" else self._mse(y_hat[l], y_target, pair)
+                terms[l] = ops.similarity(self.recon_loss[0], y_hat[l], y_target, ma, mb, **how)
                 continue
             term = 0.0
-            if "mse" in self.recon_loss:
-                term = term + w * self._mse(y_hat[l], y_target, pair)
-            if "ncc" in self.recon_loss:
-                term = term + w * self._ncc(l, y_hat[l], y_target, pair, gamma)
-            if "mind" in self.recon_loss:
-                term = term + w * self._mind(y_hat[l], y_target, pair)
+            for kind in ("mse", "ncc", "mind"):
+                if kind in self.recon_loss:
+                    term = term + w * ops.similarity(kind, y_hat[l], y_target, ma, mb, **how)
             if "dice" in self.recon_loss and dice_terms is not None:
                 term = term + w * dice_terms[l]
             elif "dice" in self.recon_loss:

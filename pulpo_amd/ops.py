@@ -1960,49 +1960,8 @@ def vecint_pair(v, nsteps: int = 7):
 
 
 # ------------------------------------------------------------------------------------------------ losses
-class _NCC(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, true, win: int, gamma: float):
-        _require_gpu(pred, true)
-        pred, true = planar(pred), planar(true)
-        B, C, D, H, W = pred.shape
-        if C != 1:
-            raise PulpoHipError("ncc: single-channel volumes expected")
-        N = B * D * H * W
-        dev = pred.device
-        S = torch.empty(5 * N, device=dev, dtype=torch.float32)
-        T = torch.empty(10 * N, device=dev, dtype=torch.float32)
-        nblk = lib.query("pulpo_loss_blocks", N)
-        part = torch.empty(nblk, device=dev, dtype=torch.float32)
-        t0 = _hbm_begin("ncc_fwd")
-        lib.call("pulpo_ncc_fwd", _ptr(true), _ptr(pred), _ptr(S), _ptr(T), _ptr(part), B, D, H, W, win, _stream())
-        _hbm_end(t0, "ncc_fwd", 4.0 * 22 * N)                  # 2 images in; three separable passes over 5 box-sum channels (write 5, read 5, write 5, read 5)
-        loss = _colsum(part, nblk, 1, -gamma / B)
-        ctx.save_for_backward(pred, true, S)
-        ctx.win, ctx.gamma = win, gamma
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        pred, true, S = ctx.saved_tensors
-        B, _, D, H, W = pred.shape
-        N = B * D * H * W
-        T = torch.empty(6 * N, device=pred.device, dtype=torch.float32)
-        gJ = torch.empty_like(pred)
-        g = g.contiguous()
-        t0 = _hbm_begin("ncc_bwd")
-        lib.call("pulpo_ncc_bwd", _ptr(true), _ptr(pred), _ptr(S), _ptr(T), _ptr(g), -ctx.gamma / B, _ptr(gJ), B, D, H, W, ctx.win, _stream())
-        _hbm_end(t0, "ncc_bwd", 4.0 * 20 * N)                  # 2 images + 5 sums in; three passes over 3 channels (write 3, read 3, write 3, read 3); gradient out
-        return gJ, None, None, None
-
-
-def ncc_loss(pred, true, win: int = 9, gamma: float = 0.05):
-    if _is2d(pred):                                    # depth 1 selects the win x win window count in the kernel
-        return ncc_loss(_lift(pred), _lift(true), win, gamma)
-    return _NCC.apply(pred, true, int(win), float(gamma))
-
-
-# ---- cost-function masking: m = mask * mask2 weights the per-voxel cost, the loss is normalised by M = sum of m
+# ---- cost-function masking: m = mask * mask2 weights the per-voxel cost, the loss is normalised by M = sum of m.  One
+# autograd node per term (_NCC, _SqDiff, _Mind): wa is None -> the unmasked term, a 0-d loss; else the four scalars of pulpo_masked_finish
 def _as_masks(img: torch.Tensor, mask, mask2, name: str):
     """the masks of a (B,C,D,H,W) image as contiguous fp32 (B,1,D,H,W) device tensors (another dtype is converted here, once)"""
     if mask is None:
@@ -2022,6 +1981,16 @@ def _as_masks(img: torch.Tensor, mask, mask2, name: str):
     return out[0], out[1]
 
 
+def _masks_of(img: torch.Tensor, mask, mask2, name: str):
+    """_as_masks of a volume, or of a slice (B,C,H,W): its masks are slices (B,1,H,W) and come back lifted to depth 1 like the image will be"""
+    if _is2d(img):
+        for m in (mask, mask2):
+            if m is not None and m.dim() != 4:
+                raise ValueError(f"{name}: masks of a (B,C,H,W) image are (B,1,H,W), got {tuple(m.shape)}")
+        img, mask, mask2 = _lift(img), _lift(mask), _lift(mask2)
+    return _as_masks(img, mask, mask2, name)
+
+
 def _masked_finish(part: torch.Tensor, nblk: int, scale: float, root: bool, count: float) -> torch.Tensor:
     """(loss, d loss / d sum, M / count, M) of a masked loss from its two-column block partials, on the device"""
     out = torch.empty(4, device=part.device, dtype=torch.float32)
@@ -2029,7 +1998,9 @@ def _masked_finish(part: torch.Tensor, nblk: int, scale: float, root: bool, coun
     return out
 
 
-class _NCCMasked(torch.autograd.Function):
+class _NCC(torch.autograd.Function):
+    """unmasked (wa is None): the loss scalar; masked: the four scalars of pulpo_masked_finish, the caller takes element 0"""
+
     @staticmethod
     def forward(ctx, pred, true, wa, wb, win: int, gamma: float):
         _require_gpu(pred, true, wa, wb)
@@ -2039,44 +2010,59 @@ class _NCCMasked(torch.autograd.Function):
             raise PulpoHipError("ncc: single-channel volumes expected")
         N = B * D * H * W
         dev = pred.device
+        masked = wa is not None
         S = torch.empty(5 * N, device=dev, dtype=torch.float32)
         T = torch.empty(10 * N, device=dev, dtype=torch.float32)
         nblk = lib.query("pulpo_loss_blocks", N)
-        part = torch.empty(2 * nblk, device=dev, dtype=torch.float32)
-        nmask = 1 if wb is None else 2
-        t0 = _hbm_begin("ncc_masked_fwd")
-        lib.call("pulpo_ncc_masked_fwd", _ptr(true), _ptr(pred), _ptr(wa), _ptr(wb), _ptr(S), _ptr(T), _ptr(part), B, D, H, W, win, _stream())
-        _hbm_end(t0, "ncc_masked_fwd", 4.0 * (22 + nmask) * N)   # ncc_fwd's traffic and one read of every mask plane
+        part = torch.empty((2 if masked else 1) * nblk, device=dev, dtype=torch.float32)
+        name, planes = ("ncc_masked_fwd", (_ptr(wa), _ptr(wb))) if masked else ("ncc_fwd", ())
+        t0 = _hbm_begin(name)
+        lib.call("pulpo_" + name, _ptr(true), _ptr(pred), *planes, _ptr(S), _ptr(T), _ptr(part), B, D, H, W, win, _stream())
+        # 2 images in; three separable passes over 5 box-sum channels (write 5, read 5, write 5, read 5); one read of every mask plane
+        _hbm_end(t0, name, 4.0 * (22 + (wa is not None) + (wb is not None)) * N)
+        ctx.win, ctx.gamma, ctx.masked = win, gamma, masked
+        if not masked:
+            ctx.save_for_backward(pred, true, S)
+            return _colsum(part, nblk, 1, -gamma / B).reshape(())
         fin = _masked_finish(part, nblk, -gamma * (D * H * W), False, float(N))
         ctx.save_for_backward(pred, true, S, wa, wb, fin)
-        ctx.win = win
-        return fin                                           # (loss, d loss / d sum, MaskFrac, M): the caller takes element 0
+        return fin
 
     @staticmethod
-    def backward(ctx, gfin):
-        pred, true, S, wa, wb, fin = ctx.saved_tensors
+    def backward(ctx, g):
+        pred, true, S, *rest = ctx.saved_tensors
         B, _, D, H, W = pred.shape
         N = B * D * H * W
         T = torch.empty(6 * N, device=pred.device, dtype=torch.float32)
         gJ = torch.empty_like(pred)
-        gs = (gfin[0] * fin[1]).contiguous()                 # upstream * (-gamma V / M), 0 for an empty mask: device scalars
-        nmask = 1 if wb is None else 2
-        t0 = _hbm_begin("ncc_masked_bwd")
-        lib.call("pulpo_ncc_masked_bwd", _ptr(true), _ptr(pred), _ptr(S), _ptr(wa), _ptr(wb), _ptr(T), _ptr(gs), 1.0, _ptr(gJ), B, D, H, W, ctx.win,
-                 _stream())
-        _hbm_end(t0, "ncc_masked_bwd", 4.0 * (20 + nmask) * N)
+        if ctx.masked:
+            wa, wb, fin = rest
+            name, planes = "ncc_masked_bwd", (_ptr(wa), _ptr(wb))
+            gs, coef = (g[0] * fin[1]).contiguous(), 1.0        # upstream * (-gamma V / M), 0 for an empty mask: device scalars
+        else:
+            wa = wb = None
+            name, planes = "ncc_bwd", ()
+            gs, coef = g.contiguous(), -ctx.gamma / B
+        t0 = _hbm_begin(name)
+        lib.call("pulpo_" + name, _ptr(true), _ptr(pred), _ptr(S), *planes, _ptr(T), _ptr(gs), coef, _ptr(gJ), B, D, H, W, ctx.win, _stream())
+        # 2 images + 5 sums in; three passes over 3 channels (write 3, read 3, write 3, read 3); gradient out; one read of every mask plane
+        _hbm_end(t0, name, 4.0 * (20 + (wa is not None) + (wb is not None)) * N)
         return gJ, None, None, None, None, None
+
+
+def ncc_loss(pred, true, win: int = 9, gamma: float = 0.05):
+    if _is2d(pred):                                    # depth 1 selects the win x win window count in the kernel
+        pred, true = _lift(pred), _lift(true)
+    return _NCC.apply(pred, true, None, None, int(win), float(gamma))
 
 
 def ncc_loss_masked(pred, true, mask, mask2=None, win: int = 9, gamma: float = 0.05):
     """-gamma V sum(m cc) / M with m = mask * mask2 and M = sum(m) (0 for an empty mask): NCC_loss with the per-voxel cost weighted by m,
     the window statistics over all voxels.  Masks: (B,1,...) weights in [0,1], 1 = counted.  Gradient to pred only."""
+    wa, wb = _masks_of(pred, mask, mask2, "ncc_loss_masked")
     if _is2d(pred):
-        if mask is not None and mask.dim() != 4 or mask2 is not None and mask2.dim() != 4:
-            raise ValueError(f"ncc_loss_masked: masks of a (B,1,H,W) image are (B,1,H,W), got {tuple(mask.shape)}")
-        return ncc_loss_masked(_lift(pred), _lift(true), _lift(mask), _lift(mask2), win, gamma)
-    wa, wb = _as_masks(pred, mask, mask2, "ncc_loss_masked")
-    return _NCCMasked.apply(pred, true, wa, wb, int(win), float(gamma))[0]
+        pred, true = _lift(pred), _lift(true)
+    return _NCC.apply(pred, true, wa, wb, int(win), float(gamma))[0]
 
 
 # ---- MIND-SSC (DESIGN.md section 3j): a similarity term between two contrasts.  f_k = exp(-(D_k - min D) / (mean(D - min D) + eps)) over
@@ -2160,8 +2146,8 @@ def mind_loss(pred, true, dilation: int = 2, eps: float = 1e-5):
 def mind_loss_masked(pred, true, mask, mask2=None, dilation: int = 2, eps: float = 1e-5):
     """V sum(m cost) / M with m = mask * mask2 and M = sum(m) (0 for an empty mask): mind_loss with the per-voxel cost weighted by m; the
     descriptors are formed from all voxels.  Gradient to pred only."""
-    dilation, eps = _mind_args("mind_loss_masked", pred, true, dilation=dilation, eps=eps)
-    wa, wb = _as_masks(pred, mask, mask2, "mind_loss_masked")
+    dilation, eps = _mind_args("mind_loss_masked", pred, true, dilation=dilation, eps=eps)      # (3-D only: raises on slices)
+    wa, wb = _masks_of(pred, mask, mask2, "mind_loss_masked")
     return _Mind.apply(pred, true.detach(), wa, wb, dilation, eps)[0]
 
 
@@ -2288,69 +2274,57 @@ def weighted_sum(terms, weights, scale=None):
 
 # ------------------------------------------------------------------------------------------------ alternative losses / metrics
 class _SqDiff(torch.autograd.Function):
-    """L2_loss: spatial sum of squared differences, mean over batch and channels"""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        _require_gpu(a, b)
-        a, b = planar(a), planar(b)
-        n = a.numel()
-        nblk = lib.query("pulpo_metric_blocks", n)
-        part = torch.empty(nblk, device=a.device, dtype=torch.float32)
-        lib.call("pulpo_sqdiff_fwd", _ptr(a), _ptr(b), n, _ptr(part), _stream())
-        ctx.save_for_backward(a, b)
-        ctx.coef = 1.0 / (a.shape[0] * a.shape[1])
-        return _colsum(part, nblk, 1, ctx.coef).reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b = ctx.saved_tensors
-        ga = torch.empty_like(a)
-        lib.call("pulpo_sqdiff_bwd", _ptr(a), _ptr(b), _ptr(g.contiguous()), ctx.coef, _ptr(ga), a.numel(), _stream())
-        return ga, None
-
-
-def l2_loss(inp, target):
-    if _is2d(inp):
-        return l2_loss(_lift(inp), _lift(target))
-    return _SqDiff.apply(inp, target)
-
-
-class _SqDiffMasked(torch.autograd.Function):
-    """(L2_masked or, with root, RMSE_masked; MaskFrac) - DESIGN.md section 3i"""
+    """unmasked (wa is None): L2_loss, the spatial sum of squared differences, mean over batch and channels; masked: the four scalars of
+    pulpo_masked_finish - (L2_masked or, with root, RMSE_masked; d value / d sum; MaskFrac; M), DESIGN.md section 3i"""
 
     @staticmethod
     def forward(ctx, a, b, wa, wb, root: bool):
         _require_gpu(a, b, wa, wb)
         a, b = planar(a), planar(b)
         B, C = a.shape[0], a.shape[1]
-        V = a.numel() // (B * C)
-        nblk = lib.query("pulpo_metric_blocks", a.numel())
+        n = a.numel()
+        V = n // (B * C)
+        nblk = lib.query("pulpo_metric_blocks", n)
+        ctx.masked = wa is not None
+        if not ctx.masked:
+            part = torch.empty(nblk, device=a.device, dtype=torch.float32)
+            lib.call("pulpo_sqdiff_fwd", _ptr(a), _ptr(b), n, _ptr(part), _stream())
+            ctx.save_for_backward(a, b)
+            ctx.coef = 1.0 / (B * C)
+            return _colsum(part, nblk, 1, ctx.coef).reshape(())
         part = torch.empty(2 * nblk, device=a.device, dtype=torch.float32)
         lib.call("pulpo_sqdiff_masked_fwd", _ptr(a), _ptr(b), _ptr(wa), _ptr(wb), _ptr(part), B, C, V, _stream())
         fin = _masked_finish(part, nblk, (1.0 if root else float(V)) / C, root, float(B * V))
         ctx.save_for_backward(a, b, wa, wb, fin)
-        return fin                                           # (value, d value / d sum, MaskFrac, M)
+        return fin
 
     @staticmethod
-    def backward(ctx, gfin):
-        a, b, wa, wb, fin = ctx.saved_tensors
-        B, C = a.shape[0], a.shape[1]
+    def backward(ctx, g):
+        a, b, *rest = ctx.saved_tensors
         ga = torch.empty_like(a)
-        gs = (gfin[0] * fin[1]).contiguous()
-        lib.call("pulpo_sqdiff_masked_bwd", _ptr(a), _ptr(b), _ptr(wa), _ptr(wb), _ptr(gs), 1.0, _ptr(ga), B, C, a.numel() // (B * C), _stream())
+        if ctx.masked:
+            wa, wb, fin = rest
+            B, C = a.shape[0], a.shape[1]
+            gs = (g[0] * fin[1]).contiguous()
+            lib.call("pulpo_sqdiff_masked_bwd", _ptr(a), _ptr(b), _ptr(wa), _ptr(wb), _ptr(gs), 1.0, _ptr(ga), B, C, a.numel() // (B * C), _stream())
+        else:
+            lib.call("pulpo_sqdiff_bwd", _ptr(a), _ptr(b), _ptr(g.contiguous()), ctx.coef, _ptr(ga), a.numel(), _stream())
         return ga, None, None, None, None
 
 
-def _sqdiff_masked(inp, target, mask, mask2, root: bool, name: str):
+def l2_loss(inp, target):
     if _is2d(inp):
-        if mask is not None and mask.dim() != 4 or mask2 is not None and mask2.dim() != 4:
-            raise ValueError(f"{name}: masks of a (B,C,H,W) image are (B,1,H,W), got {tuple(mask.shape)}")
-        return _sqdiff_masked(_lift(inp), _lift(target), _lift(mask), _lift(mask2), root, name)
+        inp, target = _lift(inp), _lift(target)
+    return _SqDiff.apply(inp, target, None, None, False)
+
+
+def _sqdiff_masked(inp, target, mask, mask2, root: bool, name: str):
+    wa, wb = _masks_of(inp, mask, mask2, name)
+    if _is2d(inp):
+        inp, target = _lift(inp), _lift(target)
     if inp.shape != target.shape:
         raise ValueError(f"{name}: input {tuple(inp.shape)} and target {tuple(target.shape)} differ in shape")
-    wa, wb = _as_masks(inp, mask, mask2, name)
-    return _SqDiffMasked.apply(inp, target, wa, wb, root)
+    return _SqDiff.apply(inp, target, wa, wb, root)
 
 
 def l2_loss_masked(inp, target, mask, mask2=None):
@@ -2363,6 +2337,24 @@ def rmse_masked(inp, target, mask, mask2=None):
     """(sqrt(L2_masked / V), MaskFrac = M / (B V)) as 0-d device tensors"""
     fin = _sqdiff_masked(inp, target, mask, mask2, True, "rmse_masked")
     return fin[0], fin[2].detach()
+
+
+SIMILARITY_TERMS = ("ncc", "mse", "mind")
+
+
+def similarity(kind: str, pred, true, mask=None, mask2=None, *, win: int = 9, gamma: float = 0.05, dilation: int = 2, eps: float = 1e-5):
+    """the similarity term `kind` between pred and true: the one place that maps (term, masks) to an operator.  No mask: ncc_loss (window win,
+    factor gamma) / l2_loss / mind_loss (dilation, eps; gamma does not apply: on MSE's scale already); with either mask of the pair, in either
+    argument: the masked form, cost weighted by mask * mask2.  An unknown kind raises ValueError before anything touches the device."""
+    if kind not in SIMILARITY_TERMS:
+        raise ValueError(f"similarity: term {kind!r} - one of {SIMILARITY_TERMS} expected")
+    if mask is None:
+        mask, mask2 = mask2, None
+    if kind == "ncc":
+        return ncc_loss(pred, true, win, gamma) if mask is None else ncc_loss_masked(pred, true, mask, mask2, win, gamma)
+    if kind == "mse":
+        return l2_loss(pred, true) if mask is None else l2_loss_masked(pred, true, mask, mask2)
+    return mind_loss(pred, true, dilation, eps) if mask is None else mind_loss_masked(pred, true, mask, mask2, dilation, eps)
 
 
 class _Dice(torch.autograd.Function):

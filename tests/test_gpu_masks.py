@@ -57,7 +57,7 @@ def check(name, got, ref, tol, power=-1):
 
 
 # (B, size, window): W = 2 (64 - 2 pad) and one past it (wave segments of the W pass); an extent below the pad (D = 3, w = 11); w = 13 (the
-# tap-form kernels: box_axis / ncc_masked_final / ncc_bwd_final); H = 1 (no march for the H pass); D = 1 (2-D window count); a voxel count
+# tap-form kernels: box_axis / ncc_final<MASKED> / ncc_bwd_final); H = 1 (no march for the H pass); D = 1 (2-D window count); a voxel count
 # that straddles the batch boundary; two pyramid level shapes
 CASES = [(2, (4, 5, 112), 9), (2, (4, 5, 113), 9), (1, (3, 12, 70), 11), (1, (10, 12, 40), 13), (2, (6, 1, 70), 5), (2, (1, 20, 130), 7),
          (2, (17, 19, 23), 7), (1, (24, 28, 20), 3), (1, (40, 40, 40), 5)]
@@ -242,6 +242,50 @@ def test_masks_of_another_dtype_and_of_a_wrong_shape(ops):
             ops.l2_loss_masked(p, t, bad)
         with pytest.raises(ValueError):
             ops.rmse_masked(p, t, d["ball"], bad)
+
+
+# ================================================================================================ the dispatcher
+# (term, B, size, keywords): H = 1 (no march in the H pass) and window 13 (the tap-form kernels) for "ncc" / "mse"; the smallest 3-D case of
+# test_gpu_mind for "mind"; the 2-D forms
+SIM_CASES = [(kind, B, size, dict(win=win)) for kind in ("ncc", "mse") for B, size, win in ((2, (6, 1, 70), 5), (1, (10, 12, 40), 13), (2, (20, 130), 7))]
+SIM_CASES.append(("mind", 2, (5, 6, 7), dict(dilation=1)))
+
+
+def _named_operator(ops, kind, kw):
+    """(unmasked, masked) operators of a term, called the way ops.similarity's caller would have to call them"""
+    if kind == "ncc":
+        return (lambda p, t: ops.ncc_loss(p, t, kw["win"], GAMMA)), (lambda p, t, m, m2: ops.ncc_loss_masked(p, t, m, m2, kw["win"], GAMMA))
+    if kind == "mse":
+        return ops.l2_loss, ops.l2_loss_masked
+    return (lambda p, t: ops.mind_loss(p, t, kw["dilation"])), (lambda p, t, m, m2: ops.mind_loss_masked(p, t, m, m2, kw["dilation"]))
+
+
+@pytest.mark.parametrize("kind,B,size,kw", SIM_CASES)
+def test_similarity_is_the_named_operator(ops, kind, B, size, kw):
+    """ops.similarity against the operator it names, value and gradient bit for bit (the same kernels on the same inputs, no atomics), for
+    no mask, one mask in either argument and two; gamma reaches "ncc" only; "mind" on a slice raises NotImplementedError"""
+    g = torch.Generator(device=DEV).manual_seed(size[-1] + B)
+    p, t, m1, m2 = (torch.rand(B, 1, *size, device=DEV, generator=g) for _ in range(4))
+    plain, masked = _named_operator(ops, kind, kw)
+
+    def value_and_grad(fn):
+        pg = p.clone().requires_grad_(True)
+        val = fn(pg)
+        assert val.dim() == 0
+        gp, = torch.autograd.grad(val, [pg], grad_outputs=torch.tensor(1.7, device=DEV))
+        return val.detach(), gp
+
+    for pair, named in (((None, None), lambda x: plain(x, t)), ((m1, None), lambda x: masked(x, t, m1, None)),
+                        ((None, m1), lambda x: masked(x, t, m1, None)), ((m1, m2), lambda x: masked(x, t, m1, m2))):
+        got = value_and_grad(lambda x: ops.similarity(kind, x, t, *pair, gamma=GAMMA, **kw))
+        want = value_and_grad(named)
+        which = tuple(m is not None for m in pair)
+        assert torch.equal(got[0], want[0]), (kind, which, float(got[0]), float(want[0]))
+        assert torch.equal(got[1], want[1]) and bool(got[1].any()), (kind, which)
+    if kind == "mind":                      # 3-D only, through the dispatcher as through ops.mind_loss(_masked)
+        for pair in ((None, None), (m1[:, :, 0], None), (None, m1[:, :, 0])):
+            with pytest.raises(NotImplementedError):
+                ops.similarity("mind", p[:, :, 0], t[:, :, 0], *pair)
 
 
 # ================================================================================================ the masks' own warp

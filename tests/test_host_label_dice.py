@@ -79,13 +79,14 @@ def test_labels_soft_map_wants_exactly_one_form():
         ops.labels_soft_map(lab, 3, pool2=True, size=(2, 2, 2))
 
 
-def test_dice_terms_stand_in_for_the_dice_term():
+def test_dice_terms_stand_in_for_the_dice_term(monkeypatch):
     """CPU scalars: with dice_terms the level term is (w ncc_l + w dice_terms[l]) / 2, everything else as before"""
     from pulpo_amd import losses
     w = {0: 4.0, 1: 8.0}
     rec = losses.HierarchicalReconstructionLoss(["ncc", "dice"], dict(w), False, 3, {0: 5, 1: 3})
     ncc = {0: torch.tensor(-0.3), 1: torch.tensor(-0.7)}
-    rec._ncc = lambda l, y_hat_l, y_target, pair, gamma: ncc[l]
+    level_of_window = {5: 0, 3: 1}
+    monkeypatch.setattr(losses.ops, "similarity", lambda kind, pred, true, mask=None, mask2=None, *, win, **kw: ncc[level_of_window[win]])
     dice = {0: torch.tensor(1.25), 1: torch.tensor(0.5)}
     y = torch.zeros(1, 1, 2, 2, 2)
     total, levels = rec(dict.fromkeys(w, y), y, dict.fromkeys(w), None, dice_terms=dice)

@@ -152,3 +152,17 @@ def test_entry_points_reject_null_pointers_and_bad_sizes():
                 (1, 8, 8, 8, 8, 8, 0), (1, 1, 8, 8, 2, 8, 8), (1, 2048, 1024, 1024, 8, 8, 8)):
         assert wm(p, p, p, *bad, None) != 0, bad
     assert b"warp_mask_fwd" in lib.raw("pulpo_last_error")()
+
+
+def test_similarity_refuses_unknown_terms():
+    """before anything asks for a GPU: CPU tensors, which every known term refuses with PulpoHipError"""
+    from pulpo_amd import ops
+    from pulpo_amd._lib import PulpoHipError
+    p, t = _pair(1, (4, 5, 6))
+    for kind in ("dice", "", "NCC", None):
+        with pytest.raises(ValueError):
+            ops.similarity(kind, p.float(), t.float())
+        with pytest.raises(ValueError):
+            ops.similarity(kind, p.float(), t.float(), torch.ones_like(p), None, win=5)
+    with pytest.raises(PulpoHipError):
+        ops.similarity("ncc", p.float(), t.float(), win=5)
