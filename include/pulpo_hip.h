@@ -274,6 +274,18 @@ int pulpo_kl_bwd(const float* mu, const float* sigma, const float* mu1, const fl
                  float* gsigma, int64_t n, void* stream);
 int pulpo_l2reg_fwd(const float* df, int64_t nplanes, int D, int H, int W, float* partial, void* stream);
 int pulpo_l2reg_bwd(const float* df, const float* gscale, float coef, float* gdf, int64_t nplanes, int D, int H, int W, void* stream);
+/* Bending-energy regulariser (no counterpart in the reference; added without a version bump).  df = nplanes planar
+ * volumes (D,H,W) of fp32 voxels, nplanes = B * C.  With central differences at INTERIOR voxels only (1 .. extent - 2; no padding, no one-sided
+ * stencil),  u_xx = u[x+1] - 2u + u[x-1],  u_xy = (u[x+1,y+1] - u[x+1,y-1] - u[x-1,y+1] + u[x-1,y-1]) / 4  and
+ *   e = u_xx^2 + u_yy^2 + u_zz^2 + 2 u_xy^2 + 2 u_xz^2 + 2 u_yz^2;    D == 1 is the 2-D form (no z term).
+ * bending_fwd: partial[blk] = the workgroup's sum of e over its interior voxels, pulpo_bending_blocks(nplanes, D, H, W) floats; finish with
+ *   pulpo_colsum(scale = lamb * D*H*W / (nplanes * n_interior)).
+ * bending_bwd: gdf = 2 * coef * gscale[0] * sum_k w_k A_k^T (M . A_k u) (gscale nullable = 1), M the interior mask, w = (1,1,1,2,2,2).
+ * One launch each, no atomics, no scratch: bit-identical run to run.  Needs H >= 3, W >= 3 and D == 1 or D >= 3; pulpo_bending_blocks
+ * returns 0 for any other shape. */
+int pulpo_bending_blocks(int64_t nplanes, int D, int H, int W);
+int pulpo_bending_fwd(const float* df, int64_t nplanes, int D, int H, int W, float* partial, void* stream);
+int pulpo_bending_bwd(const float* df, const float* gscale, float coef, float* gdf, int64_t nplanes, int D, int H, int W, void* stream);
 /* sum_l w_l * term_l of the Hierarchical* losses (src/losses.py:262-276, 305-325, 343-355) and models.py:161-162's `kl * beta` in one launch:
  * levels[i] = w[i] * terms[i] (* scale if scaled), total[0] = (sum_i w[i] * terms[i]) (* scale if scaled), summed in index order like the
  * reference's `loss = loss + all_levels[l]`.  Device arrays of n floats (total: 1); n <= 64.  Backward: gterms[i] = (gtotal[0] + glevels[i]) *

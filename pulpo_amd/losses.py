@@ -119,6 +119,14 @@ def L2_reg(deformation_field: torch.Tensor, lamb=0) -> torch.Tensor:
     return ops.l2_reg(deformation_field, lamb)
 
 
+def Bending_reg(deformation_field: torch.Tensor, lamb=0) -> torch.Tensor:
+    """lamb * H*W*D * mean over the interior voxels of the bending-energy density u_xx^2 + u_yy^2 + u_zz^2 + 2 u_xy^2 + 2 u_xz^2 + 2 u_yz^2
+    (central differences; no counterpart in the reference): L2_reg's scale, nothing charged for an affine field"""
+    if deformation_field.dim() not in (4, 5):
+        raise NotImplementedError("Bending_reg: fields (B,3,D,H,W) or (B,2,H,W) expected")
+    return ops.bending_reg(deformation_field, lamb)
+
+
 def _apply_pyramid(weight_dict: Dict[int, float], similarity_pyramid: bool) -> Dict[int, float]:
     if similarity_pyramid:                      # in place, like the reference (losses.py:238-240)
         for l in weight_dict.keys():

@@ -19,7 +19,7 @@ import torch
 
 from ._lightning import LightningModule
 from .components.pulpo import Autoencoder, DownPath, PULPoEncoder, PULPoPrior, SVFDecoder  # noqa: F401  (re-exported like the reference)
-from .losses import (HierarchicalKLLoss, HierarchicalReconstructionLoss, HierarchicalRegularization, JDetStd, KL_nondiagonal,
+from .losses import (Bending_reg, HierarchicalKLLoss, HierarchicalReconstructionLoss, HierarchicalRegularization, JDetStd, KL_nondiagonal,
                      KL_two_gauss_with_diag_cov, L2_reg)
 from .network_blocks import DFAdder, ResizeTransform, SpatialTransformer, VecInt, gauss_sampler  # noqa: F401
 from . import ops
@@ -97,8 +97,16 @@ class PULPo(ABC, LightningModule):
             regularization_loss = JDetStd
         elif self.hparams.regularizer == "L2":
             regularization_loss = L2_reg
+        elif self.hparams.regularizer == "bending":             # second order, free for affine fields
+            regularization_loss = Bending_reg
+            sizes = {l: [int(v) for v in (input_size if df_resolution == "full_res" or l == 0 else self.autoencoder.level_sizes[self.lk_offset + l])]
+                     for l in range(latent_levels)}                 # the decoders' output sizes: what final_dfs[l] has
+            small = {l: s for l, s in sizes.items() if min(s) < 3}
+            if small:
+                raise ValueError(f"regularizer 'bending' takes central differences at interior voxels: every extent of a level's field must be at "
+                                 f"least 3, but the level sizes are {sizes}")
         else:
-            raise ValueError(f"Hyperparameter regularizer is {self.hparams.regularizer}. Not a known option.")
+            raise ValueError(f"Hyperparameter regularizer is {self.hparams.regularizer}. Not a known option (known: 'L2', 'jdet', 'bending').")
 
         # NCC window per level and the loss-magnitude equalisation weights (reference models.py:104-123)
         window_size = {l: 1 + 2 * (latent_levels - l) for l in range(latent_levels)}

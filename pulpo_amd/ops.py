@@ -288,7 +288,8 @@ def act_dtype():
 # flush of concurrent workgroups, the image-gradient scatter of the warp / VecInt backward, the generic trilinear-resize backward - are replaced
 # by their ordered forms (`*_det` entry points: per-split slabs + an ordered sum; 64-bit fixed-point accumulation; a gather): two runs of the same
 # build on the same inputs give bit-identical gradients, as the reference's CPU backward does.  Everything else in a step is
-# deterministic already (two-stage reductions in fixed order).  Not covered: the `jdet` regulariser's backward (raises in this mode).
+# deterministic already (two-stage reductions in fixed order), the `bending` regulariser included (its backward is a gather).  Not covered: the
+# `jdet` regulariser's backward (raises in this mode).
 DETERMINISTIC = os.environ.get("PULPO_DETERMINISTIC", "0") == "1"
 
 
@@ -2226,6 +2227,51 @@ def l2_reg(df, lamb: float = 0.0):
     return _L2Reg.apply(df, float(lamb))
 
 
+class _Bending(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, df, lamb: float):
+        df = planar(df)
+        B, C, D, H, W = df.shape
+        n = df.numel()
+        nblk = lib.query("pulpo_bending_blocks", B * C, D, H, W)
+        part = torch.empty(nblk, device=df.device, dtype=torch.float32)
+        t0 = _hbm_begin("bending_fwd")
+        lib.call("pulpo_bending_fwd", _ptr(df), B * C, D, H, W, _ptr(part), _stream())
+        _hbm_end(t0, "bending_fwd", 4.0 * n)
+        coef = lamb * D * H * W / float(B * C * max(D - 2, 1) * (H - 2) * (W - 2))      # D == 1: the 2-D form (interior 1..H-2, 1..W-2)
+        ctx.save_for_backward(df)
+        ctx.coef = coef
+        return _colsum(part, nblk, 1, coef).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (df,) = ctx.saved_tensors
+        B, C, D, H, W = df.shape
+        gdf = torch.empty_like(df)
+        g = g.contiguous()
+        t0 = _hbm_begin("bending_bwd")
+        lib.call("pulpo_bending_bwd", _ptr(df), _ptr(g), ctx.coef, _ptr(gdf), B * C, D, H, W, _stream())
+        _hbm_end(t0, "bending_bwd", 8.0 * df.numel())
+        return gdf, None
+
+
+def bending_reg(df, lamb: float = 0.0):
+    """lamb * D*H*W * mean over (batch, components, INTERIOR voxels) of the bending-energy density
+    u_xx^2 + u_yy^2 + u_zz^2 + 2 u_xy^2 + 2 u_xz^2 + 2 u_yz^2 of a displacement field in voxels, central differences (DESIGN.md section 3o;
+    no counterpart in the reference).  On L2_reg's scale, but an affine field costs nothing.  df (B,C,D,H,W), or (B,C,H,W) / a depth of 1 for
+    the 2-D form (no z term); every other extent at least 3.  The gradient is a gather without atomics: bit-identical from run to run, in
+    deterministic mode and out of it.  No double backward."""
+    _require_gpu(df)
+    if df.dim() not in (4, 5):
+        raise ValueError(f"bending_reg: a field (B,C,D,H,W) or (B,C,H,W) expected, got shape {tuple(df.shape)}")
+    if _is2d(df):
+        df = _lift(df)
+    if min(df.shape[3:]) < 3 or df.shape[2] in (0, 2) or df.shape[0] * df.shape[1] < 1:
+        raise ValueError(f"bending_reg: every extent other than a depth of 1 must be at least 3 (central differences at interior voxels), got "
+                         f"shape {tuple(df.shape)}")
+    return _Bending.apply(df, float(lamb))
+
+
 class _WeightedSum(torch.autograd.Function):
     """(sum_i w_i t_i, [w_0 t_0, ..., w_{n-1} t_{n-1}]) (optionally * scale): the per-level weighting and summation of the Hierarchical*
     losses as ONE launch (and one in the backward pass) instead of a mul + an add kernel per level and their autograd counterparts"""
@@ -2426,7 +2472,7 @@ class _JDetStd(torch.autograd.Function):
         B, _, D, H, W = df.shape
         if DETERMINISTIC:
             raise PulpoHipError("the `jdet` regulariser's backward scatters with float atomics and has no deterministic form (PULPO_DETERMINISTIC covers "
-                                "the default training path: ncc / mse / dice + L2 regulariser)")
+                                "the default training path: ncc / mse / dice + the L2 or the bending regulariser)")
         gdf = torch.empty_like(df)
         lib.call("pulpo_jdetstd_bwd", _ptr(df), _ptr(jd), _ptr(stat), _ptr(g.contiguous()), lamb, _ptr(gdf), B, D, H, W, int(normalize), _stream())
         return gdf, None, None

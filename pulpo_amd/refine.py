@@ -125,7 +125,9 @@ def refine(model, x: torch.Tensor, y: torch.Tensor, *, individual_dfs: Optional[
                   (None: the model's list; e.g. ["mind"] refines a model trained with NCC across contrasts; "dice" raises ValueError),
                   gamma (None: the model's).  mask_x / mask_y (weight volumes (B,1,...) at full resolution) switch the masked terms on,
                   whatever the model's `mask` hyper-parameter; mask_x is re-warped by the current field every iteration, without gradient.
-    regulariser   model.hierarchical_regularization(final, lamb) (None: the model's lamb).
+    regulariser   model.hierarchical_regularization(final, lamb) (None: the model's lamb): the model's own regulariser - a model built with
+                  regularizer="bending" is refined against the bending energy, which leaves a residual affine
+                  stretch of the field free where L2 pulls it back to the identity.
     anchor        the KL divergence between two Gaussians of equal covariance, N(v, var) against the posterior N(mean, var), weighted by
                   level like the training step's KL term (kl_w, divided by B: kl_diag's normalisation): the fields move freely where the
                   model is uncertain and stay close elsewhere.  Folded once into a per-element precision
