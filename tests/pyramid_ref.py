@@ -1,13 +1,16 @@
 """float64 references of the training step's head, loss, field and ConvUnit operators, written with plain torch ops (matmul, einsum,
 softplus, cumsum, index_select, grid_sample) so that they also run on the GPU at the pyramid's sizes, and the element-wise comparison the
 pyramid tests use.  tests/test_oracle_golden.py pins every helper to oracle/pulpo_oracle.py and torch.nn.functional at small shapes;
-tests/test_gpu_pyramid_ops.py and tests/test_gpu_pyramid_convunit.py hold the HIP kernels to them."""
+tests/test_gpu_pyramid_ops.py, tests/test_gpu_pyramid_convunit.py and tests/test_gpu_vecint.py (the VecInt helpers and field generators) hold
+the HIP kernels to them."""
 from typing import Optional, Sequence
 
 import torch
 import torch.nn.functional as F
 
 from oracle import pulpo_oracle as O
+from inverse_ref import smooth_field
+from slice_ref import warp_ref as _warp2d_ref
 
 
 # ------------------------------------------------------------------------------------------------ 1x1x1 heads
@@ -143,6 +146,119 @@ def resize_ref(x, size: Sequence[int], steps: Optional[Sequence[float]] = None):
         step = steps[k] if steps is not None else x.shape[d] / size[k]
         x = lin1(x, d, int(size[k]), float(step))
     return x
+
+
+# ------------------------------------------------------------------------------------------------ VecInt (scaling and squaring)
+def self_warp_ref(d, i):
+    """O.warp(d, i) for a field d and an image i of the field's own size; a depth-1 grid is the reference's 2-D case (bilinear over y and x
+    with channels 1 and 2 of d, no coordinate along z: slice_ref.warp_ref), every channel of i sampled alike"""
+    if d.shape[2] == 1:
+        return _warp2d_ref(d[:, 1:, 0], i[:, :, 0]).unsqueeze(2)
+    return O.warp(d, i)
+
+
+def vecint_step_ref(w):
+    """one squaring step of VecInt (network_blocks.py:173-177): w + warp(w, w), in w's dtype and on its device"""
+    return w + self_warp_ref(w, w)
+
+
+def vecint_chain_ref(v, nsteps: int):
+    """the nsteps + 1 fields of O.vecint(v, nsteps): v / 2^nsteps, then every squaring step's result (the last one is the operator's)"""
+    out = [v * (1.0 / (2 ** nsteps))]
+    for _ in range(nsteps):
+        out.append(vecint_step_ref(out[-1]))
+    return out
+
+
+def vecint_step_grads_ref(w, g, disp=None):
+    """(gd, gi): the gradient of sum(g * warp(d, i)) with respect to the displacement d and to the image i, two leaves that both hold w -
+    the gradient of the step w + warp(w, w) is g + gd + gi.  disp: another displacement to sample the same image with (a nudged w: gd is
+    the part that jumps where a sample coordinate crosses a cell boundary; the scatter gi is continuous there)"""
+    d = (w if disp is None else disp).detach().clone().requires_grad_(True)
+    i = w.detach().clone().requires_grad_(True)
+    gd, gi = torch.autograd.grad((self_warp_ref(d, i) * g).sum(), [d, i])
+    return gd, gi
+
+
+def vecint_coords(w):
+    """[(axis, S, (B, D, H, W) unclamped sample coordinates of one squaring step along that axis)] for the axes longer than 1"""
+    size = w.shape[2:]
+    c = warp_coords(w, size)
+    return [(a, size[a], c[a]) for a in range(3) if size[a] > 1]
+
+
+def vecint_near_cell_boundary(w, eps: float = 1e-4):
+    """(B, 3, D, H, W) bool: voxels one of whose sample coordinates lies within eps voxel of an integer, of 0 or of S - 1 (a clamp), where
+    a rounded coordinate may take the other cell and the displacement gradient jumps (test_warp_vs_float64's rule)"""
+    near = torch.zeros(w.shape[0], *w.shape[2:], dtype=torch.bool, device=w.device)
+    for _, S, c in vecint_coords(w):
+        near |= ((c - c.round()).abs() < eps) | ((c - (S - 1)).abs() < eps) | (c.abs() < eps)
+    return near.unsqueeze(1).expand(*w.shape)
+
+
+def vecint_clamped_at_every_face(w) -> bool:
+    """some sample of the squaring step of w lies beyond each face of the volume (border padding clamps it), in every batch element"""
+    return all(bool((c < 0).flatten(1).any(1).all()) and bool((c > S - 1).flatten(1).any(1).all()) for _, S, c in vecint_coords(w))
+
+
+def vecint_corner_contributions(w, g, b: int, c: int, z: int, y: int, x: int):
+    """[((iz, iy, ix), value)]: what voxel (z, y, x) of batch element b adds to the image-role gradient of channel c in one squaring step -
+    g[b, c, z, y, x] times the trilinear weight of each corner of its sample cell (clamped coordinate, upper corner min(i0 + 1, S - 1)),
+    in Python floats.  Their scatter over all voxels is vecint_step_grads_ref's gi"""
+    size, pos, axes = w.shape[2:], (z, y, x), []
+    for a in range(3):
+        S = size[a]
+        if S == 1:
+            axes.append([(0, 1.0)])
+            continue
+        cc = ((2 * ((pos[a] + float(w[b, a, z, y, x])) / (S - 1) - 0.5) + 1) * S - 1) / 2
+        cc = min(max(cc, 0.0), S - 1.0)
+        i0 = int(cc // 1)
+        axes.append([(i0, 1.0 - (cc - i0)), (min(i0 + 1, S - 1), cc - i0)])
+    gv = float(g[b, c, z, y, x])
+    return [((iz, iy, ix), gv * wz * wy * wx) for iz, wz in axes[0] for iy, wy in axes[1] for ix, wx in axes[2]]
+
+
+def _coarse_to(size, nodes, B, seed):
+    c = torch.randn(B, 3, *nodes, generator=torch.Generator().manual_seed(seed))
+    return F.interpolate(c, size=tuple(size), mode="trilinear", align_corners=True)
+
+
+def vecint_field(kind: str, B: int, size: Sequence[int], amp: float = 3.0, seed: int = 1):
+    """float32 (B, 3, *size) test fields on the CPU, seeded.  A depth-1 field has a zero z channel (the 2-D form).
+    smooth      inverse_ref.smooth_field: 4 control points per axis, largest |value| amp
+    smooth_large  control points every 6 voxels: the value changes by about amp within one 4 x 8 x 8 tile
+    bands       y and x displacements piecewise linear in y and in x with slopes -1, 0, +1 voxel per voxel in successive 6-voxel bands
+                (0.97 cumsum(slope) + 0.13: no coordinate on an integer), z displacement constant: neighbouring voxels sample the same
+                cell, adjacent cells and cells two apart
+    noise       white noise of standard deviation amp
+    zero        the zero field (not the identity for this sampler)"""
+    D, H, W = size
+    if kind == "smooth":
+        v = smooth_field(size, amp, seed, B)
+    elif kind == "smooth_large":
+        v = _coarse_to(size, [max(2, -(-s // 6) + 1) for s in size], B, seed)
+        v = v * (amp / float(v.abs().max()))
+    elif kind == "bands":
+        def ramp(n):
+            slope = torch.tensor([-1.0] * 6 + [0.0] * 6 + [1.0] * 6).repeat(n // 18 + 1)[:n]
+            return 0.97 * torch.cumsum(slope, 0) + 0.13
+        v = torch.empty(B, 3, D, H, W)
+        for b in range(B):
+            v[b, 0] = 0.21 + 0.05 * b
+            v[b, 1] = (ramp(H) + 0.05 * b).reshape(1, H, 1)
+            v[b, 2] = (ramp(W) + 0.05 * b).reshape(1, 1, W)
+    elif kind == "noise":
+        v = torch.randn(B, 3, D, H, W, generator=torch.Generator().manual_seed(seed)) * amp
+    elif kind == "zero":
+        v = torch.zeros(B, 3, D, H, W)
+    else:
+        raise ValueError(kind)
+    if D == 1:
+        v[:, 0] = 0
+        if kind in ("smooth", "smooth_large"):
+            v = v * (amp / float(v.abs().max()))
+    return v.contiguous()
 
 
 # ------------------------------------------------------------------------------------------------ 3x3x3 convolution (ConvUnit)

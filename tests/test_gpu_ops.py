@@ -105,12 +105,17 @@ def test_vecint_backward_lds_tiled_scatter_vs_oracle(ops, size, amp):
     assert rel_l2(gv, gr) < max(1e-4, 3.0 * rel_l2(g32, gr))
 
 
+# 10^3 (1000 voxels), 12x14x10 (1680) and 6x7x5 (210) take the one-launch kernel; 20^3 (8000) and 16x24x20 (7680) lie above its 2048-voxel
+# switch and run the step-by-step kernels (tests/test_gpu_vecint.py sits on both sides of the switch: 8x16x16 and 8x16x17)
 @pytest.mark.parametrize("B,size", [(1, (20, 20, 20)), (2, (10, 10, 10)), (1, (12, 14, 10)), (1, (6, 7, 5)), (2, (16, 24, 20))])
 def test_vecint_forward_fused_in_lds_equals_the_step_by_step_kernels(ops, B, size):
-    """fields of <= 8192 voxels (the 20^3 and 10^3 pyramid levels and BASELINE config 5's coarse levels) run all seven squaring steps in ONE
-    launch with the field resident in LDS (vecint_fwd_lds_kernel; network_blocks.py:160-177): compared with the operator evaluated step by
-    step through the warp kernel (v / 2^7, then seven times v + warp(v, v)) - the same arithmetic, to fp32 rounding at worst - and with the
-    float64 oracle; the backward pass (which reads the intermediate fields the fused kernel saved) against autograd through the oracle"""
+    """fields of <= 2048 voxels per batch element (the 10^3 pyramid level and BASELINE config 5's coarsest levels; pulpo_vecint_fwd's
+    VECINT_LDS_MAXV - the kernel itself fits 8192) run all seven squaring steps in ONE launch with the field resident in LDS
+    (vecint_fwd_lds_kernel; network_blocks.py:160-177).  Of the cases here 10^3, 12x14x10 and 6x7x5 take that kernel; 20^3 and 16x24x20
+    have run the step-by-step kernels since the switch came down from 8192 and stay as cases of the same comparison.  Each is compared
+    with the operator evaluated step by step through the warp kernel (v / 2^7, then seven times v + warp(v, v)) - the same arithmetic, to
+    fp32 rounding at worst - and with the float64 oracle; the backward pass (which reads the intermediate fields the forward saved)
+    against autograd through the oracle"""
     gen = torch.Generator().manual_seed(B * 100 + size[0])
     v = torch.randn(B, 3, *size, generator=gen) * 2.0
     up = torch.randn(B, 3, *size, generator=gen)

@@ -487,6 +487,65 @@ def test_pyramid_references_match_the_oracle():
         assert float((R.resize_ref(x, want.shape[2:], (1 / f,) * 3) - want).abs().max()) < 1e-12
 
 
+def test_vecint_references_are_the_oracles_vecint_and_its_gradient(golden):
+    """tests/pyramid_ref.py's VecInt helpers on the `vecint` golden inputs, in float64 at rtol 1e-12: the last field of vecint_chain_ref is
+    O.vecint; the step gradients g + gd + gi, chained backwards over the seven stored fields and scaled by 2^-7, are autograd through
+    O.vecint (so the displacement-role / image-role split of vecint_step_grads_ref loses nothing).  Also: the depth-1 form is
+    slice_ref.vecint_ref on the (y, x) channels, a nudged displacement changes gd only, and the field generators do what they say"""
+    import pyramid_ref as R
+    import slice_ref as S
+    g = golden("vecint")
+    for s in ("", "2"):
+        v, up = T(g["v" + s]).double(), T(g["up" + s]).double()
+        vr = v.clone().requires_grad_(True)
+        out = O.vecint(vr, 7)
+        gv, = torch.autograd.grad((out * up).sum(), [vr])
+        chain = R.vecint_chain_ref(v, 7)
+        assert len(chain) == 8 and torch.equal(chain[0], v / 128)
+        np.testing.assert_allclose(chain[-1].numpy(), out.detach().numpy(), rtol=1e-12, atol=0)
+        np.testing.assert_allclose(R.vecint_step_ref(chain[3]).numpy(), chain[4].numpy(), rtol=1e-12, atol=0)
+        gk = up
+        for k in range(6, -1, -1):
+            gd, gi = R.vecint_step_grads_ref(chain[k], gk)
+            gk = gk + gd + gi
+        np.testing.assert_allclose((gk / 128).numpy(), gv.numpy(), rtol=1e-12, atol=1e-12 * float(gv.abs().max()))
+        # a nudged displacement samples the same image: gi is that of warp(disp, w), gd changes, and disp = w changes nothing
+        gd0, gi0 = R.vecint_step_grads_ref(chain[6], up)
+        gd1, gi1 = R.vecint_step_grads_ref(chain[6], up, disp=chain[6].clone())
+        assert torch.equal(gd0, gd1) and torch.equal(gi0, gi1)
+        d, i = (chain[6] + 0.25).requires_grad_(True), chain[6].clone().requires_grad_(True)
+        wd, wi = torch.autograd.grad((O.warp(d, i) * up).sum(), [d, i])
+        gd2, gi2 = R.vecint_step_grads_ref(chain[6], up, disp=chain[6] + 0.25)
+        assert torch.equal(gd2, wd) and torch.equal(gi2, wi) and not torch.equal(gd2, gd0)
+        assert len(R.vecint_chain_ref(v, 0)) == 1 and torch.equal(R.vecint_chain_ref(v, 0)[0], v)
+        # the corner contributions of one voxel are the image-role gradient of a delta upstream gradient at that voxel
+        delta = torch.zeros_like(up)
+        delta[0, 1, 2, 3, 1] = 1.7
+        want = torch.zeros_like(up)
+        for (iz, iy, ix), val in R.vecint_corner_contributions(chain[6], delta, 0, 1, 2, 3, 1):
+            want[0, 1, iz, iy, ix] += val
+        np.testing.assert_allclose(R.vecint_step_grads_ref(chain[6], delta)[1].numpy(), want.numpy(), rtol=1e-12, atol=1e-15)
+    # depth 1: the 2-D operator on channels (y, x); a zero z channel stays zero
+    v2 = R.vecint_field("smooth", 2, (1, 9, 11), amp=4.0).double()
+    assert float(v2[:, 0].abs().max()) == 0 and abs(float(v2.abs().max()) - 4.0) < 1e-6
+    c2 = R.vecint_chain_ref(v2, 7)
+    np.testing.assert_allclose(c2[-1][:, 1:, 0].numpy(), S.vecint_ref(v2[:, 1:, 0], 7).numpy(), rtol=1e-12, atol=0)
+    assert float(c2[-1][:, 0].abs().max()) == 0
+    assert [a for a, _, _ in R.vecint_coords(v2)] == [1, 2] and R.vecint_clamped_at_every_face(c2[6])
+    # generators: the band field keeps every coordinate off the integers and has the three slopes; the zero field of an even size too;
+    # a coordinate put on an integer is found
+    wb = R.vecint_field("bands", 2, (9, 26, 29)).double()
+    assert not bool(R.vecint_near_cell_boundary(wb).any())
+    dx = (wb[0, 2, 0, 0, 1:] - wb[0, 2, 0, 0, :-1]) / 0.97
+    assert sorted(set(round(float(t)) for t in dx)) == [-1, 0, 1] and float((dx - dx.round()).abs().max()) < 1e-6
+    assert not bool(R.vecint_near_cell_boundary(torch.zeros(1, 3, 8, 10, 12, dtype=torch.float64)).any())
+    wz = torch.zeros(1, 3, 9, 10, 12, dtype=torch.float64)          # odd extent: the middle plane samples c = 4 exactly
+    near = R.vecint_near_cell_boundary(wz)
+    assert bool(near[0, :, 4].all()) and int(near.sum()) == 3 * 10 * 12
+    big = R.vecint_field("smooth_large", 1, (12, 26, 29), amp=4.0)
+    assert abs(float(big.abs().max()) - 4.0) < 1e-5 and float((big[..., 8:16].amax(-1) - big[..., 8:16].amin(-1)).max()) > 2.0
+
+
 def test_pyramid_comparison_rejects_a_one_element_error():
     """the element-wise bound of the pyramid tests has power: moving one element of the reference by 1e-3 max|ref| - on a border plane, in
     the last pixel block - is rejected at the tolerances those tests use"""
