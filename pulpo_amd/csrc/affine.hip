@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void affine_compose_kernel(const float* __rest
     }
 }
 
-inline int eblocks(long items, long cap) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, cap)); }
+using pulpo::eblocks;
 
 inline bool rows4(int W, const void* a, const void* b) { return W % 4 == 0 && ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0; }
 

@@ -35,7 +35,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 }
 
 // sum over a workgroup of 256 in a fixed order (wave shuffles, then four adds; sh: 4 floats of LDS); valid in thread 0.  Every thread of the
-// block must call it.  (losses.hip, metrics.hip and mind.hip keep file-local copies of the same function.)
+// block must call it.
 __device__ __forceinline__ float block_sum_256(float v, float* sh) {
     v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
@@ -55,6 +55,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// workgroups of 256 for `items` work items, at least one and at most `cap` (grid-stride kernels; every call site states its own cap)
+inline int eblocks(long items, long cap) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, cap)); }
 
 }  // namespace pulpo
 

@@ -15,6 +15,7 @@
 // (conv3d_wgrad_w2.hip) - fewer matrix instructions, all arithmetic still fp32.
 #include "conv_shared.h"
 #include "act_io.h"
+#include "conv_epilogue.h"
 
 namespace {
 
@@ -105,15 +106,8 @@ __global__ __launch_bounds__(256, TZv == 4 ? 3 : 2) void conv3d_k3_mfma(ConvArgs
     const int lid0 = pulpo::xcd_remap(blockIdx.x, gridDim.x);
     const int split = lid0 % a.ksplit;          // splits of one tile are neighbours: they share the halo in L2
     const int lid = lid0 / a.ksplit;
-    const int cot = lid % a.ncot;
-    const int tile_lin = lid / a.ncot;
-    int t = tile_lin;
-    const int tx_ = t % a.ntx; t /= a.ntx;
-    const int ty_ = t % a.nty; t /= a.nty;
-    const int tz_ = t % a.ntz;
-    const int b = t / a.ntz;
-    const int z0 = tz_ * TZv, y0 = ty_ * TY, x0 = tx_ * TX;
-    const int co0 = cot * NT;
+    const TileId tl = decode_tile(a, lid, TZv, NT);
+    const int tile_lin = tl.tile_lin, b = tl.b, z0 = tl.z0, y0 = tl.y0, x0 = tl.x0, co0 = tl.co0;
     const int nchunk_all = (a.Cin + CH - 1) / CH;
     const int cper = (nchunk_all + a.ksplit - 1) / a.ksplit;
     const int chunk0 = split * cper, chunk1 = min(nchunk_all, chunk0 + cper);
@@ -214,10 +208,7 @@ __global__ __launch_bounds__(256, TZv == 4 ? 3 : 2) void conv3d_k3_mfma(ConvArgs
                     const long vox = (long)(gz * a.H + gy) * a.W + gx;
                     if (a.ksplit > 1) a.part[(((long)split * a.B + b) * a.D * a.H * a.W + vox) * a.Cout + co] = val;   // this split's partial sum
                     else {
-                        if (fuse) {                       // the arithmetic of bn_lrelu_apply_kernel
-                            const float t = val * fsc + fsh;
-                            val = t > 0.f ? t : t * a.slope;
-                        }
+                        if (fuse) val = pulpo::bn_lrelu(val, fsc, fsh, a.slope);      // the arithmetic of bn_lrelu_apply_kernel
                         out_b[vox * a.out_ps + (long)co * a.out_cs] = val;
                     }
                     s += val;
@@ -239,14 +230,7 @@ __global__ __launch_bounds__(256, TZv == 4 ? 3 : 2) void conv3d_k3_mfma(ConvArgs
             }
         }
         __syncthreads();
-        if (tid < 2 * NT) {
-            const int which = tid / NT, c = tid - which * NT;
-            if (co0 + c < a.Cout) {
-                const float tot = red[(0 * 2 + which) * NT + c] + red[(1 * 2 + which) * NT + c] + red[(2 * 2 + which) * NT + c] +
-                                  red[(3 * 2 + which) * NT + c];
-                a.stats[((long)tile_lin * 2 + which) * a.Cout + co0 + c] = tot;
-            }
-        }
+        stats_store<4, NT>(true, red, a.stats, tile_lin, a.Cout, co0, tid);
     }
 }
 
@@ -281,20 +265,8 @@ __global__ __launch_bounds__(256, CH == 2 ? 3 : 2) void conv3d_k3_smallk_pw(Conv
     const int i = lane & 31, kk = lane >> 5;
     const int nwork = a.B * a.ntz * a.nty * a.ntx * a.ncot, nwg = gridDim.x;
 
-    struct Tile { int tile_lin, b, z0, y0, x0, co0; };
-    auto describe = [&](int work) {
-        Tile t;
-        const int cot = work % a.ncot;
-        t.tile_lin = work / a.ncot;
-        int q = t.tile_lin;
-        const int tx_ = q % a.ntx; q /= a.ntx;
-        const int ty_ = q % a.nty; q /= a.nty;
-        const int tz_ = q % a.ntz;
-        t.b = q / a.ntz;
-        t.z0 = tz_ * 4; t.y0 = ty_ * TY; t.x0 = tx_ * TX;
-        t.co0 = cot * NT;
-        return t;
-    };
+    using Tile = TileId;
+    auto describe = [&](int work) { return decode_tile(a, work, 4, NT); };
 
     // ---- this thread's halo floats: j = channel * PHV + halo voxel (voxel fastest: planar operands are read in runs along x)
     const int in_bytes = (int)((((long)a.Cin - 1) * a.in_cs + ((long)a.D * a.H * a.W - 1) * a.in_ps + 1) * 4);
@@ -344,12 +316,8 @@ __global__ __launch_bounds__(256, CH == 2 ? 3 : 2) void conv3d_k3_smallk_pw(Conv
     int buf = 0;
     int pend_tile = -1, pend_co0 = 0;
     auto flush_stats = [&]() {
-        if (a.stats != nullptr && pend_tile >= 0 && tid < 2 * NT) {
-            const int which = tid / NT, c = tid - which * NT;
-            const float* red = red_all + (buf ^ 1) * (4 * 2 * NT);      // (buf has been flipped since the pending tile wrote its sums)
-            const float tot = red[(0 * 2 + which) * NT + c] + red[(1 * 2 + which) * NT + c] + red[(2 * 2 + which) * NT + c] + red[(3 * 2 + which) * NT + c];
-            a.stats[((long)pend_tile * 2 + which) * a.Cout + pend_co0 + c] = tot;
-        }
+        // (buf has been flipped since the pending tile wrote its sums; host: Cout % 32 == 0, every cout tile is full)
+        stats_store<4, NT, true>(a.stats != nullptr && pend_tile >= 0, red_all + (buf ^ 1) * (4 * 2 * NT), a.stats, pend_tile, a.Cout, pend_co0, tid);
     };
     float* xch = xch_all + wave * (64 * 32);
 
@@ -399,10 +367,7 @@ __global__ __launch_bounds__(256, CH == 2 ? 3 : 2) void conv3d_k3_smallk_pw(Conv
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float val = acc[m][r] + bias;
-                if (fused) {
-                    const float t = val * fsc + fsh;
-                    val = t > 0.f ? t : t * a.slope;
-                }
+                if (fused) val = pulpo::bn_lrelu(val, fsc, fsh, a.slope);
                 s += val;
                 q += val * val;
                 xch[(m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk) * 32 + i] = val;
@@ -451,10 +416,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
             float v = 0.f;
             for (int k = 0; k < ksplit; ++k) v += part[((long)k * npix + p) * C + c];
             const long b = p / V, vox = p - b * V;
-            if (fuse) {
-                const float t = pulpo::as_stored<TO>(v) * fsc + fsh;
-                v = t > 0.f ? t : t * slope;
-            }
+            if (fuse) v = pulpo::bn_lrelu(pulpo::as_stored<TO>(v), fsc, fsh, slope);
             v = pulpo::as_stored<TO>(v);
             float v1[1] = {v};
             pulpo::stv<1>(out + b * obs + vox * ops + (long)c * ocs, v1);
@@ -502,7 +464,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const float* __r
             }
             const long b = p / V, vox = p - b * V;
             if (fuse) {
-                auto act = [&](float x, float sc, float sh) { const float t = pulpo::as_stored<TO>(x) * sc + sh; return t > 0.f ? t : t * slope; };
+                auto act = [&](float x, float sc, float sh) { return pulpo::bn_lrelu(pulpo::as_stored<TO>(x), sc, sh, slope); };
                 v = make_float4(act(v.x, fsc.x, fsh.x), act(v.y, fsc.y, fsh.y), act(v.z, fsc.z, fsh.z), act(v.w, fsc.w, fsh.w));
             }
             v = make_float4(pulpo::as_stored<TO>(v.x), pulpo::as_stored<TO>(v.y), pulpo::as_stored<TO>(v.z), pulpo::as_stored<TO>(v.w));

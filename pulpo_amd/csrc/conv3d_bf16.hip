@@ -10,6 +10,7 @@
 // LDS tiles [voxel][32 + 8] bf16 (80-byte rows: 16-byte fragments, conflict-free ds_read_b128).
 #include "conv_shared.h"
 #include "act_io.h"
+#include "conv_epilogue.h"
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
@@ -139,15 +140,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16(ConvArgsH a) {
     const int lid0 = pulpo::xcd_remap(blockIdx.x, gridDim.x);
     const int split = lid0 % a.ksplit;
     const int lid = lid0 / a.ksplit;
-    const int cot = lid % a.ncot;
-    const int tile_lin = lid / a.ncot;
-    int t = tile_lin;
-    const int tx_ = t % a.ntx; t /= a.ntx;
-    const int ty_ = t % a.nty; t /= a.nty;
-    const int tz_ = t % a.ntz;
-    const int b = t / a.ntz;
-    const int z0 = tz_ * TZv, y0 = ty_ * TY, x0 = tx_ * TX;
-    const int co0 = cot * NT;
+    const pulpo_conv::TileId tl = pulpo_conv::decode_tile(a, lid, TZv, NT);
+    const int tile_lin = tl.tile_lin, b = tl.b, z0 = tl.z0, y0 = tl.y0, x0 = tl.x0, co0 = tl.co0;
     const int nchunk_all = (a.Cin + CH - 1) / CH;
     const int cper = (nchunk_all + a.ksplit - 1) / a.ksplit;
     const int chunk0 = split * cper, chunk1 = min(nchunk_all, chunk0 + cper);
@@ -260,10 +254,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16(ConvArgsH a) {
                 const bool inb = gz < a.D && gy < a.H && gx < a.W;
                 float val = acc[m][n][r] + bias;
                 if (a.ksplit == 1) {
-                    if (fuse) {
-                        const float t = pulpo::as_stored<T>(val) * fsc + fsh;        // (the pre-norm value as the unfused path would have stored it)
-                        val = t > 0.f ? t : t * a.slope;
-                    }
+                    if (fuse) val = pulpo::bn_lrelu(pulpo::as_stored<T>(val), fsc, fsh, a.slope);        // (the pre-norm value as the unfused path would have stored it)
                     val = pulpo::as_stored<T>(val);
                 }
                 const long vox = (long)(gz * a.H + gy) * a.W + gx;
@@ -299,14 +290,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16(ConvArgsH a) {
             }
         }
         __syncthreads();
-        if (tid < 2 * NT) {
-            const int which = tid / NT, c = tid - which * NT;
-            if (co0 + c < a.Cout) {
-                const float tot = red[(0 * 2 + which) * NT + c] + red[(1 * 2 + which) * NT + c] + red[(2 * 2 + which) * NT + c] +
-                                  red[(3 * 2 + which) * NT + c];
-                a.stats[((long)tile_lin * 2 + which) * a.Cout + co0 + c] = tot;
-            }
-        }
+        pulpo_conv::stats_store<4, NT>(true, red, a.stats, tile_lin, a.Cout, co0, tid);
     }
 }
 
@@ -347,20 +331,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
     const int nwork = a.B * a.ntz * a.nty * a.ntx * a.ncot, nwg = gridDim.x;
     const int nchunk = a.Cin / CH;
 
-    struct Tile { int tile_lin, b, z0, y0, x0, co0; };
-    auto describe = [&](int work) {
-        Tile t;
-        const int cot = work % a.ncot;
-        t.tile_lin = work / a.ncot;
-        int q = t.tile_lin;
-        const int tx_ = q % a.ntx; q /= a.ntx;
-        const int ty_ = q % a.nty; q /= a.nty;
-        const int tz_ = q % a.ntz;
-        t.b = q / a.ntz;
-        t.z0 = tz_ * 4; t.y0 = ty_ * TY; t.x0 = tx_ * TX;
-        t.co0 = cot * NT;
-        return t;
-    };
+    using Tile = pulpo_conv::TileId;
+    auto describe = [&](int work) { return pulpo_conv::decode_tile(a, work, 4, NT); };
 
     // ---- halo pieces of this thread: piece j = (halo voxel j / 4, 8-channel slot j % 4)
     const unsigned ps_bytes = (unsigned)a.in_ps * 2u;
@@ -464,12 +436,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
     int buf = 0;
     int pend_tile = -1, pend_co0 = 0;                   // tile whose partial statistics wait in `red`
     auto flush_stats = [&]() {                          // (behind a barrier that followed the writes of `red`; the next writes are four barriers away)
-        if (a.stats != nullptr && pend_tile >= 0 && tid < 2 * NT) {
-            const int which = tid / NT, c = tid - which * NT;
-            const float tot = red[(0 * 2 + which) * NT + c] + red[(1 * 2 + which) * NT + c] + red[(2 * 2 + which) * NT + c] +
-                              red[(3 * 2 + which) * NT + c];
-            a.stats[((long)pend_tile * 2 + which) * a.Cout + pend_co0 + c] = tot;
-        }
+        pulpo_conv::stats_store<4, NT, true>(a.stats != nullptr && pend_tile >= 0, red, a.stats, pend_tile, a.Cout, pend_co0, tid);
     };
 
     for (;;) {
@@ -581,9 +548,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_mfma_bf16_pw(ConvArgsH a) {
                 for (int r = 0; r < 16; r += 2) {
                     float v0 = acc[m][n][r] + bias, v1 = acc[m][n][r + 1] + bias;
                     if (fused) {
-                        const float t0 = pulpo::as_stored<T>(v0) * fsc + fsh, t1 = pulpo::as_stored<T>(v1) * fsc + fsh;
-                        v0 = t0 > 0.f ? t0 : t0 * a.slope;
-                        v1 = t1 > 0.f ? t1 : t1 * a.slope;
+                        v0 = pulpo::bn_lrelu(pulpo::as_stored<T>(v0), fsc, fsh, a.slope);
+                        v1 = pulpo::bn_lrelu(pulpo::as_stored<T>(v1), fsc, fsh, a.slope);
                     }
                     const uint32_t h = pulpo::pack_bf2(v0, v1);                    // (x, x + 1) of this lane's channel, rounded
                     const f32x2 rr = {__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};

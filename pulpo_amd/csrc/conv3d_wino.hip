@@ -4,6 +4,7 @@
 // conv3d_wino2p.hip does not take: planar inputs, channel counts that are not multiples of 8, volumes of 2 GiB and more.
 // Same argument block, tile order, BatchNorm partial statistics and fused eval-mode epilogue as the direct kernel in conv3d.hip.
 #include "conv_shared.h"
+#include "conv_epilogue.h"
 #include "../../include/pulpo_hip.h"
 #include "wino3_pack.h"
 
@@ -150,15 +151,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2_mfma(ConvArgs a) {
     };
     auto describe = [&](int work) {
         Tile t;
-        const int cot = work % a.ncot;
-        t.tile_lin = work / a.ncot;
-        int q = t.tile_lin;
-        const int tx_ = q % a.ntx; q /= a.ntx;
-        const int ty_ = q % a.nty; q /= a.nty;
-        const int tz_ = q % a.ntz;
-        t.b = q / a.ntz;
-        t.z0 = tz_ * 4; t.y0 = ty_ * TY; t.x0 = tx_ * TX;
-        t.co0 = cot * NT;
+        const TileId id = decode_tile(a, work, 4, NT);
+        t.tile_lin = id.tile_lin; t.b = id.b; t.z0 = id.z0; t.y0 = id.y0; t.x0 = id.x0; t.co0 = id.co0;
         t.origin = reinterpret_cast<const char*>(a.in + (long)t.b * a.in_bs) + ((long)((t.z0 - 1) * a.H + (t.y0 - 1)) * a.W + (t.x0 - 1)) * a.in_ps * 4;
         t.wsrc = a.wp + ((long)wave * a.NPad + t.co0) * CH;                      // (wave-uniform; the lane's 16 bytes are added at the issue)
         t.rmask = 0;
@@ -350,79 +344,21 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2_mfma(ConvArgs a) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             __syncthreads();                                // every wave has left xs (main loop) / the exchange buffer (previous row tile)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float m0 = acc[m][0][r], m1 = acc[m][1][r], m2 = acc[m][2][r], m3 = acc[m][3][r];
-                R[((py * 2 + 0) * 16 + r) * 64 + elane] = m0 + m1 + m2;
-                R[((py * 2 + 1) * 16 + r) * 64 + elane] = m1 - m2 - m3;
-            }
+            wino2_exchange_write(R, acc[m], py, elane);
             float4 yv[2][2];                                // (bnr) the pre-norm activations of this lane's four voxels, requested once this row tile's accumulators are dead
-            if (bnr) {
+            if (bnr) {                                      // (own text of wino2_load_y, conv_epilogue.h: the call costs <true, true> one more SGPR spill)
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const int combo = h * 16 + wave * 4 + g;
-                    const int ox = combo >> 4, r = combo & 15;
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-                    const int gz = z0 + 2 * m + (row >> 4), gy = y0 + 2 * ((row >> 2) & 3), gx = x0 + 2 * (row & 3) + ox;
-                    const long vox = (long)(gz * a.H + gy) * a.W + gx;
-                    yv[h][0] = *reinterpret_cast<const float4*>(bn_b + vox * a.bn_y_ps);
-                    yv[h][1] = *reinterpret_cast<const float4*>(bn_b + (vox + a.W) * a.bn_y_ps);
+                    const Wino2Voxel v = wino2_voxel(a, h, m, wave, g, kh, z0, y0, x0);
+                    yv[h][0] = *reinterpret_cast<const float4*>(bn_b + v.vox * a.bn_y_ps);
+                    yv[h][1] = *reinterpret_cast<const float4*>(bn_b + (v.vox + a.W) * a.bn_y_ps);
                 }
             }
             __syncthreads();
-            if (fast) {
-                float4 tq[2][4];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int combo = h * 16 + wave * 4 + g;               // (ox, r) = (combo >> 4, combo & 15)
-#pragma unroll
-                    for (int p = 0; p < 4; ++p)
-                        tq[h][p] = *reinterpret_cast<const float4*>(R + ((p * 2 + (combo >> 4)) * 16 + (combo & 15)) * 64 + kh * 32 + 4 * q);
-                }
-                float* obase = out_b + co0 + 4 * q;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int combo = h * 16 + wave * 4 + g;
-                    const int ox = combo >> 4, r = combo & 15;
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-                    const int gz = z0 + 2 * m + (row >> 4), gy = y0 + 2 * ((row >> 2) & 3), gx = x0 + 2 * (row & 3) + ox;
-                    const long vox = (long)(gz * a.H + gy) * a.W + gx;
-                    const float4 t0 = tq[h][0], t1 = tq[h][1], t2 = tq[h][2], t3 = tq[h][3];
-                    float4 v0 = make_float4(t0.x + t1.x + t2.x + b4.x, t0.y + t1.y + t2.y + b4.y, t0.z + t1.z + t2.z + b4.z, t0.w + t1.w + t2.w + b4.w);
-                    float4 v1 = make_float4(t1.x - t2.x - t3.x + b4.x, t1.y - t2.y - t3.y + b4.y, t1.z - t2.z - t3.z + b4.z, t1.w - t2.w - t3.w + b4.w);
-                    if (bnr) {
-                        // dbn = dz * lrelu'(bn(y));  sums of dbn and of dbn * (y - fp32 mean): all fp32 (the difference of two floats carries
-                        // a relative error of 2^-24 however close they are; what the ROUNDED mean leaves out is added back, in double, by
-                        // the finalize kernel: sum dbn * xhat = rstd * (sum dbn * (y - m32) - (mean - m32) * sum dbn))
-                        auto red1 = [&](float dzv, float yy, float sc, float sh, float m32, float& s_, float& q_) {
-                            const float bn = yy * sc + sh;
-                            const float d = bn > 0.f ? dzv : dzv * a.slope;
-                            s_ += d;
-                            q_ = fmaf(d, yy - m32, q_);
-                        };
-                        red1(v0.x, yv[h][0].x, sc4.x, sh4.x, bm4.x, s4.x, q4.x);
-                        red1(v0.y, yv[h][0].y, sc4.y, sh4.y, bm4.y, s4.y, q4.y);
-                        red1(v0.z, yv[h][0].z, sc4.z, sh4.z, bm4.z, s4.z, q4.z);
-                        red1(v0.w, yv[h][0].w, sc4.w, sh4.w, bm4.w, s4.w, q4.w);
-                        red1(v1.x, yv[h][1].x, sc4.x, sh4.x, bm4.x, s4.x, q4.x);
-                        red1(v1.y, yv[h][1].y, sc4.y, sh4.y, bm4.y, s4.y, q4.y);
-                        red1(v1.z, yv[h][1].z, sc4.z, sh4.z, bm4.z, s4.z, q4.z);
-                        red1(v1.w, yv[h][1].w, sc4.w, sh4.w, bm4.w, s4.w, q4.w);
-                    } else {
-                        s4.x += v0.x + v1.x; s4.y += v0.y + v1.y; s4.z += v0.z + v1.z; s4.w += v0.w + v1.w;
-                        q4.x += v0.x * v0.x + v1.x * v1.x; q4.y += v0.y * v0.y + v1.y * v1.y; q4.z += v0.z * v0.z + v1.z * v1.z; q4.w += v0.w * v0.w + v1.w * v1.w;
-                    }
-                    if (fuse) {
-                        auto act = [&](float v, float sc, float sh) { const float tt = v * sc + sh; return tt > 0.f ? tt : tt * a.slope; };
-                        v0 = make_float4(act(v0.x, sc4.x, sh4.x), act(v0.y, sc4.y, sh4.y), act(v0.z, sc4.z, sh4.z), act(v0.w, sc4.w, sh4.w));
-                        v1 = make_float4(act(v1.x, sc4.x, sh4.x), act(v1.y, sc4.y, sh4.y), act(v1.z, sc4.z, sh4.z), act(v1.w, sc4.w, sh4.w));
-                    }
-                    *reinterpret_cast<float4*>(obase + vox * a.out_ps) = v0;
-                    *reinterpret_cast<float4*>(obase + (vox + a.W) * a.out_ps) = v1;
-                }
-            } else {
-                // general path: ragged tiles (volume edge), partial cout tiles, planar / strided outputs.  Wave w finishes x parity w & 1, rows
-                // 8 (w >> 1) .. 8 (w >> 1) + 7 of the row tile; lane = (row half kk, channel i)
+            if (fast) wino2_fast_path(R, out_b, a.out_ps, co0, a, m, wave, g, kh, q, z0, y0, x0, true, bnr, fuse, b4, sc4, sh4, bm4, yv, s4, q4);
+            // (own text: as a function shared with the other F(2x2,3x3) kernel this path costs 18 - 42 more SGPR spills - profiles/epilogue_share_ab.txt;
+            //  it mirrors the general path of conv3d_wino2p.hip line for line)
+            else {
                 const int fox = wave & 1;
 #pragma unroll
                 for (int rr = 0; rr < 8; ++rr) {
@@ -437,12 +373,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2_mfma(ConvArgs a) {
                         const long vox = (long)(gz * a.H + gy) * a.W + gx;
                         if (gy < a.H) {
                             ssum += v0; ssq += v0 * v0;
-                            if (fuse) { const float tt = v0 * fsc1 + fsh1; v0 = tt > 0.f ? tt : tt * a.slope; }
+                            if (fuse) v0 = pulpo::bn_lrelu(v0, fsc1, fsh1, a.slope);
                             out_b[vox * a.out_ps + (long)(co0 + ei) * a.out_cs] = v0;
                         }
                         if (gy + 1 < a.H) {
                             ssum += v1; ssq += v1 * v1;
-                            if (fuse) { const float tt = v1 * fsc1 + fsh1; v1 = tt > 0.f ? tt : tt * a.slope; }
+                            if (fuse) v1 = pulpo::bn_lrelu(v1, fsc1, fsh1, a.slope);
                             out_b[(vox + a.W) * a.out_ps + (long)(co0 + ei) * a.out_cs] = v1;
                         }
                     }
@@ -452,32 +388,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2_mfma(ConvArgs a) {
         if (a.stats != nullptr) {
             // per-tile BatchNorm partial sums: reduce over the lanes that hold the same channel(s), then over the four waves
             if (fast) {
-#pragma unroll
-                for (int o = 8; o <= 32; o <<= 1) {
-                    s4.x += __shfl_xor(s4.x, o, 64); s4.y += __shfl_xor(s4.y, o, 64); s4.z += __shfl_xor(s4.z, o, 64); s4.w += __shfl_xor(s4.w, o, 64);
-                    q4.x += __shfl_xor(q4.x, o, 64); q4.y += __shfl_xor(q4.y, o, 64); q4.z += __shfl_xor(q4.z, o, 64); q4.w += __shfl_xor(q4.w, o, 64);
-                }
-                if (elane < 8) {
-                    *reinterpret_cast<float4*>(red + (wave * 2 + 0) * NT + 4 * q) = s4;
-                    *reinterpret_cast<float4*>(red + (wave * 2 + 1) * NT + 4 * q) = q4;
-                }
+                quad_reduce_to_red<NT>(s4, q4, red, wave, elane);
             } else {
-                ssum += __shfl_xor(ssum, 32, 64);
-                ssq += __shfl_xor(ssq, 32, 64);
-                if (elane < 32) {
-                    red[(wave * 2 + 0) * NT + ei] = ssum;
-                    red[(wave * 2 + 1) * NT + ei] = ssq;
-                }
+                half_reduce_to_red<NT>(ssum, ssq, red, wave, elane);
             }
             __syncthreads();
-            if (tid < 2 * NT) {
-                const int which = tid / NT, c = tid - which * NT;
-                if (co0 + c < a.Cout) {
-                    const float tot = red[(0 * 2 + which) * NT + c] + red[(1 * 2 + which) * NT + c] + red[(2 * 2 + which) * NT + c] +
-                                      red[(3 * 2 + which) * NT + c];
-                    a.stats[((long)cur.tile_lin * 2 + which) * a.Cout + co0 + c] = tot;
-                }
-            }
+            stats_store<4, NT>(true, red, a.stats, cur.tile_lin, a.Cout, co0, tid);
         }
         if (!has_next) break;
         cur = nxt;

@@ -14,6 +14,7 @@
 //   * Image = [channel quad][row] float4s (rows = (hz, px, hy, x-pair), planes of 164 rows): the 16 lanes of every ds_read_b128 lane group
 //     fall on 16 different 16-byte slots without pad floats (rows {0-3, 24-27} of one plane and {8-11, 16-19} of the next, plane stride 4 mod 16).
 #include "conv_shared.h"
+#include "conv_epilogue.h"
 
 namespace {
 
@@ -329,26 +330,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             if (m > 0) __syncthreads();                 // every wave has left the exchange buffer (previous row tile)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float m0 = acc[m][0][r], m1 = acc[m][1][r], m2 = acc[m][2][r], m3 = acc[m][3][r];
-                R[((py * 2 + 0) * 16 + r) * 64 + elane] = m0 + m1 + m2;
-                R[((py * 2 + 1) * 16 + r) * 64 + elane] = m1 - m2 - m3;
-            }
-            float4 yv[2][2];                                // (bnr) the pre-norm activations of this lane's four voxels
-            if (bnr) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int combo = h * 16 + wave * 4 + g;
-                    const int ox = combo >> 4, r = combo & 15;
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-                    const int gz = z0 + 2 * m + (row >> 4), gy = y0 + 2 * ((row >> 2) & 3), gx = x0 + 2 * (row & 3) + ox;
-                    const long vox = (long)(gz * a.H + gy) * a.W + gx;
-                    yv[h][0] = *reinterpret_cast<const float4*>(bn_b + vox * a.bn_y_ps);
-                    yv[h][1] = *reinterpret_cast<const float4*>(bn_b + (vox + a.W) * a.bn_y_ps);
-                }
-            }
+            wino2_exchange_write(R, acc[m], py, elane);
+            float4 yv[2][2];                                // (bnr) the pre-norm activations of this lane's four voxels, requested once this row tile's accumulators are dead
+            if (bnr) wino2_load_y(yv, a, bn_b, m, wave, g, kh, z0, y0, x0);
             __syncthreads();
+            // (own text: calling wino2_fast_path - conv_epilogue.h, which this mirrors line for line - costs this kernel 13 more SGPR spills and 100 bytes,
+            //  profiles/epilogue_share_ab.txt)
             if (fast) {
                 float4 tq[2][4];
 #pragma unroll
@@ -368,45 +355,29 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                     const long vox = (long)(gz * a.H + gy) * a.W + gx;
                     const bool in0 = whole || (gz < a.D && gy < a.H && gx < a.W), in1 = whole || (gz < a.D && gy + 1 < a.H && gx < a.W);
                     const float4 t0 = tq[h][0], t1 = tq[h][1], t2 = tq[h][2], t3 = tq[h][3];
-                    float4 v0 = make_float4(t0.x + t1.x + t2.x + b4.x, t0.y + t1.y + t2.y + b4.y, t0.z + t1.z + t2.z + b4.z, t0.w + t1.w + t2.w + b4.w);
-                    float4 v1 = make_float4(t1.x - t2.x - t3.x + b4.x, t1.y - t2.y - t3.y + b4.y, t1.z - t2.z - t3.z + b4.z, t1.w - t2.w - t3.w + b4.w);
+                    float4 v0, v1;
+                    inverse_last(t0, t1, t2, t3, b4, v0, v1);
                     if (bnr) {
-                        // dbn = dz * lrelu'(bn(y));  sums of dbn and of dbn * (y - fp32 mean): all fp32 (what the ROUNDED mean leaves out is
-                        // added back, in double, by the finalize kernel: sum dbn * xhat = rstd * (sum dbn * (y - m32) - (mean - m32) * sum dbn))
-                        auto red1 = [&](float dzv, float yy, float sc, float sh, float m32, float& s_, float& q_) {
-                            const float bn = yy * sc + sh;
-                            const float d = bn > 0.f ? dzv : dzv * a.slope;
-                            s_ += d;
-                            q_ = fmaf(d, yy - m32, q_);
-                        };
-                        red1(v0.x, yv[h][0].x, sc4.x, sh4.x, bm4.x, s4.x, q4.x);
-                        red1(v0.y, yv[h][0].y, sc4.y, sh4.y, bm4.y, s4.y, q4.y);
-                        red1(v0.z, yv[h][0].z, sc4.z, sh4.z, bm4.z, s4.z, q4.z);
-                        red1(v0.w, yv[h][0].w, sc4.w, sh4.w, bm4.w, s4.w, q4.w);
-                        red1(v1.x, yv[h][1].x, sc4.x, sh4.x, bm4.x, s4.x, q4.x);
-                        red1(v1.y, yv[h][1].y, sc4.y, sh4.y, bm4.y, s4.y, q4.y);
-                        red1(v1.z, yv[h][1].z, sc4.z, sh4.z, bm4.z, s4.z, q4.z);
-                        red1(v1.w, yv[h][1].w, sc4.w, sh4.w, bm4.w, s4.w, q4.w);
+                        bn_bwd_reduce_pair(v0, v1, yv[h][0], yv[h][1], sc4, sh4, bm4, a.slope, s4, q4);     // (pulpo::bn_bwd_reduce_step, head_bn.h)
                     } else if (whole) {
-                        s4.x += v0.x + v1.x; s4.y += v0.y + v1.y; s4.z += v0.z + v1.z; s4.w += v0.w + v1.w;
-                        q4.x += v0.x * v0.x + v1.x * v1.x; q4.y += v0.y * v0.y + v1.y * v1.y; q4.z += v0.z * v0.z + v1.z * v1.z; q4.w += v0.w * v0.w + v1.w * v1.w;
+                        stats_add_pair(v0, v1, s4, q4);
                     } else {
-                        if (in0) { s4.x += v0.x; s4.y += v0.y; s4.z += v0.z; s4.w += v0.w; q4.x += v0.x * v0.x; q4.y += v0.y * v0.y; q4.z += v0.z * v0.z; q4.w += v0.w * v0.w; }
-                        if (in1) { s4.x += v1.x; s4.y += v1.y; s4.z += v1.z; s4.w += v1.w; q4.x += v1.x * v1.x; q4.y += v1.y * v1.y; q4.z += v1.z * v1.z; q4.w += v1.w * v1.w; }
+                        if (in0) stats_add_one(v0, s4, q4);
+                        if (in1) stats_add_one(v1, s4, q4);
                     }
                     if (fuse) {
-                        auto act = [&](float v, float sc, float sh) { const float tt = v * sc + sh; return tt > 0.f ? tt : tt * a.slope; };
-                        v0 = make_float4(act(v0.x, sc4.x, sh4.x), act(v0.y, sc4.y, sh4.y), act(v0.z, sc4.z, sh4.z), act(v0.w, sc4.w, sh4.w));
-                        v1 = make_float4(act(v1.x, sc4.x, sh4.x), act(v1.y, sc4.y, sh4.y), act(v1.z, sc4.z, sh4.z), act(v1.w, sc4.w, sh4.w));
+                        v0 = bn_lrelu4(v0, sc4, sh4, a.slope);
+                        v1 = bn_lrelu4(v1, sc4, sh4, a.slope);
                     }
                     {
                         if (in0) *reinterpret_cast<float4*>(obase + vox * o_ps) = v0;
                         if (in1) *reinterpret_cast<float4*>(obase + (vox + a.W) * o_ps) = v1;
                     }
                 }
-            } else {
-                // general path: ragged tiles (volume edge), partial cout tiles, planar / strided outputs.  Wave w finishes x parity w & 1, rows
-                // 8 (w >> 1) .. 8 (w >> 1) + 7 of the row tile; lane = (row half kk, channel i)
+            }
+            // (general path, own text: as a function shared with the other F(2x2,3x3) kernel it costs 18 - 42 more SGPR spills - profiles/epilogue_share_ab.txt;
+            //  it mirrors the general path of conv3d_wino.hip line for line)
+            else {
                 const int fox = wave & 1;
 #pragma unroll
                 for (int rr = 0; rr < 8; ++rr) {
@@ -421,12 +392,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
                         const long vox = (long)(gz * a.H + gy) * a.W + gx;
                         if (gy < a.H) {
                             ssum += v0; ssq += v0 * v0;
-                            if (fuse) { const float tt = v0 * fsc1 + fsh1; v0 = tt > 0.f ? tt : tt * a.slope; }
+                            if (fuse) v0 = pulpo::bn_lrelu(v0, fsc1, fsh1, a.slope);
                             out_b[vox * o_ps + (long)(co0 + ei) * o_cs] = v0;
                         }
                         if (gy + 1 < a.H) {
                             ssum += v1; ssq += v1 * v1;
-                            if (fuse) { const float tt = v1 * fsc1 + fsh1; v1 = tt > 0.f ? tt : tt * a.slope; }
+                            if (fuse) v1 = pulpo::bn_lrelu(v1, fsc1, fsh1, a.slope);
                             out_b[(vox + a.W) * o_ps + (long)(co0 + ei) * o_cs] = v1;
                         }
                     }
@@ -437,33 +408,13 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wino2p_mfma(ConvArgs a) {
         // separates the exchange buffer's last reads from the next tile's staging into the same image, so it is taken without statistics too.
         if (stats != nullptr) {
             if (fast) {
-#pragma unroll
-                for (int o = 8; o <= 32; o <<= 1) {
-                    s4.x += __shfl_xor(s4.x, o, 64); s4.y += __shfl_xor(s4.y, o, 64); s4.z += __shfl_xor(s4.z, o, 64); s4.w += __shfl_xor(s4.w, o, 64);
-                    q4.x += __shfl_xor(q4.x, o, 64); q4.y += __shfl_xor(q4.y, o, 64); q4.z += __shfl_xor(q4.z, o, 64); q4.w += __shfl_xor(q4.w, o, 64);
-                }
-                if (elane < 8) {
-                    *reinterpret_cast<float4*>(red + (wave * 2 + 0) * NT + 4 * q) = s4;
-                    *reinterpret_cast<float4*>(red + (wave * 2 + 1) * NT + 4 * q) = q4;
-                }
+                quad_reduce_to_red<NT>(s4, q4, red, wave, elane);
             } else {
-                ssum += __shfl_xor(ssum, 32, 64);
-                ssq += __shfl_xor(ssq, 32, 64);
-                if (elane < 32) {
-                    red[(wave * 2 + 0) * NT + ei] = ssum;
-                    red[(wave * 2 + 1) * NT + ei] = ssq;
-                }
+                half_reduce_to_red<NT>(ssum, ssq, red, wave, elane);
             }
         }
         __syncthreads();
-        if (stats != nullptr && tid < 2 * NT) {
-            const int which = tid / NT, c = tid - which * NT;
-            if (co0 + c < a.Cout) {
-                const float tot = red[(0 * 2 + which) * NT + c] + red[(1 * 2 + which) * NT + c] + red[(2 * 2 + which) * NT + c] +
-                                  red[(3 * 2 + which) * NT + c];
-                stats[((long)cur.tile_lin * 2 + which) * a.Cout + co0 + c] = tot;
-            }
-        }
+        stats_store<4, NT>(stats != nullptr, red, stats, cur.tile_lin, a.Cout, co0, tid);
         if (!has_next) break;
         cur = nxt;
         work = next_work;

@@ -25,6 +25,7 @@
 // vmcnt behind them becomes a worst-case guess); the plane offset must ride in the VECTOR offset of a buffer load (the bounds check that
 // zeroes out-of-volume planes ignores the scalar offset).
 #include "conv_shared.h"
+#include "conv_epilogue.h"
 #include "wino3_pack.h"
 
 namespace {
@@ -206,13 +207,7 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
     // are not written again before the next tile's epilogue, nchunk barriers away.
     int pend_tile = -1, pend_co0 = 0;
     auto flush_stats = [&]() {
-        if (a.stats != nullptr && pend_tile >= 0 && tid < 2 * NT) {
-            const int which = tid / NT, c = tid - which * NT;
-            float tot = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) tot += red[(w * 2 + which) * NT + c];
-            if (pend_co0 + c < a.Cout) a.stats[((long)pend_tile * 2 + which) * a.Cout + pend_co0 + c] = tot;
-        }
+        stats_store<8, NT>(a.stats != nullptr && pend_tile >= 0, red, a.stats, pend_tile, a.Cout, pend_co0, tid);
         pend_tile = -1;
     };
     for (;;) {
@@ -405,28 +400,17 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
                 const float4 u1 = *reinterpret_cast<const float4*>(R + (((1 * 4 + p) * 2 + ox) * 16 + rr) * 64 + kh * 32 + 4 * q);
                 t[p] = make_float4(u0.x + u1.x, u0.y + u1.y, u0.z + u1.z, u0.w + u1.w);
             }
-            float4 v0 = make_float4(t[0].x + t[1].x + t[2].x + b4.x, t[0].y + t[1].y + t[2].y + b4.y, t[0].z + t[1].z + t[2].z + b4.z, t[0].w + t[1].w + t[2].w + b4.w);
-            float4 v1 = make_float4(t[1].x - t[2].x - t[3].x + b4.x, t[1].y - t[2].y - t[3].y + b4.y, t[1].z - t[2].z - t[3].z + b4.z, t[1].w - t[2].w - t[3].w + b4.w);
+            float4 v0, v1;
+            inverse_last(t[0], t[1], t[2], t[3], b4, v0, v1);
             if (BNR) {
-                auto red1 = [&](float dzv, float yy, float sc, float sh, float m32, float& s_, float& q_) {
-                    const float bn = yy * sc + sh;
-                    const float d = bn > 0.f ? dzv : dzv * a.slope;
-                    s_ += d;
-                    q_ = fmaf(d, yy - m32, q_);
-                };
-                red1(v0.x, yv0.x, sc4.x, sh4.x, bm4.x, s4.x, q4.x); red1(v0.y, yv0.y, sc4.y, sh4.y, bm4.y, s4.y, q4.y);
-                red1(v0.z, yv0.z, sc4.z, sh4.z, bm4.z, s4.z, q4.z); red1(v0.w, yv0.w, sc4.w, sh4.w, bm4.w, s4.w, q4.w);
-                red1(v1.x, yv1.x, sc4.x, sh4.x, bm4.x, s4.x, q4.x); red1(v1.y, yv1.y, sc4.y, sh4.y, bm4.y, s4.y, q4.y);
-                red1(v1.z, yv1.z, sc4.z, sh4.z, bm4.z, s4.z, q4.z); red1(v1.w, yv1.w, sc4.w, sh4.w, bm4.w, s4.w, q4.w);
+                bn_bwd_reduce_pair(v0, v1, yv0, yv1, sc4, sh4, bm4, a.slope, s4, q4);     // (pulpo::bn_bwd_reduce_step, head_bn.h)
                 if (oz == 0) { __builtin_amdgcn_sched_barrier(0); load_y(1); __builtin_amdgcn_sched_barrier(0); }
             } else {
-                s4.x += v0.x + v1.x; s4.y += v0.y + v1.y; s4.z += v0.z + v1.z; s4.w += v0.w + v1.w;
-                q4.x += v0.x * v0.x + v1.x * v1.x; q4.y += v0.y * v0.y + v1.y * v1.y; q4.z += v0.z * v0.z + v1.z * v1.z; q4.w += v0.w * v0.w + v1.w * v1.w;
+                stats_add_pair(v0, v1, s4, q4);
             }
             if (fuse) {
-                auto act = [&](float v, float sc, float sh) { const float tt = v * sc + sh; return tt > 0.f ? tt : tt * a.slope; };
-                v0 = make_float4(act(v0.x, sc4.x, sh4.x), act(v0.y, sc4.y, sh4.y), act(v0.z, sc4.z, sh4.z), act(v0.w, sc4.w, sh4.w));
-                v1 = make_float4(act(v1.x, sc4.x, sh4.x), act(v1.y, sc4.y, sh4.y), act(v1.z, sc4.z, sh4.z), act(v1.w, sc4.w, sh4.w));
+                v0 = bn_lrelu4(v0, sc4, sh4, a.slope);
+                v1 = bn_lrelu4(v1, sc4, sh4, a.slope);
             }
             float* obase = out_b + (long)((co0 + 4 * q) >> 3) * a.out_kb + ((4 * q) & 7);      // (out_kb = 8: channels-last, co0 + 4 q)
             if (qok) {

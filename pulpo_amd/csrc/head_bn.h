@@ -1,5 +1,7 @@
-// Expressions shared by the BatchNorm / LeakyReLU passes (norm_act.hip) and the 1x1x1 head kernels that form the activation and its gradient
-// themselves (heads.hip: the last ConvUnit in front of a head - its output z and the gradient dz have one reader each and are never written).
+// Expressions shared by the BatchNorm / LeakyReLU passes (norm_act.hip), the 1x1x1 head kernels that form the activation and its gradient
+// themselves (heads.hip: the last ConvUnit in front of a head - its output z and the gradient dz have one reader each and are never written)
+// and the convolution kernels (conv3d*.hip): their eval-mode fused store is bn_lrelu, and the data-gradient kernels that deliver the
+// BatchNorm-backward sums of the unit in front take bn_bwd_reduce_step per element.
 // ONE definition each, as sampling.h does for the warp coordinate: the fp32 results of the fused kernels are then the separate passes' bits.
 #pragma once
 #include "common.h"
@@ -10,6 +12,17 @@ namespace pulpo {
 __device__ __forceinline__ float bn_lrelu(float y, float scale, float shift, float slope) {
     const float t = y * scale + shift;
     return t > 0.f ? t : t * slope;
+}
+
+// One element of the first BatchNorm-backward pass: dbn = dz * lrelu'(bn(y));  s0 += dbn,  s1 += dbn * (y - m32), m32 = the batch mean rounded
+// to fp32.  All fp32: the difference of two floats carries a relative error of 2^-24 however close they are, and what the ROUNDED mean leaves
+// out is added back, in double, by pulpo_bn_bwd_finalize:  sum dbn * xhat = rstd * (sum dbn * (y - m32) - (mean - m32) * sum dbn).
+// (bn_lrelu_bwd_reduce_kernel, heads_bwd_kernel<.., BN> and the *_bnred data-gradient epilogues write partial rows the suite holds to the same bits)
+__device__ __forceinline__ void bn_bwd_reduce_step(float dz, float y, float scale, float shift, float m32, float slope, float& s0, float& s1) {
+    const float bn = y * scale + shift;
+    const float d = bn > 0.f ? dz : dz * slope;
+    s0 += d;
+    s1 = fmaf(d, y - m32, s1);
 }
 
 // The six per-channel constants of the second BatchNorm-backward pass, kst = [6][C] in LDS: scale, shift, m32, B, C hi, C lo with

@@ -22,12 +22,21 @@ __device__ __forceinline__ float group_sum(float v) {
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
 // NOUT = 3: plain head.  NOUT = 6: rows 0-2 mu, rows 3-5 sigma pre-activation.
-template <int NOUT, bool VEC, typename TH = float>
-__global__ __launch_bounds__(256) void heads_fwd_kernel(const TH* __restrict__ h, long ps, const float* __restrict__ Wt,
-                                                          const float* __restrict__ bias, const float* __restrict__ eps, float* __restrict__ o0,
-                                                          float* __restrict__ o1, float* __restrict__ o2, int B, long V, int C) {
-    extern __shared__ float wl[];              // [NOUT][C]
+// BN: the head on the PRE-NORM tensor of the ConvUnit in front of it (PULPoEncoder.sample_merge_block -> mu_sigma, VelocityField's last unit -> its
+// 1x1x1 convolution).  That unit's output z = lrelu(scale * y + shift) has no reader but the head, and the gradient dz the head sends back none but
+// the unit's BatchNorm backward: both are formed where they are used (z: three operations per element in kernels that wait for memory; dz: 3 - 6
+// products per element from planar values the kernels hold anyway), so the chain reads y three times and writes dy once instead of ten passes.
+// h is then y (fp32), coef the unit's coefficient block (pulpo_bn_fwd_finalize), and the load applies pulpo::bn_lrelu from scale / shift in LDS.
+template <int NOUT, bool VEC, bool BN, typename TH = float>
+__global__ __launch_bounds__(256) void heads_fwd_kernel(const TH* __restrict__ h, long ps, const float* __restrict__ coef, float slope,
+                                                          const float* __restrict__ Wt, const float* __restrict__ bias, const float* __restrict__ eps,
+                                                          float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2, int B, long V, int C) {
+    extern __shared__ float wl[];              // [NOUT][C] weights | (BN) [C] scale | [C] shift
+    float* scl = wl + NOUT * C;
+    float* shl = scl + C;
     for (int j = threadIdx.x; j < NOUT * C; j += blockDim.x) wl[j] = Wt[j];
+    if constexpr (BN)
+        for (int j = threadIdx.x; j < C; j += blockDim.x) { scl[j] = coef[2 * C + j]; shl[j] = coef[3 * C + j]; }
     __syncthreads();
     const int g = threadIdx.x & (G - 1);
     const long npix = (long)B * V;
@@ -40,23 +49,19 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const TH* __restrict__ h
         for (int j = 0; j < NOUT; ++j) acc[j] = 0.f;
         if (live) {
             const TH* hp = h + p * ps;
-            if constexpr (VEC) {
-                for (int c = 4 * g; c < C; c += 4 * G) {
-                    float x[4];
-                    pulpo::ldv<4>(hp + c, x);
+            constexpr int NV = VEC ? 4 : 1;
+            for (int c = NV * g; c < C; c += NV * G) {
+                float x[NV];
+                pulpo::ldv<NV>(hp + c, x);
+                if constexpr (BN) {
 #pragma unroll
-                    for (int j = 0; j < NOUT; ++j) {
-                        const float* w = wl + j * C + c;
-                        acc[j] += x[0] * w[0] + x[1] * w[1] + x[2] * w[2] + x[3] * w[3];
-                    }
+                    for (int k = 0; k < NV; ++k) x[k] = pulpo::bn_lrelu(x[k], scl[c + k], shl[c + k], slope);
                 }
-            } else {
-                for (int c = g; c < C; c += G) {
-                    float x1[1];
-                    pulpo::ldv<1>(hp + c, x1);
-                    const float x = x1[0];
 #pragma unroll
-                    for (int j = 0; j < NOUT; ++j) acc[j] += x * wl[j * C + c];
+                for (int j = 0; j < NOUT; ++j) {
+                    const float* w = wl + j * C + c;
+                    if constexpr (VEC) acc[j] += x[0] * w[0] + x[1] * w[1] + x[2] * w[2] + x[3] * w[3];
+                    else acc[j] += x[0] * w[0];
                 }
             }
         }
@@ -82,184 +87,40 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const TH* __restrict__ h
     }
 }
 
+// The five planar 3-channel operands of a pixel (upstream gradients of mu / sigma / z, the noise, sigma) are the same 15 values for every
+// thread of the pixel's row.  Loaded by each thread they were 15 of the 16 load instructions a wave issued per trip, and the kernels ran at
+// what the vector-memory unit issues (2.3 TB/s at 96 channels) instead of what HBM delivers: the row's first threads fetch them once into
+// sv16[slot][0..14] (absent operands stored as 0), the row reads them from LDS behind the trip's barrier (two buffers by trip parity: one barrier per trip).
+__device__ __forceinline__ void stage_head_operands(float (*sv16)[16], int slot, int col, int CV, const float* g0, const float* g1, const float* g2, const float* eps,
+                                                    const float* sigma, long base, long V) {
+    for (int q = col; q < 15; q += CV) {
+        const int arr = q / 3, j = q - 3 * arr;
+        const float* src = arr == 0 ? g0 : arr == 1 ? g1 : arr == 2 ? g2 : arr == 3 ? eps : sigma;
+        sv16[slot][q] = src != nullptr ? src[base + j * V] : 0.f;
+    }
+}
+
 // backward.  dpre[j] (j < NOUT) per voxel is formed from the upstream gradients:
 //   NOUT == 3 : dpre = g0
 //   NOUT == 6 : dmu = g0 + g2 ; dsigma = g1 + g2 * eps ; dpre[3+j] = dsigma * (1 - exp(-sigma))   (softplus' = sigmoid)
 // outputs: dh[pixel][C] ;  partial[blk][NOUT*C + NOUT] = per-block sums for dW and db.
 // Thread (col,row) owns VEC channels and walks the block's pixels, so dW accumulates in NOUT*VEC registers.
-template <int NOUT, int VEC, typename TH = float>
-__global__ __launch_bounds__(256) void heads_bwd_kernel(const TH* __restrict__ h, long ps, const float* __restrict__ Wt,
-                                                          const float* __restrict__ g0, const float* __restrict__ g1, const float* __restrict__ g2,
-                                                          const float* __restrict__ eps, const float* __restrict__ sigma, TH* __restrict__ dh,
-                                                          long dps, float* __restrict__ partial, int B, long V, int C) {
-    extern __shared__ float red[];             // [RB][NOUT*C + NOUT]
-    const int CV = C / VEC, RB = blockDim.x / CV;
-    const int col = threadIdx.x % CV, row = threadIdx.x / CV;
-    const int c = col * VEC;
-    const int ROWLEN = NOUT * C + NOUT;
-    const long npix = (long)B * V;
-    float dw[NOUT][VEC], db[NOUT], w[NOUT][VEC];
-#pragma unroll
-    for (int j = 0; j < NOUT; ++j) {
-        db[j] = 0.f;
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) { dw[j][k] = 0.f; w[j][k] = (row < RB) ? Wt[j * C + c + k] : 0.f; }
-    }
-    if constexpr (NOUT == 6) {
-        // The five planar 3-channel operands of a pixel (upstream gradients of mu / sigma / z, the noise, sigma) are the same 15 values for every
-        // thread of the pixel's row.  Loaded by each thread they were 15 of the 16 load instructions a wave issued per trip, and the kernel ran at
-        // what the vector-memory unit issues (2.3 TB/s at 96 channels) instead of what HBM delivers: the row's first threads now fetch them once,
-        // the row reads them from LDS (two buffers by trip parity: one barrier per trip).  Uniform trip count per block for that barrier.
-        float (*sc)[16] = reinterpret_cast<float (*)[16]>(red + (size_t)RB * ROWLEN);       // [2 * RB][16], behind the reduction rows (sized by the launcher)
-        int it = 0;
-        for (long pb = (long)blockIdx.x * RB; pb < npix; pb += (long)gridDim.x * RB, it ^= 1) {
-            const long p = pb + row;
-            const bool live = row < RB && p < npix;
-            const long pc = live ? p : 0;
-            const long b = pc / V, v = pc - b * V;
-            const long base = b * 3 * V + v;
-            if (live)
-                for (int q = col; q < 15; q += CV) {
-                    const int arr = q / 3, j = q - 3 * arr;
-                    const float* src = arr == 0 ? g0 : arr == 1 ? g1 : arr == 2 ? g2 : arr == 3 ? eps : sigma;
-                    sc[it * RB + row][q] = src != nullptr ? src[base + j * V] : 0.f;
-                }
-            float x[VEC];
-            if (live) pulpo::ldv<VEC>(h + p * ps + c, x);
-            __syncthreads();
-            if (live) {
-                const float* sv = sc[it * RB + row];
-                float dpre[6];
-                pulpo::head_dpre6(sv, dpre);                                   // dmu = g0 + g2 ; dsigma = g1 + g2 * eps (eps absent: stored as 0)
-                float o[VEC];
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) o[k] = 0.f;
-#pragma unroll
-                for (int j = 0; j < NOUT; ++j) {
-                    db[j] += dpre[j];
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) { o[k] += dpre[j] * w[j][k]; dw[j][k] = fmaf(dpre[j], x[k], dw[j][k]); }    // (fmaf spelled out: heads_bwd_bn_kernel adds the same bits)
-                }
-                pulpo::stv<VEC>(dh + p * dps + c, o);
-            }
-        }
-    } else if (row < RB) {
-        for (long p = (long)blockIdx.x * RB + row; p < npix; p += (long)gridDim.x * RB) {
-            const long b = p / V, v = p - b * V;
-            const long base = b * 3 * V + v;
-            float dpre[NOUT];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) dpre[j] = g0[base + j * V];
-            float x[VEC], o[VEC];
-            pulpo::ldv<VEC>(h + p * ps + c, x);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) o[k] = 0.f;
-#pragma unroll
-            for (int j = 0; j < NOUT; ++j) {
-                db[j] += dpre[j];
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) { o[k] += dpre[j] * w[j][k]; dw[j][k] = fmaf(dpre[j], x[k], dw[j][k]); }    // (fmaf spelled out: heads_bwd_bn_kernel adds the same bits)
-            }
-            pulpo::stv<VEC>(dh + p * dps + c, o);
-        }
-    }
-    if (row < RB) {
-#pragma unroll
-        for (int j = 0; j < NOUT; ++j) {
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) red[row * ROWLEN + j * C + c + k] = dw[j][k];
-            if (col == 0) red[row * ROWLEN + NOUT * C + j] = db[j];
-        }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < ROWLEN; j += blockDim.x) {
-        float t = 0.f;
-        for (int r = 0; r < RB; ++r) t += red[r * ROWLEN + j];
-        partial[(long)blockIdx.x * ROWLEN + j] = t;
-    }
-}
-
-// ---- the head on the PRE-NORM tensor of the ConvUnit in front of it (PULPoEncoder.sample_merge_block -> mu_sigma, VelocityField's last unit -> its
-// 1x1x1 convolution).  That unit's output z = lrelu(scale * y + shift) has no reader but the head, and the gradient dz the head sends back none but
-// the unit's BatchNorm backward: both are formed where they are used (z: three operations per element in kernels that wait for memory; dz: 3 - 6
-// products per element from planar values the kernels hold anyway), so the chain reads y three times and writes dy once instead of ten passes.
-// fp32 activations.  coef: the unit's coefficient block (pulpo_bn_fwd_finalize).
-template <int NOUT, bool VEC>
-__global__ __launch_bounds__(256) void heads_fwd_bn_kernel(const float* __restrict__ y, long ps, const float* __restrict__ coef, float slope,
-                                                             const float* __restrict__ Wt, const float* __restrict__ bias, const float* __restrict__ eps,
-                                                             float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2, int B, long V, int C) {
-    extern __shared__ float wl[];              // [NOUT][C] weights | [C] scale | [C] shift
-    float* scl = wl + NOUT * C;
-    float* shl = scl + C;
-    for (int j = threadIdx.x; j < NOUT * C; j += blockDim.x) wl[j] = Wt[j];
-    for (int j = threadIdx.x; j < C; j += blockDim.x) { scl[j] = coef[2 * C + j]; shl[j] = coef[3 * C + j]; }
-    __syncthreads();
-    const int g = threadIdx.x & (G - 1);
-    const long npix = (long)B * V;
-    const long pstep = (long)gridDim.x * (blockDim.x / G);
-    for (long p0 = (long)blockIdx.x * (blockDim.x / G); p0 < npix; p0 += pstep) {   // uniform trip count per block
-        const long p = p0 + threadIdx.x / G;
-        const bool live = p < npix;
-        float acc[NOUT];
-#pragma unroll
-        for (int j = 0; j < NOUT; ++j) acc[j] = 0.f;
-        if (live) {
-            const float* hp = y + p * ps;
-            if constexpr (VEC) {
-                for (int c = 4 * g; c < C; c += 4 * G) {
-                    float x[4];
-                    pulpo::ldv<4>(hp + c, x);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) x[k] = pulpo::bn_lrelu(x[k], scl[c + k], shl[c + k], slope);
-#pragma unroll
-                    for (int j = 0; j < NOUT; ++j) {
-                        const float* w = wl + j * C + c;
-                        acc[j] += x[0] * w[0] + x[1] * w[1] + x[2] * w[2] + x[3] * w[3];
-                    }
-                }
-            } else {
-                for (int c = g; c < C; c += G) {
-                    const float x = pulpo::bn_lrelu(hp[c], scl[c], shl[c], slope);
-#pragma unroll
-                    for (int j = 0; j < NOUT; ++j) acc[j] += x * wl[j * C + c];
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NOUT; ++j) acc[j] = group_sum(acc[j]);
-        if (live && g < 3) {                   // (as heads_fwd_kernel: lane g < 3 finishes output component g)
-            const long b = p / V, v = p - b * V;
-            const long at = b * 3 * V + v + g * V;
-            const float a_lo = g == 0 ? acc[0] : g == 1 ? acc[1] : acc[2];
-            if constexpr (NOUT == 3) {
-                o0[at] = a_lo + bias[g];
-            } else {
-                const float a_hi = g == 0 ? acc[3] : g == 1 ? acc[4] : acc[5];
-                const float mu = a_lo + bias[g];
-                const float sg = softplus_f(a_hi + bias[3 + g]);
-                o0[at] = mu;
-                o1[at] = sg;
-                o2[at] = eps != nullptr ? mu + sg * eps[at] : mu;
-            }
-        }
-    }
-}
-
-// backward of the head AND the first pass of the unit's BatchNorm / LeakyReLU backward (heads_bwd_kernel + bn_lrelu_bwd_reduce_kernel): a thread
-// owns VEC channels and walks the block's pixels as in heads_bwd_kernel; it reads y, forms z for dW and dz = sum_j dpre[j] * W[j][c] for
+// BN: the backward of the head AND the first pass of the unit's BatchNorm / LeakyReLU backward (bn_lrelu_bwd_reduce_kernel): h is the pre-norm
+// tensor y; the thread forms z for dW and dz = sum_j dpre[j] * W[j][c] for
 //   dbn = dz * lrelu'(scale * y + shift);   bnpart[blk][0][c] = sum dbn,  bnpart[blk][1][c] = sum dbn * (y - m32)
-// (the reduce kernel's arithmetic, m32 = the fp32-rounded batch mean; rows as pulpo_bn_bwd_finalize reads them) and stores neither.
-// partial[blk][NOUT*C + NOUT] as heads_bwd_kernel writes it.  Fixed block partition, fixed summation order: the same bits on every run.
-template <int NOUT, int VEC>
-__global__ __launch_bounds__(256) void heads_bwd_bn_kernel(const float* __restrict__ y, long ps, const float* __restrict__ coef, float slope,
-                                                             const float* __restrict__ Wt, const float* __restrict__ g0, const float* __restrict__ g1,
-                                                             const float* __restrict__ g2, const float* __restrict__ eps, const float* __restrict__ sigma,
-                                                             float* __restrict__ partial, float* __restrict__ bnpart, int B, long V, int C) {
-    extern __shared__ float red[];             // [RB][NOUT*C + NOUT + 2*C]
+// (pulpo::bn_bwd_reduce_step; rows as pulpo_bn_bwd_finalize reads them) and stores no dh.  Fixed block partition, fixed summation order: the
+// same bits on every run.  The row count is blockDim.x / CV (the BN launcher may start fewer than 256 threads).
+template <int NOUT, int VEC, bool BN, typename TH = float>
+__global__ __launch_bounds__(256) void heads_bwd_kernel(const TH* __restrict__ h, long ps, const float* __restrict__ coef, float slope,
+                                                          const float* __restrict__ Wt, const float* __restrict__ g0, const float* __restrict__ g1,
+                                                          const float* __restrict__ g2, const float* __restrict__ eps, const float* __restrict__ sigma,
+                                                          TH* __restrict__ dh, long dps, float* __restrict__ partial, float* __restrict__ bnpart, int B, long V,
+                                                          int C) {
+    extern __shared__ float red[];             // [RB][NOUT*C + NOUT (+ 2*C)] | (NOUT 6) [2 * RB][16] planar operands (sized by the launcher)
     const int CV = C / VEC, RB = blockDim.x / CV;
     const int col = threadIdx.x % CV, row = threadIdx.x / CV;
     const int c = col * VEC;
-    const int ROWLEN = NOUT * C + NOUT, ROWLEN2 = ROWLEN + 2 * C;
+    const int ROWLEN = NOUT * C + NOUT, ROWLEN2 = ROWLEN + (BN ? 2 * C : 0);
     const long npix = (long)B * V;
     const bool mine = row < RB;
     float dw[NOUT][VEC], db[NOUT], w[NOUT][VEC], sc[VEC], sh[VEC], m32[VEC], s0[VEC], s1[VEC];
@@ -269,55 +130,55 @@ __global__ __launch_bounds__(256) void heads_bwd_bn_kernel(const float* __restri
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { dw[j][k] = 0.f; w[j][k] = mine ? Wt[j * C + c + k] : 0.f; }
     }
+    if constexpr (BN) {
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        s0[k] = s1[k] = 0.f;
-        sc[k] = mine ? coef[2 * C + c + k] : 0.f;
-        sh[k] = mine ? coef[3 * C + c + k] : 0.f;
-        m32[k] = mine ? coef[c + k] : 0.f;
+        for (int k = 0; k < VEC; ++k) {
+            s0[k] = s1[k] = 0.f;
+            sc[k] = mine ? coef[2 * C + c + k] : 0.f;
+            sh[k] = mine ? coef[3 * C + c + k] : 0.f;
+            m32[k] = mine ? coef[c + k] : 0.f;
+        }
     }
-    // one pixel: v = y, dpre = the head's pre-activation gradients
-    auto pixel = [&](const float (&v)[VEC], const float (&dpre)[NOUT]) {
+    // one pixel: v = h (BN: y), dpre = the head's pre-activation gradients
+    auto pixel = [&](long p, const float (&v)[VEC], const float (&dpre)[NOUT]) {
         float x[VEC], o[VEC];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) { x[k] = pulpo::bn_lrelu(v[k], sc[k], sh[k], slope); o[k] = 0.f; }
+        for (int k = 0; k < VEC; ++k) { x[k] = BN ? pulpo::bn_lrelu(v[k], sc[k], sh[k], slope) : v[k]; o[k] = 0.f; }
 #pragma unroll
         for (int j = 0; j < NOUT; ++j) {
             db[j] += dpre[j];
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) { o[k] = fmaf(dpre[j], w[j][k], o[k]); dw[j][k] = fmaf(dpre[j], x[k], dw[j][k]); }
+            for (int k = 0; k < VEC; ++k) {
+                // (BN: dz spelled fmaf - bn_lrelu_bwd_apply_heads_kernel forms the same bits again; the stored dh keeps the expression it always had,
+                //  which the compiler does not contract everywhere)
+                if constexpr (BN) o[k] = fmaf(dpre[j], w[j][k], o[k]);
+                else o[k] += dpre[j] * w[j][k];
+                dw[j][k] = fmaf(dpre[j], x[k], dw[j][k]);
+            }
         }
+        if constexpr (BN) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            const float bn = v[k] * sc[k] + sh[k];
-            const float d = bn > 0.f ? o[k] : o[k] * slope;
-            s0[k] += d;
-            s1[k] = fmaf(d, v[k] - m32[k], s1[k]);
+            for (int k = 0; k < VEC; ++k) pulpo::bn_bwd_reduce_step(o[k], v[k], sc[k], sh[k], m32[k], slope, s0[k], s1[k]);
+        } else {
+            pulpo::stv<VEC>(dh + p * dps + c, o);
         }
     };
     if constexpr (NOUT == 6) {
-        // (the 15 planar values of a pixel: fetched once per row and shared through LDS, two buffers by trip parity - see heads_bwd_kernel)
-        float (*sv16)[16] = reinterpret_cast<float (*)[16]>(red + (size_t)RB * ROWLEN2);       // [2 * RB][16]
+        float (*sv16)[16] = reinterpret_cast<float (*)[16]>(red + (size_t)RB * ROWLEN2);       // [2 * RB][16], behind the reduction rows
         int it = 0;
-        for (long pb = (long)blockIdx.x * RB; pb < npix; pb += (long)gridDim.x * RB, it ^= 1) {
+        for (long pb = (long)blockIdx.x * RB; pb < npix; pb += (long)gridDim.x * RB, it ^= 1) {     // uniform trip count per block for the barrier
             const long p = pb + row;
             const bool live = mine && p < npix;
             const long pc = live ? p : 0;
             const long b = pc / V, v_ = pc - b * V;
-            const long base = b * 3 * V + v_;
-            if (live)
-                for (int q = col; q < 15; q += CV) {
-                    const int arr = q / 3, j = q - 3 * arr;
-                    const float* src = arr == 0 ? g0 : arr == 1 ? g1 : arr == 2 ? g2 : arr == 3 ? eps : sigma;
-                    sv16[it * RB + row][q] = src != nullptr ? src[base + j * V] : 0.f;
-                }
+            if (live) stage_head_operands(sv16, it * RB + row, col, CV, g0, g1, g2, eps, sigma, b * 3 * V + v_, V);
             float v[VEC];
-            if (live) pulpo::ldv<VEC>(y + p * ps + c, v);
+            if (live) pulpo::ldv<VEC>(h + p * ps + c, v);
             __syncthreads();
             if (live) {
                 float dpre[6];
-                pulpo::head_dpre6(sv16[it * RB + row], dpre);
-                pixel(v, dpre);
+                pulpo::head_dpre6(sv16[it * RB + row], dpre);                  // dmu = g0 + g2 ; dsigma = g1 + g2 * eps (eps absent: stored as 0)
+                pixel(p, v, dpre);
             }
         }
     } else if (mine) {
@@ -327,8 +188,8 @@ __global__ __launch_bounds__(256) void heads_bwd_bn_kernel(const float* __restri
             float dpre[NOUT], v[VEC];
 #pragma unroll
             for (int j = 0; j < 3; ++j) dpre[j] = g0[base + j * V];
-            pulpo::ldv<VEC>(y + p * ps + c, v);
-            pixel(v, dpre);
+            pulpo::ldv<VEC>(h + p * ps + c, v);
+            pixel(p, v, dpre);
         }
     }
     if (mine) {
@@ -339,14 +200,16 @@ __global__ __launch_bounds__(256) void heads_bwd_bn_kernel(const float* __restri
             for (int k = 0; k < VEC; ++k) r[j * C + c + k] = dw[j][k];
             if (col == 0) r[NOUT * C + j] = db[j];
         }
+        if constexpr (BN) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) { r[ROWLEN + c + k] = s0[k]; r[ROWLEN + C + c + k] = s1[k]; }
+            for (int k = 0; k < VEC; ++k) { r[ROWLEN + c + k] = s0[k]; r[ROWLEN + C + c + k] = s1[k]; }
+        }
     }
     __syncthreads();
     for (int j = threadIdx.x; j < ROWLEN2; j += blockDim.x) {
         float t = 0.f;
         for (int r = 0; r < RB; ++r) t += red[(size_t)r * ROWLEN2 + j];
-        if (j < ROWLEN) partial[(long)blockIdx.x * ROWLEN + j] = t;
+        if (!BN || j < ROWLEN) partial[(long)blockIdx.x * ROWLEN + j] = t;
         else bnpart[(long)blockIdx.x * 2 * C + (j - ROWLEN)] = t;
     }
 }
@@ -385,7 +248,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_bwd_apply_heads_kernel(const flo
         const long base = b * 3 * V + v_;
         float dpre[NOUT], v[VEC], g[VEC], o[VEC];
         if constexpr (NOUT == 6) {
-            if (live)
+            if (live)                               // (own text of stage_head_operands: the call costs this kernel 4 SGPRs and 0.0025 ms of 0.024 per launch, profiles/epilogue_share_ab.txt)
                 for (int q = col; q < 15; q += CV) {
                     const int arr = q / 3, j = q - 3 * arr;
                     const float* src = arr == 0 ? g0 : arr == 1 ? g1 : arr == 2 ? g2 : arr == 3 ? eps : sigma;
@@ -405,7 +268,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_bwd_apply_heads_kernel(const flo
 #pragma unroll
         for (int k = 0; k < VEC; ++k) g[k] = 0.f;
 #pragma unroll
-        for (int j = 0; j < NOUT; ++j) {            // dz, the expression of heads_bwd_bn_kernel
+        for (int j = 0; j < NOUT; ++j) {            // dz, the expression of heads_bwd_kernel
             float wj[VEC];
             pulpo::ldv<VEC>(wl + j * C + cl, wj);
 #pragma unroll
@@ -473,11 +336,11 @@ PULPO_API int pulpo_heads_fwd_t(const void* h, int h_dt, int64_t ps, const float
     PULPO_DISPATCH_DT(h_dt, TH, {
         const TH* hp = (const TH*)h;
         if (nout == 3) {
-            if (vec) hipLaunchKernelGGL((heads_fwd_kernel<3, true, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, Wt, bias, eps, o0, o1, o2, B, V, C);
-            else hipLaunchKernelGGL((heads_fwd_kernel<3, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, Wt, bias, eps, o0, o1, o2, B, V, C);
+            if (vec) hipLaunchKernelGGL((heads_fwd_kernel<3, true, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, nullptr, 0.f, Wt, bias, eps, o0, o1, o2, B, V, C);
+            else hipLaunchKernelGGL((heads_fwd_kernel<3, false, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, nullptr, 0.f, Wt, bias, eps, o0, o1, o2, B, V, C);
         } else {
-            if (vec) hipLaunchKernelGGL((heads_fwd_kernel<6, true, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, Wt, bias, eps, o0, o1, o2, B, V, C);
-            else hipLaunchKernelGGL((heads_fwd_kernel<6, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, Wt, bias, eps, o0, o1, o2, B, V, C);
+            if (vec) hipLaunchKernelGGL((heads_fwd_kernel<6, true, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, nullptr, 0.f, Wt, bias, eps, o0, o1, o2, B, V, C);
+            else hipLaunchKernelGGL((heads_fwd_kernel<6, false, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, nullptr, 0.f, Wt, bias, eps, o0, o1, o2, B, V, C);
         }
     });
     return pulpo::check_launch("heads_fwd");
@@ -515,11 +378,11 @@ PULPO_API int pulpo_heads_bwd_t(const void* h, int h_dt, int64_t ps, const float
         const TH* hp = (const TH*)h;
         TH* dhp = (TH*)dh;
         if (nout == 3) {
-            if (v4) hipLaunchKernelGGL((heads_bwd_kernel<3, 4, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, Wt, g0, g1, g2, eps, sigma, dhp, dps, partial, B, V, C);
-            else hipLaunchKernelGGL((heads_bwd_kernel<3, 1, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, Wt, g0, g1, g2, eps, sigma, dhp, dps, partial, B, V, C);
+            if (v4) hipLaunchKernelGGL((heads_bwd_kernel<3, 4, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, nullptr, 0.f, Wt, g0, g1, g2, eps, sigma, dhp, dps, partial, nullptr, B, V, C);
+            else hipLaunchKernelGGL((heads_bwd_kernel<3, 1, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, nullptr, 0.f, Wt, g0, g1, g2, eps, sigma, dhp, dps, partial, nullptr, B, V, C);
         } else {
-            if (v4) hipLaunchKernelGGL((heads_bwd_kernel<6, 4, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, Wt, g0, g1, g2, eps, sigma, dhp, dps, partial, B, V, C);
-            else hipLaunchKernelGGL((heads_bwd_kernel<6, 1, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, Wt, g0, g1, g2, eps, sigma, dhp, dps, partial, B, V, C);
+            if (v4) hipLaunchKernelGGL((heads_bwd_kernel<6, 4, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, nullptr, 0.f, Wt, g0, g1, g2, eps, sigma, dhp, dps, partial, nullptr, B, V, C);
+            else hipLaunchKernelGGL((heads_bwd_kernel<6, 1, false, TH>), dim3(nblk), dim3(256), lds, st, hp, ps, nullptr, 0.f, Wt, g0, g1, g2, eps, sigma, dhp, dps, partial, nullptr, B, V, C);
         }
     });
     return pulpo::check_launch("heads_bwd");
@@ -542,11 +405,11 @@ PULPO_API int pulpo_heads_fwd_bn_t(const float* y, int64_t ps, const float* coef
     const size_t lds = (size_t)(nout + 2) * C * sizeof(float);
     PULPO_REQUIRE(lds <= 64 * 1024, "heads_fwd_bn: LDS budget exceeded");
     if (nout == 3) {
-        if (vec) hipLaunchKernelGGL((heads_fwd_bn_kernel<3, true>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
-        else hipLaunchKernelGGL((heads_fwd_bn_kernel<3, false>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
+        if (vec) hipLaunchKernelGGL((heads_fwd_kernel<3, true, true>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
+        else hipLaunchKernelGGL((heads_fwd_kernel<3, false, true>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
     } else {
-        if (vec) hipLaunchKernelGGL((heads_fwd_bn_kernel<6, true>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
-        else hipLaunchKernelGGL((heads_fwd_bn_kernel<6, false>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
+        if (vec) hipLaunchKernelGGL((heads_fwd_kernel<6, true, true>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
+        else hipLaunchKernelGGL((heads_fwd_kernel<6, false, true>), dim3(nblk), dim3(256), lds, st, y, ps, coef, slope, Wt, bias, eps, o0, o1, o2, B, V, C);
     }
     return pulpo::check_launch("heads_fwd_bn");
 }
@@ -572,11 +435,11 @@ PULPO_API int pulpo_heads_bwd_bn_t(const float* y, int64_t ps, const float* coef
     PULPO_REQUIRE(lds <= 64 * 1024, "heads_bwd_bn: LDS budget exceeded");
     const int nthr = RB == std::max(1, 256 / CV) ? 256 : RB * CV;          // (the kernel's row count is blockDim.x / CV)
     if (nout == 3) {
-        if (v4) hipLaunchKernelGGL((heads_bwd_bn_kernel<3, 4>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, partial, bnpart, B, V, C);
-        else hipLaunchKernelGGL((heads_bwd_bn_kernel<3, 1>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, partial, bnpart, B, V, C);
+        if (v4) hipLaunchKernelGGL((heads_bwd_kernel<3, 4, true>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, (float*)nullptr, 0L, partial, bnpart, B, V, C);
+        else hipLaunchKernelGGL((heads_bwd_kernel<3, 1, true>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, (float*)nullptr, 0L, partial, bnpart, B, V, C);
     } else {
-        if (v4) hipLaunchKernelGGL((heads_bwd_bn_kernel<6, 4>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, partial, bnpart, B, V, C);
-        else hipLaunchKernelGGL((heads_bwd_bn_kernel<6, 1>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, partial, bnpart, B, V, C);
+        if (v4) hipLaunchKernelGGL((heads_bwd_kernel<6, 4, true>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, (float*)nullptr, 0L, partial, bnpart, B, V, C);
+        else hipLaunchKernelGGL((heads_bwd_kernel<6, 1, true>), dim3(nblk), dim3(nthr), lds, st, y, ps, coef, slope, Wt, g0, g1, g2, eps, sigma, (float*)nullptr, 0L, partial, bnpart, B, V, C);
     }
     return pulpo::check_launch("heads_bwd_bn");
 }

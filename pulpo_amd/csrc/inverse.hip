@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void vecint_pair_step_kernel(const float* __re
     }
 }
 
-inline int eblocks(long items, int cap) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, cap)); }
+using pulpo::eblocks;
 
 inline bool pair_lds(int D, int H, int W, int nsteps) { return nsteps > 0 && (long)D * H * W <= PAIR_LDS_MAXV; }
 

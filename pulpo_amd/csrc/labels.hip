@@ -19,7 +19,7 @@ using pulpo::sample_coord;
 constexpr int kMaxClasses = 256;
 constexpr double kFix = 4294967296.0;        // 2^32: fixed-point unit of the Dice weight sums
 
-inline int eblocks(long items, int cap) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, cap)); }
+using pulpo::eblocks;
 
 __device__ __forceinline__ unsigned long long to_fix(float p) { return (unsigned long long)__float2ull_rn(p * 4294967296.f); }
 

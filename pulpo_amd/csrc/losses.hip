@@ -9,17 +9,8 @@
 
 namespace {
 
-inline int eblocks(long items, int cap = 4096) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, cap)); }
-
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-    v = pulpo::wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x == 0) t = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return t;   // valid in thread 0
-}
+using pulpo::block_sum_256;
+using pulpo::eblocks;
 
 // the squared local correlation coefficient of a voxel from its five window sums s = box of (I, J, I*I, J*J, I*J): losses.py:125-132, same
 // expression order
@@ -491,13 +482,13 @@ static int ncc_forward(const float* I, const float* J, const float* wa, const fl
     const float nwin = ncc_window_count(win, D);
     float* T1 = T;
     float* T2 = T + 5 * N;
-    hipLaunchKernelGGL(box_x_kernel<0>, dim3(eblocks(nrows * segs * 64)), dim3(256), 0, st, I, J, T1, N, nrows, W, pad, 5, segs);
+    hipLaunchKernelGGL(box_x_kernel<0>, dim3(eblocks(nrows * segs * 64, 4096)), dim3(256), 0, st, I, J, T1, N, nrows, W, pad, 5, segs);
     int rc = pulpo::check_launch("ncc box_x");
     if (rc) return rc;
     const bool march = pad >= 1 && pad <= 5;            // windows 3 .. 11 (the model's: 9, 7, 5, 3 from the finest level down)
     if (march && H > 1) rc = launch_march<5, 0>(pad, eblocks(N, 1024), st, T1, T2, N, H, (long)W);
     else {
-        hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N)), dim3(256), 0, st, T1, T2, N, 5, H, (long)W, pad);
+        hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N, 4096)), dim3(256), 0, st, T1, T2, N, 5, H, (long)W, pad);
         rc = pulpo::check_launch("ncc box_y");
     }
     if (rc) return rc;
@@ -518,22 +509,22 @@ static int ncc_backward(const float* I, const float* J, const float* S, const fl
     const long nrows = (long)B * D * H;
     float* T1 = T;
     float* T2 = T + 3 * N;
-    if (wa) hipLaunchKernelGGL(ncc_abc_kernel<true>, dim3(eblocks(N)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D), wa, wb);
-    else hipLaunchKernelGGL(ncc_abc_kernel<false>, dim3(eblocks(N)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D), wa, wb);
+    if (wa) hipLaunchKernelGGL(ncc_abc_kernel<true>, dim3(eblocks(N, 4096)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D), wa, wb);
+    else hipLaunchKernelGGL(ncc_abc_kernel<false>, dim3(eblocks(N, 4096)), dim3(256), 0, st, S, T1, N, ncc_window_count(win, D), wa, wb);
     int rc = pulpo::check_launch("ncc abc");
     if (rc) return rc;
-    hipLaunchKernelGGL(box_x_kernel<1>, dim3(eblocks(nrows * segs * 64)), dim3(256), 0, st, T1, nullptr, T2, N, nrows, W, pad, 3, segs);
+    hipLaunchKernelGGL(box_x_kernel<1>, dim3(eblocks(nrows * segs * 64, 4096)), dim3(256), 0, st, T1, nullptr, T2, N, nrows, W, pad, 3, segs);
     rc = pulpo::check_launch("ncc bwd box_x");
     if (rc) return rc;
     const bool march = pad >= 1 && pad <= 5;
     if (march && H > 1) rc = launch_march<3, 0>(pad, eblocks(N, 1024), st, T2, T1, N, H, (long)W);
     else {
-        hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N)), dim3(256), 0, st, T2, T1, N, 3, H, (long)W, pad);
+        hipLaunchKernelGGL(box_axis_kernel, dim3(eblocks(N, 4096)), dim3(256), 0, st, T2, T1, N, 3, H, (long)W, pad);
         rc = pulpo::check_launch("ncc bwd box_y");
     }
     if (rc) return rc;
     if (march) return launch_march<3, 2>(pad, eblocks(N, 1024), st, T1, gJ, N, D, (long)H * W, 0.f, nullptr, I, J, gscale, coef);
-    hipLaunchKernelGGL(ncc_bwd_final_kernel, dim3(eblocks(N)), dim3(256), 0, st, T1, I, J, gscale, coef, gJ, N, D, (long)H * W, pad);
+    hipLaunchKernelGGL(ncc_bwd_final_kernel, dim3(eblocks(N, 4096)), dim3(256), 0, st, T1, I, J, gscale, coef, gJ, N, D, (long)H * W, pad);
     return pulpo::check_launch("ncc bwd final");
 }
 
@@ -582,7 +573,7 @@ PULPO_API int pulpo_kl_fwd(const float* mu, const float* sigma, const float* mu1
 PULPO_API int pulpo_kl_bwd(const float* mu, const float* sigma, const float* mu1, const float* sigma1, const float* gscale, float coef, float* gmu,
                            float* gsigma, int64_t n, void* stream) {
     PULPO_REQUIRE(mu && sigma && gmu && gsigma && n > 0, "kl_bwd: bad arguments");
-    hipLaunchKernelGGL(kl_bwd_kernel, dim3(eblocks(n)), dim3(256), 0, (hipStream_t)stream, mu, sigma, mu1, sigma1, gscale, coef, gmu, gsigma, (long)n);
+    hipLaunchKernelGGL(kl_bwd_kernel, dim3(eblocks(n, 4096)), dim3(256), 0, (hipStream_t)stream, mu, sigma, mu1, sigma1, gscale, coef, gmu, gsigma, (long)n);
     return pulpo::check_launch("kl_bwd");
 }
 
@@ -600,9 +591,9 @@ PULPO_API int pulpo_l2reg_fwd(const float* df, int64_t nplanes, int D, int H, in
 PULPO_API int pulpo_l2reg_bwd(const float* df, const float* gscale, float coef, float* gdf, int64_t nplanes, int D, int H, int W, void* stream) {
     PULPO_REQUIRE(df && gdf && nplanes > 0 && D >= 1 && H > 1 && W > 1, "l2reg_bwd: bad arguments");
     if (W % 4 == 0 && ((((uintptr_t)df) | ((uintptr_t)gdf)) & 15) == 0)
-        hipLaunchKernelGGL(l2reg_bwd_vec_kernel, dim3(eblocks(nplanes * D * H * (W / 4))), dim3(256), 0, (hipStream_t)stream, df, gscale, coef, gdf, (long)nplanes, D, H, W);
+        hipLaunchKernelGGL(l2reg_bwd_vec_kernel, dim3(eblocks(nplanes * D * H * (W / 4), 4096)), dim3(256), 0, (hipStream_t)stream, df, gscale, coef, gdf, (long)nplanes, D, H, W);
     else
-        hipLaunchKernelGGL(l2reg_bwd_kernel, dim3(eblocks(nplanes * D * H * W)), dim3(256), 0, (hipStream_t)stream, df, gscale, coef, gdf, (long)nplanes, D, H, W);
+        hipLaunchKernelGGL(l2reg_bwd_kernel, dim3(eblocks(nplanes * D * H * W, 4096)), dim3(256), 0, (hipStream_t)stream, df, gscale, coef, gdf, (long)nplanes, D, H, W);
     return pulpo::check_launch("l2reg_bwd");
 }
 

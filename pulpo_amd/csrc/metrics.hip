@@ -5,17 +5,8 @@
 
 namespace {
 
-inline int eblocks(long items, int cap = 4096) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, cap)); }
-
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-    v = pulpo::wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x == 0) t = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return t;
-}
+using pulpo::block_sum_256;
+using pulpo::eblocks;
 
 // ------------------------------------------------------------------------------------------------ L2_loss
 __global__ __launch_bounds__(256) void sqdiff_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, long n, float* __restrict__ partial) {
@@ -388,7 +379,7 @@ PULPO_API int pulpo_sqdiff_fwd(const float* a, const float* b, int64_t n, float*
 }
 PULPO_API int pulpo_sqdiff_bwd(const float* a, const float* b, const float* gscale, float coef, float* ga, int64_t n, void* stream) {
     PULPO_REQUIRE(a && b && ga && n > 0, "sqdiff_bwd: bad arguments");
-    hipLaunchKernelGGL(sqdiff_bwd_kernel, dim3(eblocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, gscale, coef, ga, (long)n);
+    hipLaunchKernelGGL(sqdiff_bwd_kernel, dim3(eblocks(n, 4096)), dim3(256), 0, (hipStream_t)stream, a, b, gscale, coef, ga, (long)n);
     return pulpo::check_launch("sqdiff_bwd");
 }
 // masked L2_loss: a, b planar (B,C,V), wa / wb (nullable) (B,1,V).  partial: 2 * pulpo_metric_blocks(B*C*V) floats (sum of m d^2, sum of m);
@@ -405,7 +396,7 @@ PULPO_API int pulpo_sqdiff_masked_bwd(const float* a, const float* b, const floa
                                       int C, int64_t V, void* stream) {
     PULPO_REQUIRE(a && b && wa && ga && B > 0 && C > 0 && V > 0, "sqdiff_masked_bwd: bad arguments");
     const long n = (long)B * C * V;
-    hipLaunchKernelGGL(sqdiff_masked_bwd_kernel, dim3(eblocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, wa, wb, gscale, coef, ga, C, (long)V, n);
+    hipLaunchKernelGGL(sqdiff_masked_bwd_kernel, dim3(eblocks(n, 4096)), dim3(256), 0, (hipStream_t)stream, a, b, wa, wb, gscale, coef, ga, C, (long)V, n);
     return pulpo::check_launch("sqdiff_masked_bwd");
 }
 
@@ -451,7 +442,7 @@ PULPO_API int pulpo_jdetstd_bwd(const float* df, const float* jdet, const double
     const long n = (long)B * D * H * W;
     hipError_t e = hipMemsetAsync(gdf, 0, sizeof(float) * (D == 1 ? 2 : 3) * n, st);        // D == 1: two-channel 2-D field
     if (e != hipSuccess) return pulpo::fail((int)e, "jdetstd_bwd memset: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(jdetstd_bwd_kernel, dim3(eblocks(n)), dim3(256), 0, st, df, make_geom(B, D, H, W, normalize), jdet, stat, gscale, lamb, (double)n, gdf);
+    hipLaunchKernelGGL(jdetstd_bwd_kernel, dim3(eblocks(n, 4096)), dim3(256), 0, st, df, make_geom(B, D, H, W, normalize), jdet, stat, gscale, lamb, (double)n, gdf);
     return pulpo::check_launch("jdetstd_bwd");
 }
 
@@ -675,7 +666,7 @@ PULPO_API int pulpo_kl_nondiag_fwd(const float* mu, const float* sigma, int64_t 
 PULPO_API int pulpo_kl_nondiag_bwd(const float* mu, const float* sigma, const float* gscale, int64_t nplanes, int D, int H, int W, float prior_lambda,
                                    float* gmu, float* gsigma, void* stream) {
     PULPO_REQUIRE(mu && sigma && gmu && gsigma && nplanes > 0 && D >= 1 && H > 1 && W > 1, "kl_nondiag_bwd: bad arguments");
-    hipLaunchKernelGGL(kln_bwd_kernel, dim3(eblocks(nplanes * D * H * W)), dim3(256), 0, (hipStream_t)stream, mu, sigma, gscale, (long)nplanes, D, H, W,
+    hipLaunchKernelGGL(kln_bwd_kernel, dim3(eblocks(nplanes * D * H * W, 4096)), dim3(256), 0, (hipStream_t)stream, mu, sigma, gscale, (long)nplanes, D, H, W,
                        prior_lambda, gmu, gsigma);
     return pulpo::check_launch("kl_nondiag_bwd");
 }

@@ -44,15 +44,7 @@ static bool pick_tiling(int B, int D, int H, int W, int d, int nimg, Tiling& t) 
     return true;
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-    v = pulpo::wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x == 0) t = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return t;   // valid in thread 0
-}
+using pulpo::block_sum_256;
 
 // MODE 0: out[k N + e] = f_k of img0                                            (one image staged)
 // MODE 1: partial[block] = sum of cost; with masks partial[2 block] = sum of m cost, partial[2 block + 1] = sum of m

@@ -191,8 +191,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_apply_pool2_kernel(const TY* __r
                     pulpo::ldv<4>(y + vox * yps + c, v);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const float t = v[k] * sc[k] + sh[k];
-                        v[k] = pulpo::as_stored<TZ>(t > 0.f ? t : t * slope);        // (the pooled tensor averages z as stored)
+                        v[k] = pulpo::as_stored<TZ>(pulpo::bn_lrelu(v[k], sc[k], sh[k], slope));        // (the pooled tensor averages z as stored)
                         acc[k] += v[k];
                     }
                     if (z != nullptr) pulpo::stv<4>(z + vox * zps + c, v);       // (null: only the pooled tensor has a reader - DownPath levels above the first latent level)
@@ -205,9 +204,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_apply_pool2_kernel(const TY* __r
 }
 
 // pass 1 of the backward: partial[blk][0][c] = sum dbn, partial[blk][1][c] = sum dbn * (y - m32)
-//   dbn = dz * (bn_out > 0 ? 1 : slope),  bn_out = y*scale + shift,  m32 = the batch mean rounded to fp32 (coef[c])
-// All fp32: the difference of two floats carries a relative error of 2^-24 however close they are, and what the ROUNDED mean leaves out is
-// added back in double by bn_bwd_finalize_kernel (sum dbn * xhat = rstd * (sum dbn * (y - m32) - (mean - m32) * sum dbn)).  No doubles per
+// per element pulpo::bn_bwd_reduce_step (head_bn.h: why the sums are fp32 and what bn_bwd_finalize_kernel adds back).  No doubles per
 // element: a wave needs 40 instead of 64 registers, so that two instead of one fit on a SIMD beside the weight-gradient kernel.
 // POOL: dz is not read but PRODUCED here - the gradient of an activation that was pooled (gpool: gradient of the pooled tensor, spread over
 // each 2 x 2 x 2 window with the ceil-mode divisor, the arithmetic of avgpool2_bwd_kernel) and possibly also used as a skip connection
@@ -264,12 +261,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_bwd_reduce_kernel(const TG* __re
             }
             pulpo::ldv<VEC>(y + p * yps + c, v);
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                const float bn = v[k] * sc[k] + sh[k];
-                const float d = bn > 0.f ? g[k] : g[k] * slope;
-                s0[k] += d;
-                s1[k] = fmaf(d, v[k] - m32[k], s1[k]);
-            }
+            for (int k = 0; k < VEC; ++k) pulpo::bn_bwd_reduce_step(g[k], v[k], sc[k], sh[k], m32[k], slope, s0[k], s1[k]);
         }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {

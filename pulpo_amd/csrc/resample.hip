@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256) void feedback_bwd4_kernel(FeedbackArgs a, cons
     }
 }
 
-inline int eblocks(long items) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, 8192)); }
+using pulpo::eblocks;
 
 }  // namespace
 
@@ -448,11 +448,11 @@ int avgpool2_fwd_t(const T* in, long ips, T* out, long ops, int B, int D, int H,
     pulpo::GroupProbe g(C);
     g.add(in, ips, sizeof(T)); g.add(out, ops, sizeof(T));
     if (sizeof(T) == 2 && g.ok8) {
-        hipLaunchKernelGGL((avgpool2_fwd_kernel<8, T>), dim3(eblocks((long)B * Do * Ho * Wo * (C / 8))), dim3(256), 0, st, in, ips, out, ops, B, D, H, W, Do, Ho, Wo, C);
+        hipLaunchKernelGGL((avgpool2_fwd_kernel<8, T>), dim3(eblocks((long)B * Do * Ho * Wo * (C / 8), 8192)), dim3(256), 0, st, in, ips, out, ops, B, D, H, W, Do, Ho, Wo, C);
     } else if (g.ok4) {
-        hipLaunchKernelGGL((avgpool2_fwd_kernel<4, T>), dim3(eblocks((long)B * Do * Ho * Wo * (C / 4))), dim3(256), 0, st, in, ips, out, ops, B, D, H, W, Do, Ho, Wo, C);
+        hipLaunchKernelGGL((avgpool2_fwd_kernel<4, T>), dim3(eblocks((long)B * Do * Ho * Wo * (C / 4), 8192)), dim3(256), 0, st, in, ips, out, ops, B, D, H, W, Do, Ho, Wo, C);
     } else {
-        hipLaunchKernelGGL((avgpool2_fwd_kernel<1, T>), dim3(eblocks((long)B * Do * Ho * Wo * C)), dim3(256), 0, st, in, ips, out, ops, B, D, H, W, Do, Ho, Wo, C);
+        hipLaunchKernelGGL((avgpool2_fwd_kernel<1, T>), dim3(eblocks((long)B * Do * Ho * Wo * C, 8192)), dim3(256), 0, st, in, ips, out, ops, B, D, H, W, Do, Ho, Wo, C);
     }
     return pulpo::check_launch("avgpool2_fwd");
 }
@@ -463,11 +463,11 @@ int avgpool2_bwd_t(const T* gout, long gops, const T* add, long aps, T* gin, lon
     pulpo::GroupProbe g(C);
     g.add(gout, gops, sizeof(T)); g.add(gin, gips, sizeof(T)); g.add(add, aps, sizeof(T));
     if (sizeof(T) == 2 && g.ok8) {
-        hipLaunchKernelGGL((avgpool2_bwd_kernel<8, T>), dim3(eblocks((long)B * D * H * W * (C / 8))), dim3(256), 0, st, gout, gops, gin, gips, B, D, H, W, Do, Ho, Wo, C, add, aps);
+        hipLaunchKernelGGL((avgpool2_bwd_kernel<8, T>), dim3(eblocks((long)B * D * H * W * (C / 8), 8192)), dim3(256), 0, st, gout, gops, gin, gips, B, D, H, W, Do, Ho, Wo, C, add, aps);
     } else if (g.ok4) {
-        hipLaunchKernelGGL((avgpool2_bwd_kernel<4, T>), dim3(eblocks((long)B * D * H * W * (C / 4))), dim3(256), 0, st, gout, gops, gin, gips, B, D, H, W, Do, Ho, Wo, C, add, aps);
+        hipLaunchKernelGGL((avgpool2_bwd_kernel<4, T>), dim3(eblocks((long)B * D * H * W * (C / 4), 8192)), dim3(256), 0, st, gout, gops, gin, gips, B, D, H, W, Do, Ho, Wo, C, add, aps);
     } else {
-        hipLaunchKernelGGL((avgpool2_bwd_kernel<1, T>), dim3(eblocks((long)B * D * H * W * C)), dim3(256), 0, st, gout, gops, gin, gips, B, D, H, W, Do, Ho, Wo, C, add, aps);
+        hipLaunchKernelGGL((avgpool2_bwd_kernel<1, T>), dim3(eblocks((long)B * D * H * W * C, 8192)), dim3(256), 0, st, gout, gops, gin, gips, B, D, H, W, Do, Ho, Wo, C, add, aps);
     }
     return pulpo::check_launch("avgpool2_bwd");
 }
@@ -515,11 +515,11 @@ PULPO_API int pulpo_resize_trilinear_scaled_fwd(const float* in, const float* ad
                 sw = scale_w > 0.f ? scale_w : (float)Wi / (float)Wo;
     if (Do == 2 * Di && Ho == 2 * Hi && Wo == 2 * Wi && sd == 0.5f && sh == 0.5f && sw == 0.5f && nplanes * (long)Do * Ho < (1L << 31) &&
         (((uintptr_t)out | (uintptr_t)add) & 7) == 0) {
-        hipLaunchKernelGGL(resize_up2_fwd_kernel, dim3(eblocks(nplanes * Do * Ho * Wi)), dim3(256), 0, (hipStream_t)stream, in, add, out, (int)nplanes, Di, Hi,
+        hipLaunchKernelGGL(resize_up2_fwd_kernel, dim3(eblocks(nplanes * Do * Ho * Wi, 8192)), dim3(256), 0, (hipStream_t)stream, in, add, out, (int)nplanes, Di, Hi,
                            Wi, mult);
         return pulpo::check_launch("resize_up2_fwd");
     }
-    hipLaunchKernelGGL(resize_fwd_kernel, dim3(eblocks(nplanes * Do * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, in, add, out, (long)nplanes, Di,
+    hipLaunchKernelGGL(resize_fwd_kernel, dim3(eblocks(nplanes * Do * Ho * Wo, 8192)), dim3(256), 0, (hipStream_t)stream, in, add, out, (long)nplanes, Di,
                        Hi, Wi, Do, Ho, Wo, sd, sh, sw, mult);
     return pulpo::check_launch("resize_fwd");
 }
@@ -536,17 +536,17 @@ static int resize_bwd_impl(const float* gout, float* gin, int64_t nplanes, int D
     const float sd = scale_d > 0.f ? scale_d : (float)Di / (float)Do, sh = scale_h > 0.f ? scale_h : (float)Hi / (float)Ho,
                 sw = scale_w > 0.f ? scale_w : (float)Wi / (float)Wo;
     if (Do == 2 * Di && Ho == 2 * Hi && Wo == 2 * Wi && sd == 0.5f && sh == 0.5f && sw == 0.5f) {
-        hipLaunchKernelGGL(resize_up2_bwd_kernel, dim3(eblocks(nplanes * Di * Hi * Wi)), dim3(256), 0, st, gout, gin, (long)nplanes, Di, Hi, Wi, mult);
+        hipLaunchKernelGGL(resize_up2_bwd_kernel, dim3(eblocks(nplanes * Di * Hi * Wi, 8192)), dim3(256), 0, st, gout, gin, (long)nplanes, Di, Hi, Wi, mult);
         return pulpo::check_launch("resize_up2_bwd");
     }
     if (det) {
-        hipLaunchKernelGGL(resize_bwd_gather_kernel, dim3(eblocks(nplanes * Di * Hi * Wi)), dim3(256), 0, st, gout, gin, (long)nplanes, Di, Hi, Wi, Do,
+        hipLaunchKernelGGL(resize_bwd_gather_kernel, dim3(eblocks(nplanes * Di * Hi * Wi, 8192)), dim3(256), 0, st, gout, gin, (long)nplanes, Di, Hi, Wi, Do,
                            Ho, Wo, sd, sh, sw, mult);
         return pulpo::check_launch("resize_bwd_gather");
     }
     hipError_t e = hipMemsetAsync(gin, 0, sizeof(float) * nplanes * Di * Hi * Wi, st);
     if (e != hipSuccess) return pulpo::fail((int)e, "resize_bwd memset: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(resize_bwd_atomic_kernel, dim3(eblocks(nplanes * Do * Ho * Wo)), dim3(256), 0, st, gout, gin, (long)nplanes, Di, Hi, Wi, Do,
+    hipLaunchKernelGGL(resize_bwd_atomic_kernel, dim3(eblocks(nplanes * Do * Ho * Wo, 8192)), dim3(256), 0, st, gout, gin, (long)nplanes, Di, Hi, Wi, Do,
                        Ho, Wo, sd, sh, sw, mult);
     return pulpo::check_launch("resize_bwd_atomic");
 }
@@ -577,7 +577,7 @@ PULPO_API int pulpo_feedback_up2_fwd_t(const float* const* srcs, const int* chan
     a.nsrc = nsrc; a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi;
     for (int i = 0; i < nsrc; ++i) { a.src[i] = srcs[i]; a.ch[i] = chans[i]; a.ctot += chans[i]; }
     PULPO_REQUIRE(a.ctot <= 16, "feedback_up2_fwd: more than 16 feedback channels");
-    const int nb = eblocks((long)B * 8 * Di * Hi * Wi);
+    const int nb = eblocks((long)B * 8 * Di * Hi * Wi, 8192);
     PULPO_DISPATCH_DT(dt, T, hipLaunchKernelGGL((feedback_fwd_kernel<T>), dim3(nb), dim3(256), 0, (hipStream_t)stream, a, (T*)out, (long)ops));
     return pulpo::check_launch("feedback_up2_fwd");
 }
@@ -598,8 +598,8 @@ PULPO_API int pulpo_feedback_up2_bwd_t(const void* gout, int dt, int64_t gops, f
     PULPO_REQUIRE(a.ctot <= 16, "feedback_up2_bwd: more than 16 feedback channels");
     const bool four = a.ctot % 4 == 0 && gops % 4 == 0 && (((uintptr_t)gout) % (dt ? 8 : 16)) == 0;
     PULPO_DISPATCH_DT(dt, T, {
-        if (four) hipLaunchKernelGGL((feedback_bwd4_kernel<T>), dim3(eblocks((long)B * Di * Hi * Wi * (a.ctot / 4))), dim3(256), 0, (hipStream_t)stream, a, (const T*)gout, (long)gops);
-        else hipLaunchKernelGGL((feedback_bwd_kernel<T>), dim3(eblocks((long)B * Di * Hi * Wi * a.ctot)), dim3(256), 0, (hipStream_t)stream, a, (const T*)gout, (long)gops);
+        if (four) hipLaunchKernelGGL((feedback_bwd4_kernel<T>), dim3(eblocks((long)B * Di * Hi * Wi * (a.ctot / 4), 8192)), dim3(256), 0, (hipStream_t)stream, a, (const T*)gout, (long)gops);
+        else hipLaunchKernelGGL((feedback_bwd_kernel<T>), dim3(eblocks((long)B * Di * Hi * Wi * a.ctot, 8192)), dim3(256), 0, (hipStream_t)stream, a, (const T*)gout, (long)gops);
     });
     return pulpo::check_launch("feedback_up2_bwd");
 }

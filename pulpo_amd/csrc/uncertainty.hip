@@ -7,7 +7,7 @@
 
 namespace {
 
-inline int eblocks(long items, int cap = 8192) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, cap)); }
+using pulpo::eblocks;
 
 // k = number of samples including this one (k >= 1)
 __global__ __launch_bounds__(256) void mc_update_kernel(const float* __restrict__ sample, float* __restrict__ mean, float* __restrict__ m2, long n,
@@ -41,13 +41,13 @@ __global__ __launch_bounds__(256) void mc_std_kernel(const float* __restrict__ m
 
 PULPO_API int pulpo_mc_moments_update(const float* sample, float* mean, float* m2, int64_t n, int k, void* stream) {
     PULPO_REQUIRE(sample && mean && m2 && n > 0 && k >= 1, "mc_moments_update: bad arguments");
-    hipLaunchKernelGGL(mc_update_kernel, dim3(eblocks(n)), dim3(256), 0, (hipStream_t)stream, sample, mean, m2, (long)n, k);
+    hipLaunchKernelGGL(mc_update_kernel, dim3(eblocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, sample, mean, m2, (long)n, k);
     return pulpo::check_launch("mc_moments_update");
 }
 
 PULPO_API int pulpo_mc_moments_std(const float* m2, const float* scale, float* out, int B, int C, int64_t V, int k, void* stream) {
     PULPO_REQUIRE(m2 && out && B > 0 && C > 0 && V > 0 && k >= 1, "mc_moments_std: bad arguments");
     const long total = (long)B * V;
-    hipLaunchKernelGGL(mc_std_kernel, dim3(eblocks(total)), dim3(256), 0, (hipStream_t)stream, m2, scale, out, C, (long)V, total, k);
+    hipLaunchKernelGGL(mc_std_kernel, dim3(eblocks(total, 8192)), dim3(256), 0, (hipStream_t)stream, m2, scale, out, C, (long)V, total, k);
     return pulpo::check_launch("mc_moments_std");
 }

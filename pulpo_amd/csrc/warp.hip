@@ -300,7 +300,7 @@ __global__ __launch_bounds__(VI_THREADS) void vecint_fwd_lds_kernel(const float*
     }
 }
 
-inline int eblocks(long items) { return (int)std::max<long>(1, std::min<long>((items + 255) / 256, 8192)); }
+using pulpo::eblocks;
 
 // ------------------------------------------------------------------------------------------------ deterministic backward (PULPO_DETERMINISTIC)
 // The scatter of the image gradient (grid_sampler_3d_backward's atomics; network_blocks.py:120, :175) is what makes these backward passes differ
@@ -419,7 +419,7 @@ PULPO_API int pulpo_warp_mask_fwd(const float* df, const float* mask, float* out
     PULPO_REQUIRE(df && mask && out && B > 0, "warp_mask_fwd: bad arguments");
     PULPO_REQUIRE(Dg >= 1 && Hg > 1 && Wg > 1 && Di > 0 && Hi > 0 && Wi > 0 && (Dg > 1 || Di == 1), "warp_mask_fwd: grid H, W must be > 1 (depth 1 = 2-D form, with a depth-1 mask)");
     PULPO_REQUIRE((long)Dg * Hg * Wg < (1L << 31), "warp_mask_fwd: grids of 2^31 voxels and more are not supported");
-    hipLaunchKernelGGL(warp_mask_fwd_kernel, dim3(eblocks((long)B * Dg * Hg * Wg)), dim3(256), 0, (hipStream_t)stream, df, mask, out, B, Dg, Hg, Wg, Di, Hi, Wi);
+    hipLaunchKernelGGL(warp_mask_fwd_kernel, dim3(eblocks((long)B * Dg * Hg * Wg, 8192)), dim3(256), 0, (hipStream_t)stream, df, mask, out, B, Dg, Hg, Wg, Di, Hi, Wi);
     return pulpo::check_launch("warp_mask_fwd");
 }
 
@@ -430,9 +430,9 @@ PULPO_API int pulpo_warp3d_fwd(const float* df, const float* img, float* out, in
     PULPO_REQUIRE((long)Dg * Hg * Wg < (1L << 31), "warp3d_fwd: grids of 2^31 voxels and more are not supported");
     const long total = (long)B * Dg * Hg * Wg;
     hipStream_t st = (hipStream_t)stream;
-    if (C == 1) hipLaunchKernelGGL(warp_fwd_kernel<1>, dim3(eblocks(total)), dim3(256), 0, st, df, img, nullptr, out, B, Dg, Hg, Wg, Di, Hi, Wi, C);
-    else if (C == 3) hipLaunchKernelGGL(warp_fwd_kernel<3>, dim3(eblocks(total)), dim3(256), 0, st, df, img, nullptr, out, B, Dg, Hg, Wg, Di, Hi, Wi, C);
-    else hipLaunchKernelGGL(warp_fwd_kernel<0>, dim3(eblocks(total)), dim3(256), 0, st, df, img, nullptr, out, B, Dg, Hg, Wg, Di, Hi, Wi, C);
+    if (C == 1) hipLaunchKernelGGL(warp_fwd_kernel<1>, dim3(eblocks(total, 8192)), dim3(256), 0, st, df, img, nullptr, out, B, Dg, Hg, Wg, Di, Hi, Wi, C);
+    else if (C == 3) hipLaunchKernelGGL(warp_fwd_kernel<3>, dim3(eblocks(total, 8192)), dim3(256), 0, st, df, img, nullptr, out, B, Dg, Hg, Wg, Di, Hi, Wi, C);
+    else hipLaunchKernelGGL(warp_fwd_kernel<0>, dim3(eblocks(total, 8192)), dim3(256), 0, st, df, img, nullptr, out, B, Dg, Hg, Wg, Di, Hi, Wi, C);
     return pulpo::check_launch("warp3d_fwd");
 }
 
@@ -447,7 +447,7 @@ PULPO_API int pulpo_warp3d_bwd(const float* df, const float* img, const float* g
         if (e != hipSuccess) return pulpo::fail((int)e, "warp3d_bwd memset: %s", hipGetErrorString(e));
     }
     const long total = (long)B * Dg * Hg * Wg;
-    hipLaunchKernelGGL(warp_bwd_kernel<false>, dim3(eblocks(total)), dim3(256), 0, st, df, img, gout, gdf, gimg, B, Dg, Hg, Wg, Di, Hi, Wi, C);
+    hipLaunchKernelGGL(warp_bwd_kernel<false>, dim3(eblocks(total, 8192)), dim3(256), 0, st, df, img, gout, gdf, gimg, B, Dg, Hg, Wg, Di, Hi, Wi, C);
     return pulpo::check_launch("warp3d_bwd");
 }
 
@@ -472,12 +472,12 @@ PULPO_API int pulpo_vecint_fwd(const float* v, float* work, int B, int D, int H,
         hipLaunchKernelGGL(vecint_fwd_lds_kernel, dim3(B), dim3(VI_THREADS), lds, st, v, work, B, D, H, W, nsteps, 1.0f / (float)(1 << nsteps));
         return pulpo::check_launch("vecint_fwd_lds");
     }
-    hipLaunchKernelGGL(scale_kernel, dim3(eblocks(n)), dim3(256), 0, st, v, work, 1.0f / (float)(1 << nsteps), n);
+    hipLaunchKernelGGL(scale_kernel, dim3(eblocks(n, 8192)), dim3(256), 0, st, v, work, 1.0f / (float)(1 << nsteps), n);
     int rc = pulpo::check_launch("vecint scale");
     if (rc) return rc;
     for (int k = 0; k < nsteps; ++k) {
         const float* cur = work + (long)k * n;
-        hipLaunchKernelGGL(warp_fwd_kernel<3>, dim3(eblocks(total)), dim3(256), 0, st, cur, cur, cur, work + (long)(k + 1) * n, B, D, H, W, D, H, W, 3);
+        hipLaunchKernelGGL(warp_fwd_kernel<3>, dim3(eblocks(total, 8192)), dim3(256), 0, st, cur, cur, cur, work + (long)(k + 1) * n, B, D, H, W, D, H, W, 3);
         rc = pulpo::check_launch("vecint step");
         if (rc) return rc;
     }
@@ -530,13 +530,13 @@ PULPO_API int pulpo_vecint_bwd(const float* work, const float* gout, float* gin,
             gp = tmp + (long)(k & 1) * n;
             hipError_t e = hipMemcpyAsync(gp, g, sizeof(float) * n, hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) return pulpo::fail((int)e, "vecint_bwd copy: %s", hipGetErrorString(e));
-            hipLaunchKernelGGL(warp_bwd_kernel<true>, dim3(eblocks(total)), dim3(256), 0, st, cur, cur, g, gp, gp, B, D, H, W, D, H, W, 3);
+            hipLaunchKernelGGL(warp_bwd_kernel<true>, dim3(eblocks(total, 8192)), dim3(256), 0, st, cur, cur, g, gp, gp, B, D, H, W, D, H, W, 3);
         }
         int rc = pulpo::check_launch("vecint_bwd step");
         if (rc) return rc;
         g = gp;
     }
-    hipLaunchKernelGGL(scale_kernel, dim3(eblocks(n)), dim3(256), 0, st, g, gin, scale, n);
+    hipLaunchKernelGGL(scale_kernel, dim3(eblocks(n, 8192)), dim3(256), 0, st, g, gin, scale, n);
     return pulpo::check_launch("vecint_bwd scale");
 }
 
@@ -557,7 +557,7 @@ PULPO_API int pulpo_warp3d_bwd_det(const float* df, const float* img, const floa
     if (gimg == nullptr) {
         // the displacement gradient alone is a gather with plain stores, deterministic as it is: the plain kernel (the fixed-point one reads its
         // scale slot from the workspace, which this call need not pass)
-        hipLaunchKernelGGL(warp_bwd_kernel<false>, dim3(eblocks(total)), dim3(256), 0, st, df, img, gout, gdf, (float*)nullptr, B, Dg, Hg, Wg, Di, Hi, Wi, C);
+        hipLaunchKernelGGL(warp_bwd_kernel<false>, dim3(eblocks(total, 8192)), dim3(256), 0, st, df, img, gout, gdf, (float*)nullptr, B, Dg, Hg, Wg, Di, Hi, Wi, C);
         return pulpo::check_launch("warp3d_bwd_det");
     }
     unsigned* slots = (unsigned*)ws;
@@ -565,7 +565,7 @@ PULPO_API int pulpo_warp3d_bwd_det(const float* df, const float* img, const floa
     hipError_t e = hipMemsetAsync(ws, 0, 256 + sizeof(long long) * (size_t)ni, st);
     if (e != hipSuccess) return pulpo::fail((int)e, "warp3d_bwd_det memset: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(absmax_kernel, dim3(fx_blocks((long)B * C * Dg * Hg * Wg)), dim3(256), 0, st, gout, (long)B * C * Dg * Hg * Wg, slots);
-    hipLaunchKernelGGL(warp_bwd_fx_kernel<false>, dim3(eblocks(total)), dim3(256), 0, st, df, img, gout, gdf, acc, slots, B, Dg, Hg, Wg, Di, Hi, Wi, C);
+    hipLaunchKernelGGL(warp_bwd_fx_kernel<false>, dim3(eblocks(total, 8192)), dim3(256), 0, st, df, img, gout, gdf, acc, slots, B, Dg, Hg, Wg, Di, Hi, Wi, C);
     hipLaunchKernelGGL(fx_to_float_kernel, dim3(fx_blocks(ni)), dim3(256), 0, st, acc, gimg, ni, slots, 1.0f, (unsigned*)nullptr);
     return pulpo::check_launch("warp3d_bwd_det");
 }
@@ -583,7 +583,7 @@ PULPO_API int pulpo_vecint_bwd_det(const float* work, const float* gout, float* 
     const long n = (long)B * 3 * D * H * W, total = (long)B * D * H * W;
     const float scale = 1.0f / (float)(1 << nsteps);
     if (nsteps == 0) {
-        hipLaunchKernelGGL(scale_kernel, dim3(eblocks(n)), dim3(256), 0, st, gout, gin, scale, n);
+        hipLaunchKernelGGL(scale_kernel, dim3(eblocks(n, 8192)), dim3(256), 0, st, gout, gin, scale, n);
         return pulpo::check_launch("vecint_bwd_det scale");
     }
     unsigned* slots = (unsigned*)ws;                       // slot k: largest |gradient| entering step k's scatter
@@ -595,7 +595,7 @@ PULPO_API int pulpo_vecint_bwd_det(const float* work, const float* gout, float* 
     const float* g = gout;
     for (int k = nsteps - 1; k >= 0; --k) {
         const float* cur = work + (long)k * n;
-        hipLaunchKernelGGL(warp_bwd_fx_kernel<true>, dim3(eblocks(total)), dim3(256), 0, st, cur, cur, g, (float*)nullptr, acc, slots + k, B, D, H, W, D, H, W, 3);
+        hipLaunchKernelGGL(warp_bwd_fx_kernel<true>, dim3(eblocks(total, 8192)), dim3(256), 0, st, cur, cur, g, (float*)nullptr, acc, slots + k, B, D, H, W, D, H, W, 3);
         float* out = k == 0 ? gin : buf[k & 1];
         hipLaunchKernelGGL(fx_to_float_kernel, dim3(fx_blocks(n)), dim3(256), 0, st, acc, out, n, slots + k, k == 0 ? scale : 1.0f, k == 0 ? (unsigned*)nullptr : slots + (k - 1));
         g = out;
