@@ -480,6 +480,29 @@ size_t pulpo_surface_distances_ws_bytes(int B, int C, int D, int H, int W);
 int pulpo_surface_distances(const void* lab_a, const void* lab_b, int ldt, int C, double q, float* out, int* hist /*nullable*/, void* ws, int* flag,
                             int B, int D, int H, int W, int nd, void* stream);
 
+/* ------------------------------------------------------------------------- training augmentation (added within ABI 8: nothing else changed)
+ * No counterpart in the reference, whose datasets hand out raw pairs; DESIGN.md section 3p holds the definitions.
+ * Spatial map of an output voxel v of the grid (D,H,W): q = v + e(v), p = c + M (q - c) + t with theta (B,3,4) = [M | t] as for the affine
+ *   operators (NULL: the identity); e = the cubic B-spline free-form deformation of the control lattice phi (B,3,Gz,Gy,Gx), voxel displacements,
+ *   integer spacing s >= 2 voxels, G = ceil((S - 1) / s) + 3 per axis (NULL: e = 0).  A depth-1 grid is the 2-D form: Gz = 1, no depth coordinate.
+ * Sampler, in voxel units: images and masks trilinear at p with corners outside the volume contributing `fill`
+ *   (grid_sample(align_corners=True, padding_mode="zeros") for fill = 0); label maps at floor(p + 0.5) per axis, fill_label outside.
+ * pulpo_augment_apply: one launch for up to three sources of a sample on the grid (D,H,W), each with an output of its own shape - img (B,C,..)
+ *   fp32, mask (B,Cm,..) fp32, labels (B,1,..) (ldt 0 uint8, 1 int32); any may be NULL, not all.  The image alone goes through the intensity
+ *   transform, in this order, each piece present when its bit of iflags is set: 1 r = clamp(r,0,1)^gamma; (bias non-NULL) r *= exp(beta(v)),
+ *   beta = the trilinear interpolation of the lattice bias (B,Lz,Ly,Lx) whose end nodes sit on the volume's end voxels (at most 4096 nodes);
+ *   2 r = gain r + offset; 4 r += sigma n(i); 8 r = clamp(r,0,1).  iparams (B,4) = gamma, gain, offset, sigma per sample.  n(i): a standard
+ *   normal that is a pure function of the seed (one int64 ON THE DEVICE) and the element's linear index i in the planar output - Philox4x32-10
+ *   with counter (i >> 2, 0) and key = the seed's halves, Box-Muller on the word pair of lane i & 3.  No atomics: the same bits on every call.
+ * pulpo_bspline_field: out (B,3,D,H,W) planar = e, or p - v when theta is given; the fused kernel's coordinates bit for bit.
+ * pulpo_philox4x32: out (n,4) = Philox4x32-10 of counters (n,4) under key (2 words), all int32 bit patterns on the device. */
+int pulpo_augment_apply(const float* theta, const float* phi, int spacing, int Gz, int Gy, int Gx, const float* img, float* img_out, int C,
+                        const float* mask, float* mask_out, int Cm, const void* labels, void* labels_out, int ldt, const float* iparams, int iflags,
+                        const float* bias, int Lz, int Ly, int Lx, const void* seed, float fill, int fill_label, int B, int D, int H, int W,
+                        void* stream);
+int pulpo_bspline_field(const float* phi, const float* theta, float* out, int spacing, int Gz, int Gy, int Gx, int B, int D, int H, int W, void* stream);
+int pulpo_philox4x32(const void* counters, const void* key, void* out, int64_t n, void* stream);
+
 /* --------------------------------------------------------------------------------------------------- optimizer
  * torch.optim.Adam(lr) defaults (src/models.py:398-400) over a flat fp32 arena; gscale pre-multiplies the gradient.  beta1, beta2 are doubles
  * (since ABI 8): 1 - beta and 1 - beta^step are formed in double. */

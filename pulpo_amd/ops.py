@@ -3186,3 +3186,188 @@ def affine_compose(theta, df, image_size=None):
     lib.call("pulpo_affine_compose", _ptr(theta), _ptr(df5), _ptr(out), B, Dg, Hg, Wg, Di, Hi, Wi, _stream())
     _hbm_end(t0, "affine_compose", 8.0 * out.numel())
     return _unlift_field(out) if two_d else out
+
+
+# ------------------------------------------------------------------------------------------------ training augmentation
+# Augmentation is data: no autograd, and a source that requires grad is refused.  Every refusal below is a ValueError raised before anything is
+# launched (and before a GPU is needed).
+_INTENSITY_KEYS = ("gamma", "gain", "offset", "sigma", "bias", "seed", "clip")
+_AUG_BIAS_MAX_NODES = 4096
+
+
+def bspline_lattice_size(size, spacing: int):
+    """extents of the control lattice of a grid: ceil((S - 1) / s) + 3 per axis"""
+    return tuple(-(-(int(S) - 1) // int(spacing)) + 3 for S in size)
+
+
+def _aug_lattice(phi, spacing, two_d: bool, size3, B: int, name: str):
+    """phi as (B,3,Gz,Gy,Gx) (slices: (B,2,Gy,Gx) lifted with a zero depth component and Gz = 1), checked against the grid"""
+    if spacing is None or int(spacing) != spacing or int(spacing) < 2:
+        raise ValueError(f"{name}: an integer lattice spacing >= 2 voxels expected with phi, got {spacing!r}")
+    nd = 2 if two_d else 3
+    if phi.dim() != nd + 2 or phi.shape[1] != nd:
+        raise ValueError(f"{name}: phi (B,{nd}," + ",".join("G" * nd) + f") expected for {nd}-D arguments, got {tuple(phi.shape)}")
+    if phi.shape[0] != B:
+        raise ValueError(f"{name}: phi has batch size {phi.shape[0]}, the other arguments {B}")
+    want = bspline_lattice_size(size3[3 - nd:], spacing)
+    if tuple(phi.shape[2:]) != want:
+        raise ValueError(f"{name}: a lattice of ceil((S - 1) / s) + 3 = {want} nodes expected for the grid {tuple(size3[3 - nd:])} at spacing {spacing}, "
+                         f"got {tuple(phi.shape[2:])}")
+    phi = phi.detach()
+    return _lift_field(phi) if two_d else phi
+
+
+def _per_sample_column(v, B: int, default: float, dev, name: str):
+    if v is None:
+        v = default
+    if torch.is_tensor(v):
+        if v.numel() != B:
+            raise ValueError(f"augment: intensity[{name!r}] holds {v.numel()} values for a batch of {B}")
+        return v.detach().reshape(B).to(device=dev, dtype=torch.float32)
+    return float(v)
+
+
+@torch.no_grad()
+def augment(img=None, mask=None, labels=None, *, theta=None, phi=None, spacing=None, intensity=None, fill: float = 0.0, fill_label: int = 0):
+    """One random spatial map per sample, evaluated once per output voxel and applied to every source given, in ONE launch that writes neither a
+    sampling grid nor a field.  Output voxel v samples the sources at p = c + M (q - c) + t, q = v + e(v): theta (B,3,4) = [M | t] in voxel
+    units about the grid's centre c (None: the identity), e the cubic B-spline free-form deformation of the control lattice phi
+    (B,3,Gz,Gy,Gx) of integer `spacing` s >= 2 voxels with G = ceil((S - 1) / s) + 3 nodes per axis (None: e = 0).
+    img (B,C,D,H,W) fp32 and mask (B,Cm,D,H,W) fp32: trilinear in voxel units, corners outside the volume contribute `fill`
+    (grid_sample(align_corners=True, padding_mode="zeros")); labels (B,1,D,H,W) uint8 / int32: the nearest voxel floor(p + 0.5), fill_label
+    outside.  The identity returns every source bit for bit.  Slices: (B,C,H,W) sources with theta (B,2,3) and phi (B,2,Gy,Gx).
+    intensity (the image only, after sampling, every piece optional): a dict of per-sample tensors (B,) or floats - r = clamp(r,0,1)^gamma;
+    r *= exp(beta), beta the trilinear interpolation of the log-bias lattice `bias` (B,Lz,Ly,Lx) spanning the volume; r = gain r + offset;
+    r += sigma n, n a standard normal that is a pure function of `seed` (an int, or one int64 on the device) and the element's index
+    (Philox4x32-10); clip: clamp(r,0,1).  Returns a tuple, in the order of the sources given.  Deterministic, no autograd."""
+    given = [(n, t) for n, t in (("img", img), ("mask", mask), ("labels", labels)) if t is not None]
+    if not given:
+        raise ValueError("augment: give at least one of img, mask, labels")
+    first = given[0][1]
+    if first.dim() not in (4, 5):
+        raise ValueError(f"augment: (B,C,D,H,W) or (B,C,H,W) sources expected, got {tuple(first.shape)}")
+    two_d = first.dim() == 4
+    B, grid = first.shape[0], tuple(first.shape[2:])
+    for n, t in given:
+        if t.dim() != first.dim():
+            raise ValueError("augment: 2-D and 3-D arguments do not mix")
+        if t.shape[0] != B or tuple(t.shape[2:]) != grid:
+            raise ValueError(f"augment: {n} {tuple(t.shape)} does not share the batch size and grid of {given[0][0]} {tuple(first.shape)}")
+        if t.requires_grad:
+            raise ValueError(f"augment: {n} requires grad; augmentation is data (detach it)")
+    for n, t in (("img", img), ("mask", mask)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"augment: {n} is fp32 (got {t.dtype})")
+    if labels is not None:
+        if labels.is_floating_point() or labels.dtype not in _LABEL_DT:
+            raise ValueError(f"augment: label maps are uint8 or int32 (got {labels.dtype}); a float map goes in as mask")
+        if labels.shape[1] != 1:
+            raise ValueError(f"augment: a label map (B,1,...) expected, got {tuple(labels.shape)}")
+    size3 = ((1,) + grid) if two_d else grid
+    theta3 = None
+    if theta is not None:
+        if theta.dim() != 3 or tuple(theta.shape[1:]) != ((2, 3) if two_d else (3, 4)):
+            raise ValueError(f"augment: theta (B,2,3) for slices, (B,3,4) for volumes expected, got {tuple(theta.shape)} for {first.dim() - 2}-D sources")
+        if theta.shape[0] != B:
+            raise ValueError(f"augment: theta has batch size {theta.shape[0]}, the sources {B}")
+        theta3 = _theta3(theta.detach(), "augment")[0]
+    phi5 = _aug_lattice(phi, spacing, two_d, size3, B, "augment") if phi is not None else None
+    cfg = dict(intensity or {})
+    unknown = [k for k in cfg if k not in _INTENSITY_KEYS]
+    if unknown:
+        raise ValueError(f"augment: unknown intensity keys {unknown} (known: {_INTENSITY_KEYS})")
+    active = any(cfg.get(k) is not None for k in ("gamma", "gain", "offset", "sigma", "bias")) or bool(cfg.get("clip"))
+    if active and img is None:
+        raise ValueError("augment: the intensity transform applies to img, which is missing")
+    bias = cfg.get("bias")
+    if bias is not None:
+        if bias.dim() != first.dim() - 1 or bias.shape[0] != B:
+            raise ValueError(f"augment: a log-bias lattice (B,{'Ly,Lx' if two_d else 'Lz,Ly,Lx'}) expected, got {tuple(bias.shape)}")
+        if bias[0].numel() > _AUG_BIAS_MAX_NODES or bias[0].numel() < 1:
+            raise ValueError(f"augment: a log-bias lattice of 1 to {_AUG_BIAS_MAX_NODES} nodes expected, got {bias[0].numel()}")
+    if cfg.get("sigma") is not None and cfg.get("seed") is None:
+        raise ValueError("augment: intensity['sigma'] needs intensity['seed']")
+    dev = first.device
+    cols = [_per_sample_column(cfg.get(k), B, d, dev, k) for k, d in (("gamma", 1.0), ("gain", 1.0), ("offset", 0.0), ("sigma", 0.0))]
+
+    _require_gpu(img, mask, theta3, phi5, bias)
+    _require_labels(labels)
+    iflags = (1 if cfg.get("gamma") is not None else 0) | (2 if cfg.get("gain") is not None or cfg.get("offset") is not None else 0) \
+        | (4 if cfg.get("sigma") is not None else 0) | (8 if cfg.get("clip") else 0)
+    iparams = seed = None
+    if iflags & 7:
+        if any(torch.is_tensor(c) for c in cols):
+            iparams = torch.stack([c if torch.is_tensor(c) else torch.full((B,), c, device=dev, dtype=torch.float32) for c in cols], dim=1).contiguous()
+        else:
+            iparams = torch.tensor([cols] * B, dtype=torch.float32).to(dev)
+    if iflags & 4:
+        seed = cfg["seed"]
+        if not torch.is_tensor(seed):
+            s = int(seed) & ((1 << 64) - 1)
+            seed = torch.tensor([s - (1 << 64) if s >= (1 << 63) else s], dtype=torch.int64).to(dev)
+        elif seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_cuda:
+            raise PulpoHipError("augment: intensity['seed'] is an int or one int64 on the device")
+    lift = (lambda t: None if t is None else t.unsqueeze(2)) if two_d else (lambda t: t)
+    img5 = None if img is None else planar(lift(img))
+    mask5 = None if mask is None else planar(lift(mask))
+    lab5 = None if labels is None else lift(labels).contiguous()
+    bias4 = None if bias is None else (bias.detach().unsqueeze(1) if two_d else bias.detach()).contiguous()
+    theta3 = None if theta3 is None else theta3.contiguous()
+    phi5 = None if phi5 is None else planar(phi5)
+    D, H, W = size3
+    outs = [None if t is None else torch.empty_like(t) for t in (img5, mask5, lab5)]
+    Gz, Gy, Gx = phi5.shape[2:] if phi5 is not None else (0, 0, 0)
+    Lz, Ly, Lx = bias4.shape[1:] if bias4 is not None else (0, 0, 0)
+    nbytes = 2.0 * sum(t.numel() * t.element_size() for t in (img5, mask5, lab5) if t is not None)      # the sources read once, the results written
+    t0 = _hbm_begin("augment_apply")
+    lib.call("pulpo_augment_apply", _ptr(theta3), _ptr(phi5), int(spacing) if phi5 is not None else 0, int(Gz), int(Gy), int(Gx),
+             _ptr(img5), _ptr(outs[0]), img5.shape[1] if img5 is not None else 0, _ptr(mask5), _ptr(outs[1]), mask5.shape[1] if mask5 is not None else 0,
+             _ptr(lab5), _ptr(outs[2]), _LABEL_DT[lab5.dtype] if lab5 is not None else 0, _ptr(iparams), iflags, _ptr(bias4), int(Lz), int(Ly), int(Lx),
+             _ptr(seed), float(fill), int(fill_label), B, D, H, W, _stream())
+    _hbm_end(t0, "augment_apply", nbytes)
+    return tuple(o.squeeze(2) if two_d else o for o in outs if o is not None)
+
+
+@torch.no_grad()
+def bspline_field(phi, size, spacing: int, theta=None):
+    """the displacement the augmentation's spatial map stands for, as a dense tensor: e (B,3,D,H,W), the cubic B-spline free-form deformation of
+    the control lattice phi (B,3,Gz,Gy,Gx) on the grid `size` at integer spacing s >= 2 (ops.augment's definition), or p - v when an affine
+    theta (B,3,4) is given - from the fused kernel's own coordinate code, bit for bit.  Slices: phi (B,2,Gy,Gx), size (H,W), theta (B,2,3) ->
+    (B,2,H,W).  No autograd."""
+    if phi.dim() not in (4, 5):
+        raise ValueError(f"bspline_field: phi (B,3,Gz,Gy,Gx) or (B,2,Gy,Gx) expected, got {tuple(phi.shape)}")
+    two_d = phi.dim() == 4
+    size3 = _size3(size, two_d, "bspline_field")
+    B = phi.shape[0]
+    theta3 = None
+    if theta is not None:
+        if theta.dim() != 3 or tuple(theta.shape[1:]) != ((2, 3) if two_d else (3, 4)) or theta.shape[0] != B:
+            raise ValueError(f"bspline_field: theta {tuple(theta.shape)} and phi {tuple(phi.shape)} do not go together")
+        theta3 = _theta3(theta.detach(), "bspline_field")[0]
+    phi5 = _aug_lattice(phi, spacing, two_d, size3, B, "bspline_field")
+    _require_gpu(phi5, theta3)
+    phi5 = planar(phi5)
+    theta3 = None if theta3 is None else theta3.contiguous()
+    D, H, W = size3
+    out = torch.empty((B, 3, D, H, W), device=phi5.device, dtype=torch.float32)
+    t0 = _hbm_begin("bspline_field")
+    lib.call("pulpo_bspline_field", _ptr(phi5), _ptr(theta3), _ptr(out), int(spacing), *(int(g) for g in phi5.shape[2:]), B, D, H, W, _stream())
+    _hbm_end(t0, "bspline_field", 4.0 * out.numel())
+    return _unlift_field(out) if two_d else out
+
+
+@torch.no_grad()
+def philox4x32(counters, key):
+    """raw Philox4x32-10 words: counters (N,4) and key (2,) as int32 bit patterns (or int64 values below 2^32) on the device -> (N,4) int32
+    bit patterns.  The generator behind ops.augment's noise, exposed so that it can be held to the published vectors."""
+    if counters.dim() != 2 or counters.shape[1] != 4 or counters.shape[0] < 1:
+        raise ValueError(f"philox4x32: counters (N,4) expected, got {tuple(counters.shape)}")
+    key = torch.as_tensor(key, device=counters.device)
+    if key.numel() != 2:
+        raise ValueError(f"philox4x32: a key of two words expected, got {tuple(key.shape)}")
+    if not counters.is_cuda:
+        raise PulpoHipError("pulpo_amd operators run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    c32, k32 = counters.to(torch.int32).contiguous(), key.reshape(2).to(torch.int32).contiguous()
+    out = torch.empty_like(c32)
+    lib.call("pulpo_philox4x32", _ptr(c32), _ptr(k32), _ptr(out), c32.shape[0], _stream())
+    return out
