@@ -533,6 +533,19 @@ int pulpo_conv3d_k3_fwd_wino3(const float* in, int64_t in_bs, int64_t in_ps, int
 int pulpo_conv3d_k3_dgrad_wino3_bnred(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* wp, float* out, int64_t out_bs,
                                       int64_t out_ps, const float* bn_y, int64_t bn_y_bs, int64_t bn_y_ps, const float* bn_coef, float slope, float* part,
                                       int B, int D, int H, int W, int K, int N, void* stream);
+/* The same F(2x2x2,3x3x3) convolution as 64 batched GEMMs in the transformed domain (added without a version bump), for the coarse pyramid
+ * levels whose extents are not whole 4x8x8 tiles (20^3, 10^3): an input transform writes V[64][rows][K] (one row per 2x2x2 output block, rows
+ * padded to 128), a batched MFMA GEMM forms M[p] = V[p] U[p] with U = the pack of pulpo_conv3d_k3_pack_weight_wino3 read as it is, an output
+ * transform stores the result through its strides with the bias and either the BatchNorm partials (stats: pulpo_conv3d_k3_stat_tiles() rows of
+ * 2 * N floats, every row written) or the eval-mode store (coef).  No atomics.  Takes even D, H, W, K % 8 == 0, N % 4 == 0 and any operand /
+ * result strides; scratch: pulpo_conv3d_k3_fwd_wino3g_scratch_floats() floats, 16-byte aligned, any content.  pulpo_conv3d_k3_wino3g_ok() = 1
+ * for the shapes the host routes here by default - fp32, pulpo_conv3d_k3_algo() == 2, N % 32 == 0, 125 .. 1000 output blocks,
+ * min(K, N) >= 128; pulpo_conv3d_k3_algo() keeps answering 2 for them (pulpo_conv3d_k3_fwd_wino2 still takes them). */
+int pulpo_conv3d_k3_wino3g_ok(int B, int D, int H, int W, int K, int N);
+size_t pulpo_conv3d_k3_fwd_wino3g_scratch_floats(int B, int D, int H, int W, int K, int N);
+int pulpo_conv3d_k3_fwd_wino3g(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* wp, const float* bias, const float* coef,
+                               float slope, float* out, int64_t out_bs, int64_t out_ps, int64_t out_cs, float* stats, float* scratch, int B, int D,
+                               int H, int W, int K, int N, void* stream);
 
 /* ------------------------------------------------------------------------- bf16 ACTIVATION STORAGE (BASELINE configs 4-5; since ABI 3)
  * No counterpart in the reference (fp32 throughout).  On top of the bf16-operand convolutions the multi-channel activation

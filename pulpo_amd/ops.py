@@ -420,10 +420,12 @@ def _pack_weight_now(w: torch.Tensor, dgrad: bool, shape=None, register: bool = 
     algo = lib.query("pulpo_conv3d_k3_algo", *shape, K, N) if shape is not None else 0
     if CONV_ALGO is not None and algo != 0:            # diagnostic override; only among the kernels valid for this shape
         algo = {"direct": 0, "wino2": 2, "wino3": algo}[CONV_ALGO]          # ("wino3": wherever the library's own policy picks it)
-    if algo == 3:
+    # the coarse levels' wide layers (20^3, 10^3 of the 160^3 pyramid): F(2x2x2,3x3x3) as batched GEMMs on the F(2x2x2) pack; forcing "wino2" keeps the (y, x) kernel
+    gemm = algo == 2 and CONV_ALGO in (None, "wino3") and bool(lib.query("pulpo_conv3d_k3_wino3g_ok", *shape, K, N))
+    if algo == 3 or gemm:
         wp = torch.empty(lib.query("pulpo_conv3d_k3_packed_wino3_floats", K, N), device=w.device, dtype=torch.float32)
         lib.call("pulpo_conv3d_k3_pack_weight_wino3", _ptr(w.contiguous()), _ptr(wp), Cin, Cout, int(dgrad), _stream())
-        wp._pulpo_algo = "wino3"
+        wp._pulpo_algo = "wino3g" if gemm else "wino3"
         if register:
             if w.is_contiguous():
                 _register_pack(w, wp, Cin, Cout, dgrad, 4)
@@ -482,6 +484,14 @@ def _conv_raw(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], o
         lib.call("pulpo_conv3d_k3_fwd_wino3", _ptr(x), xb, xp, xc, _ptr(wp), _ptr(bias), _ptr(coef), LRELU_SLOPE, _ptr(out), ob, op, oc, _ptr(stats),
                  B, D, H, W, K, N, _stream())
         _trace_end(t0, "conv3d_k3_wino3_mfma<false>", 54.0 * K * N * B * D * H * W, 4.0 * (K + N) * B * D * H * W)
+        return
+    if algo == "wino3g":
+        # F(2x2x2,3x3x3) as batched GEMMs: any operand / result strides; the transformed operand and the products live in a scratch
+        scratch = torch.empty(lib.query("pulpo_conv3d_k3_fwd_wino3g_scratch_floats", B, D, H, W, K, N), device=x.device, dtype=torch.float32)
+        t0 = _trace_begin()
+        lib.call("pulpo_conv3d_k3_fwd_wino3g", _ptr(x), xb, xp, xc, _ptr(wp), _ptr(bias), _ptr(coef), LRELU_SLOPE, _ptr(out), ob, op, oc, _ptr(stats),
+                 _ptr(scratch), B, D, H, W, K, N, _stream())
+        _trace_end(t0, f"conv3d_k3_wino3_gemm<{3 if N % 96 == 0 else 2}>", 54.0 * K * N * B * D * H * W, 4.0 * (K + N) * B * D * H * W)
         return
     if algo == "wino2":
         if (D % 4 or D * H * W < 8000) and not vec_ok:     # (volumes below 20^3 - the 10^3 level - run on the pipelined kernel only: channels-last operand)
