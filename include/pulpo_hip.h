@@ -268,6 +268,20 @@ int pulpo_mind_fwd(const float* y_true, const float* y_pred, const float* wa /*n
                    int H, int W, int d, float eps, void* stream);
 int pulpo_mind_bwd(const float* y_true, const float* y_pred, const float* wa /*nullable*/, const float* wb /*nullable*/, float* scratch /*12N*/,
                    const float* gscale, float coef, float* gpred, int B, int D, int H, int W, int d, float eps, void* stream);
+/* Mutual-information similarity term (Mattes; no counterpart in the reference): a cubic-B-spline Parzen joint histogram
+ *   P[a,c] = sum_v m_v beta3(u(pred_v) - a) beta3(u(true_v) - c),  u(v) = clamp(v,0,1) (K - 3) + 1,  K bins in [4, 64],  m = wa * wb (1 without),
+ *   p = P / sum P,  MI_b = sum p (log(p + 1e-12) - log(pa pb + 1e-12)),  loss = -gamma V mean_b MI_b  (MI_b = 0 where sum P = 0).
+ * Images planar fp32, B batch elements of V voxels each (volumes and slices alike: the term is pointwise), expected in [0,1].
+ * mi_fwd: scratch = pulpo_mi_scratch_floats(B,V,K) floats, one slab row per workgroup of the histogram kernel (pulpo_mi_blocks(B,V) rows
+ *   over the batch), uninitialised on entry; writes p (B K K), mi (B), G = d MI_b / d P (B K K) and the loss scalar.  No host read.
+ * mi_bwd: gpred = coef * gscale[0] * d(sum_b sum_ac G P)/d pred (gscale nullable = 1); the caller's coef is -gamma V / B.
+ * No atomics: bit-identical run to run, and a time that does not depend on the image content. */
+int pulpo_mi_blocks(int B, int64_t V);
+int64_t pulpo_mi_scratch_floats(int B, int64_t V, int K);
+int pulpo_mi_fwd(const float* y_true, const float* y_pred, const float* wa /*nullable*/, const float* wb /*nullable*/, float* scratch, double* p,
+                 double* mi, float* G, float* loss, int B, int64_t V, int K, double gamma, void* stream);
+int pulpo_mi_bwd(const float* y_true, const float* y_pred, const float* wa /*nullable*/, const float* wb /*nullable*/, const float* G,
+                 const float* gscale, float coef, float* gpred, int B, int64_t V, int K, void* stream);
 int pulpo_kl_fwd(const float* mu, const float* sigma, const float* mu1 /*nullable: 0*/, const float* sigma1 /*nullable: 1*/, int64_t n,
                  float* partial, void* stream);
 int pulpo_kl_bwd(const float* mu, const float* sigma, const float* mu1, const float* sigma1, const float* gscale, float coef, float* gmu,

@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 
-LOSSES = ("ncc", "mse", "mind")
+LOSSES = ("ncc", "mse", "mind", "mi")
 # Step size and iterations per level, coarsest first, of fit().  A float64 sweep of the fitter's definition on the CPU (DESIGN.md section 3m has
 # the table): lr in {0.003, 0.01, 0.03} x iterations {15/20/30, 30/40/60, 60/80/120} on one synthetic pair at 32^3 and 24x32x28, NCC and MSE.
 # Every setting with 130 iterations or more ends between 0.30 and 0.49 voxels of corner error, a spread one pair cannot resolve; halving the
@@ -26,6 +26,8 @@ LOSSES = ("ncc", "mse", "mind")
 DEFAULT_LR = 0.01
 DEFAULT_ITERS = (30, 40, 60)
 DEFAULT_WIN = (9, 7, 5)
+# Joint-histogram bins of the "mi" term per level, coarsest first: an 8^3 level has 512 voxels, too few for 32 x 32 joint bins
+DEFAULT_MI_BINS = (16, 16, 32)
 
 
 # ------------------------------------------------------------------------------------------------ helpers (tiny torch algebra, off the hot path)
@@ -143,7 +145,7 @@ def _per_level(given, default, levels: int):
 
 def fit(x: torch.Tensor, y: torch.Tensor, *, dof: int = 12, levels: int = 3, iters: Optional[Sequence[int]] = None, lr: float = DEFAULT_LR,
         loss: str = "ncc", win: Optional[Sequence[int]] = None, mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None,
-        theta0: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        theta0: Optional[torch.Tensor] = None, mi_bins=None) -> Dict[str, torch.Tensor]:
     """Fit the affine transform that brings the moving image x onto the fixed image y (both (B,1,D,H,W), or (B,1,H,W) slices, on one grid):
     minimise loss(ops.affine_warp(theta, x), y) over theta, coarse to fine.
 
@@ -153,8 +155,9 @@ def fit(x: torch.Tensor, y: torch.Tensor, *, dof: int = 12, levels: int = 3, ite
     iters     Adam iterations per level, coarsest first (default DEFAULT_ITERS, for another level count its last `levels` entries repeated
               as needed); lr the step size (DEFAULT_LR).  Adam starts from zero moments at every level.
     loss      "ncc" (window win[k] at the k-th level visited, default DEFAULT_WIN), "mse" or "mind" (3-D only, NotImplementedError on slices
-              as ops.mind_loss): the project's similarity terms, with gamma = 1 - sums over the level's voxels, so rows of history from
-              different levels are not on one scale.
+              as ops.mind_loss) or "mi" (mutual information, for pairs of different contrast; images in [0,1]): the project's similarity
+              terms, with gamma = 1 - sums over the level's voxels, so rows of history from different levels are not on one scale.
+    mi_bins   joint-histogram bins of "mi": an int, or one entry per level, coarsest first, like win (default DEFAULT_MI_BINS).
     mask_x / mask_y   weight volumes (B,1,...) of the moving / the fixed image: the masked forms of the terms.  mask_x is re-warped by the
               current transform every iteration, without gradient (ops.warp_mask(ops.affine_field(theta), mask_x)), as the training step
               re-warps it by the current field.
@@ -179,6 +182,9 @@ def fit(x: torch.Tensor, y: torch.Tensor, *, dof: int = 12, levels: int = 3, ite
     iters, win = _per_level(iters, DEFAULT_ITERS, levels), _per_level(win, DEFAULT_WIN, levels)
     if len(iters) != levels or len(win) != levels or min(iters) < 0:
         raise ValueError(f"affine.fit: iters and win need one entry per level ({levels}), coarsest first")
+    bins = _per_level((int(mi_bins),) * levels if isinstance(mi_bins, int) else mi_bins, DEFAULT_MI_BINS, levels)
+    if len(bins) != levels or not all(4 <= int(k) <= 64 for k in bins):
+        raise ValueError(f"affine.fit: mi_bins needs an int or one entry per level ({levels}), coarsest first, each in [4, 64]")
     nd = x.dim() - 2
     if loss == "mind" and nd == 2:
         ops.mind_loss(x, y)                              # (raises the project's NotImplementedError for slices before any work)
@@ -200,7 +206,7 @@ def fit(x: torch.Tensor, y: torch.Tensor, *, dof: int = 12, levels: int = 3, ite
         xl, yl, mxl, myl = pyr[lvl]
         theta = _theta_of(P, r0 / 2 ** lvl, dof, nd)
         wx = ops.warp_mask(ops.affine_field(theta, xl.shape[2:]), mxl) if mxl is not None else None
-        return ops.similarity(loss, ops.affine_warp(theta, xl), yl, wx, myl, gamma=1.0, win=int(win[k]))
+        return ops.similarity(loss, ops.affine_warp(theta, xl), yl, wx, myl, gamma=1.0, win=int(win[k]), bins=int(bins[k]))
 
     row = 0
     for k, lvl in enumerate(reversed(range(levels))):

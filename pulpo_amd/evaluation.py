@@ -32,6 +32,8 @@ MIND_METRICS = ("MIND",)
 SURFACE_METRICS = ("HD95", "ASSD")
 # the row level_scores adds with bending=True: the second-order smoothness of the field beside JDetStd
 BENDING_METRICS = ("BendingE",)
+# the row level_scores adds with mi=True: mutual information between the warped and the fixed image, higher is better
+MI_METRICS = ("MI",)
 
 
 def _zero(ref: torch.Tensor) -> torch.Tensor:
@@ -44,7 +46,7 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
                  num_classes: Optional[int] = None, final_dfs_inv: Optional[Dict[int, torch.Tensor]] = None,
                  mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
                  mind_eps: float = 1e-5, surface: bool = False, include_background: bool = False,
-                 bending: bool = False) -> Dict[str, Dict[int, torch.Tensor]]:
+                 bending: bool = False, mi: bool = False, mi_bins: int = 32) -> Dict[str, Dict[int, torch.Tensor]]:
     """The level losses of evaluate.py:1433-1474 for one pair: {metric: {level: 0-d device tensor}}.
 
     outputs[l], final_dfs[l]: the warped image and the final field of level l (predict_deterministic + combine_dfs); y: the fixed image.
@@ -78,7 +80,10 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
     class 0 is left out unless include_background; 0 when no class qualifies and at the other levels (PerformanceTable reads 0 as missing).
     bending=True (no counterpart in the reference) adds, beside the rows above, which do not change,
       BendingE[l]      mean over batch, components and interior voxels of the bending-energy density of final_dfs[l], in voxels^2
-                       = losses.Bending_reg(final_dfs[l], 1) / num_pixels_l; 0 for an affine field (every extent of a level at least 3)."""
+                       = losses.Bending_reg(final_dfs[l], 1) / num_pixels_l; 0 for an affine field (every extent of a level at least 3).
+    mi=True (no counterpart in the reference) adds, beside the rows above, which do not change,
+      MI[l]            mean over the batch of the mutual information of outputs[l] and the target over mi_bins x mi_bins Parzen bins
+                       (ops.joint_histogram; images in [0,1]); higher is better."""
     levels = sorted(outputs.keys())
     if sorted(final_dfs.keys()) != levels:
         raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs {sorted(final_dfs.keys())}")
@@ -113,6 +118,12 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
             size = tuple(outputs[l].shape[2:])
             target = y if size == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
             res["MIND"][l] = ops.mind_loss(outputs[l], target, mind_dilation, mind_eps) / float(np.prod(size))
+    if mi:
+        res["MI"] = {}
+        for l in levels:
+            size = tuple(outputs[l].shape[2:])
+            target = y if size == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
+            res["MI"][l] = ops.joint_histogram(outputs[l], target, mi_bins)[1].mean().float()
     if bending:
         res["BendingE"] = {l: ops.bending_reg(final_dfs[l], 1.0) / float(np.prod(final_dfs[l].shape[2:])) for l in levels}
     if seg_x is not None:
@@ -162,14 +173,16 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
                 num_classes: Optional[int] = None, inverse: bool = False, mask_x: Optional[torch.Tensor] = None,
                 mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
                 mind_eps: float = 1e-5, refine: Optional[Dict[str, object]] = None, surface: bool = False,
-                include_background: bool = False, affine=None, bending: bool = False) -> Dict[str, Dict[int, torch.Tensor]]:
+                include_background: bool = False, affine=None, bending: bool = False, mi: bool = False,
+                mi_bins: int = 32) -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
     unless the samplers are pinned (network_blocks.FixedNoiseSampler).  inverse=True also integrates the inverse fields
     (model.combine_dfs_bidirectional: one integration call per level for both directions) and adds the INVERSE_METRICS rows; mask_x / mask_y
     add the MASK_METRICS rows, mind=True the MIND_METRICS row, surface=True (with segmentations) the SURFACE_METRICS rows, bending=True the
-    BENDING_METRICS row (of the refined and of the affine-composed fields where those are scored, like JDetStd).  refine (a dict of pulpo_amd.refine.refine's keyword arguments, {} for its
+    BENDING_METRICS row (of the refined and of the affine-composed fields where those are scored, like JDetStd), mi=True the MI_METRICS row
+    over mi_bins bins.  refine (a dict of pulpo_amd.refine.refine's keyword arguments, {} for its
     defaults; no counterpart in the reference): the same rows for the fields of model.refine(x, y, **refine) instead of the prediction's
     (DESIGN.md section 3k); the masks given here score, they reach the refinement only through the dict.
     affine (no counterpart in the reference): None - the pair is taken as affinely aligned, today's path; a (B,3,4)
@@ -202,7 +215,7 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
         final_dfs = {l: ops.affine_compose(theta, df, x.shape[2:]) for l, df in final_dfs.items()}
     return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv,
                         mask_x=mask_x, mask_y=mask_y, mind=mind, mind_dilation=mind_dilation, mind_eps=mind_eps,
-                        surface=surface, include_background=include_background, bending=bending)
+                        surface=surface, include_background=include_background, bending=bending, mi=mi, mi_bins=mi_bins)
 
 
 @torch.no_grad()

@@ -112,6 +112,19 @@ def MIND_loss_masked(y_pred: torch.Tensor, y_true: torch.Tensor, mask: torch.Ten
     return ops.mind_loss_masked(y_pred, y_true, mask, mask2, dilation, eps)
 
 
+def MI_loss(y_pred: torch.Tensor, y_true: torch.Tensor, bins: int = 32, gamma: float = 0.05) -> torch.Tensor:
+    """-gamma * V * mean_batch(MI): Mattes mutual information over a bins x bins cubic-B-spline Parzen joint histogram of images in [0,1]
+    (values outside are clamped), on NCC_loss's scale.  Volumes (B,1,D,H,W) or slices (B,1,H,W)"""
+    return ops.mi_loss(y_pred, y_true, bins, gamma)
+
+
+def MI_loss_masked(y_pred: torch.Tensor, y_true: torch.Tensor, mask: torch.Tensor, mask2: Optional[torch.Tensor] = None, bins: int = 32,
+                   gamma: float = 0.05) -> torch.Tensor:
+    """MI_loss with cost-function masking: every voxel enters the joint histogram with the weight m = mask * mask2, and the histogram is
+    normalised by sum(m); 0 for an empty mask (DESIGN.md sections 3i, 3r)"""
+    return ops.mi_loss_masked(y_pred, y_true, mask, mask2, bins, gamma)
+
+
 def L2_reg(deformation_field: torch.Tensor, lamb=0) -> torch.Tensor:
     """lamb * H*W*D * mean of squared forward differences over the [1:,1:,1:] block"""
     if deformation_field.dim() not in (4, 5):
@@ -178,6 +191,8 @@ class HierarchicalKLLoss(nn.Module):
 class HierarchicalReconstructionLoss(nn.Module):
     """sum_l w_l * recon(y_hat_l, y resized to level l) / len(recon_loss)   (losses.py:279-325)"""
 
+    mi_bins = 32        # joint-histogram bins of the "mi" term; set on the instance to change them (model.hierarchical_recon_loss.mi_bins = 16)
+
     def __init__(self, recon_loss: List[str], weight_dict: Dict[int, float], similarity_pyramid: bool, ndims: int, window_size: Dict[int, float],
                  mind_dilation: int = 2, mind_eps: float = 1e-5) -> None:
         super().__init__()
@@ -192,10 +207,10 @@ class HierarchicalReconstructionLoss(nn.Module):
                 masks: Optional[Dict[int, Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]] = None,
                 dice_terms: Optional[Dict[int, torch.Tensor]] = None):
         """masks (not in the reference): {level: (mask_a, mask_b)}, weight volumes at the level's size, either of a pair may be None; a level
-        with a pair uses the masked NCC / MSE / MIND term (cost weighted by mask_a * mask_b), the Dice term is unchanged.
+        with a pair uses the masked NCC / MSE / MIND / MI term (cost weighted by mask_a * mask_b), the Dice term is unchanged.
         dice_terms (not in the reference): {level: the level's Dice term}, computed by the caller (PULPo.label_dice_terms, from label maps);
         dice_terms[l] stands in for Soft_dice_loss(y_hat_seg[l], ...), and y_hat_seg / seg_y are not read"""
-        single = len(self.recon_loss) == 1 and self.recon_loss[0] in ("mse", "ncc", "dice", "mind")
+        single = len(self.recon_loss) == 1 and self.recon_loss[0] in ("mse", "ncc", "dice", "mind", "mi")
         loss = 0.0
         all_levels, terms = {}, {}
         for l, w in self.weight_dict.items():
@@ -203,13 +218,13 @@ class HierarchicalReconstructionLoss(nn.Module):
             # F.interpolate(y, size) of the reference; the identity resize at full resolution is skipped
             y_target = y if tuple(size) == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
             ma, mb = (masks.get(l) if masks is not None else None) or (None, None)
-            how = dict(win=self.window_size[l], gamma=gamma, dilation=self.mind_dilation, eps=self.mind_eps)
+            how = dict(win=self.window_size[l], gamma=gamma, dilation=self.mind_dilation, eps=self.mind_eps, bins=self.mi_bins)
             if single and self.recon_loss[0] != "dice":
                 # one term per level (the default, ["ncc"]): weighting and summation of all levels in one launch; x / 1 is x
                 terms[l] = ops.similarity(self.recon_loss[0], y_hat[l], y_target, ma, mb, **how)
                 continue
             term = 0.0
-            for kind in ("mse", "ncc", "mind"):
+            for kind in ("mse", "ncc", "mind", "mi"):
                 if kind in self.recon_loss:
                     term = term + w * ops.similarity(kind, y_hat[l], y_target, ma, mb, **how)
             if "dice" in self.recon_loss and dice_terms is not None:

@@ -2162,6 +2162,97 @@ def mind_loss_masked(pred, true, mask, mask2=None, dilation: int = 2, eps: float
     return _Mind.apply(pred, true.detach(), wa, wb, dilation, eps)[0]
 
 
+# ---- Mutual information: Mattes MI over a cubic-B-spline Parzen joint histogram of K bins, images expected in [0,1].
+# loss = -gamma V mean_b MI_b: NCC_loss's scale.  Pointwise, so slices run as depth-1 volumes.
+def _mi_args(name: str, pred, true, bins):
+    for t in (pred, true):
+        if t.dim() not in (4, 5) or t.shape[1] != 1:
+            raise PulpoHipError(f"{name}: single-channel volumes (B,1,D,H,W) or slices (B,1,H,W) expected, got {tuple(t.shape)}")
+    if pred.shape != true.shape:
+        raise ValueError(f"{name}: pred {tuple(pred.shape)} and true {tuple(true.shape)} differ in shape")
+    bins = int(bins)
+    if not 4 <= bins <= 64:
+        raise ValueError(f"{name}: bins must be in [4, 64], got {bins}")
+    return bins
+
+
+def _mi_forward(pred, true, wa, wb, bins: int, gamma: float):
+    """(loss, p, MI, G) of planar device images; the slab is scratch of this call"""
+    B = pred.shape[0]
+    V = pred.numel() // B
+    dev = pred.device
+    slab = torch.empty(lib.query("pulpo_mi_scratch_floats", B, V, bins), device=dev, dtype=torch.float32)
+    p = torch.empty((B, bins, bins), device=dev, dtype=torch.float64)
+    mi = torch.empty(B, device=dev, dtype=torch.float64)
+    G = torch.empty((B, bins, bins), device=dev, dtype=torch.float32)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    nmask = (wa is not None) + (wb is not None)
+    t0 = _hbm_begin("mi_fwd")
+    lib.call("pulpo_mi_fwd", _ptr(true), _ptr(pred), _ptr(wa), _ptr(wb), _ptr(slab), _ptr(p), _ptr(mi), _ptr(G), _ptr(loss), B, V, bins, float(gamma),
+             _stream())
+    _hbm_end(t0, "mi_fwd", 4.0 * (2 + nmask) * B * V)                     # 2 images (+ masks) in; the slab and the tables are noise beside them
+    return loss, p, mi, G
+
+
+class _MI(torch.autograd.Function):
+    """the loss scalar, masked (wa given) or not: the masks enter the joint histogram, whose own sum normalises it"""
+
+    @staticmethod
+    def forward(ctx, pred, true, wa, wb, bins: int, gamma: float):
+        _require_gpu(pred, true, wa, wb)
+        pred, true = planar(pred), planar(true)
+        loss, _, _, G = _mi_forward(pred, true, wa, wb, bins, gamma)
+        ctx.bins, ctx.gamma = bins, gamma
+        ctx.save_for_backward(pred, true, wa, wb, G)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, true, wa, wb, G = ctx.saved_tensors
+        B = pred.shape[0]
+        V = pred.numel() // B
+        gpred = torch.empty_like(pred)
+        nmask = (wa is not None) + (wb is not None)
+        t0 = _hbm_begin("mi_bwd")
+        lib.call("pulpo_mi_bwd", _ptr(true), _ptr(pred), _ptr(wa), _ptr(wb), _ptr(G), _ptr(g.contiguous()), -ctx.gamma * V / B, _ptr(gpred), B, V,
+                 ctx.bins, _stream())
+        _hbm_end(t0, "mi_bwd", 4.0 * (3 + nmask) * B * V)                 # 2 images (+ masks) in, the gradient out
+        return gpred, None, None, None, None, None
+
+
+def mi_loss(pred, true, bins: int = 32, gamma: float = 0.05):
+    """-gamma V mean_b MI_b, MI_b the Mattes mutual information of pred_b and true_b over a bins x bins cubic-B-spline Parzen histogram
+    (images in [0,1], values outside are clamped).  Volumes or slices.  Gradient to pred only."""
+    bins = _mi_args("mi_loss", pred, true, bins)
+    if _is2d(pred):
+        pred, true = _lift(pred), _lift(true)
+    return _MI.apply(pred, true.detach(), None, None, bins, float(gamma))
+
+
+def mi_loss_masked(pred, true, mask, mask2=None, bins: int = 32, gamma: float = 0.05):
+    """mi_loss with every voxel's histogram weight multiplied by m = mask * mask2 ((B,1,...) weights in [0,1]); the histogram is normalised
+    by M = sum(m), V stays the voxel count; 0 with a zero gradient for an empty mask.  Gradient to pred only."""
+    bins = _mi_args("mi_loss_masked", pred, true, bins)
+    wa, wb = _masks_of(pred, mask, mask2, "mi_loss_masked")
+    if _is2d(pred):
+        pred, true = _lift(pred), _lift(true)
+    return _MI.apply(pred, true.detach(), wa, wb, bins, float(gamma))
+
+
+def joint_histogram(a, b, bins: int = 32, mask=None, mask2=None):
+    """(p (B,K,K) float64, MI (B,) float64): the normalised Parzen joint histogram of a (rows) and b (columns) and its mutual information
+    per batch element, as mi_loss forms them.  No gradient."""
+    bins = _mi_args("joint_histogram", a, b, bins)
+    if mask is None:
+        mask, mask2 = mask2, None
+    wa, wb = _masks_of(a, mask, mask2, "joint_histogram") if mask is not None else (None, None)
+    if _is2d(a):
+        a, b = _lift(a), _lift(b)
+    _require_gpu(a, b, wa, wb)
+    _, p, mi, _ = _mi_forward(planar(a.detach()), planar(b.detach()), wa, wb, bins, 0.0)
+    return p, mi
+
+
 class _KL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, sigma, mu1, sigma1):
@@ -2395,13 +2486,15 @@ def rmse_masked(inp, target, mask, mask2=None):
     return fin[0], fin[2].detach()
 
 
-SIMILARITY_TERMS = ("ncc", "mse", "mind")
+SIMILARITY_TERMS = ("ncc", "mse", "mind", "mi")
 
 
-def similarity(kind: str, pred, true, mask=None, mask2=None, *, win: int = 9, gamma: float = 0.05, dilation: int = 2, eps: float = 1e-5):
+def similarity(kind: str, pred, true, mask=None, mask2=None, *, win: int = 9, gamma: float = 0.05, dilation: int = 2, eps: float = 1e-5,
+               bins: int = 32):
     """the similarity term `kind` between pred and true: the one place that maps (term, masks) to an operator.  No mask: ncc_loss (window win,
-    factor gamma) / l2_loss / mind_loss (dilation, eps; gamma does not apply: on MSE's scale already); with either mask of the pair, in either
-    argument: the masked form, cost weighted by mask * mask2.  An unknown kind raises ValueError before anything touches the device."""
+    factor gamma) / l2_loss / mind_loss (dilation, eps; gamma does not apply: on MSE's scale already) / mi_loss (bins, factor gamma as for
+    NCC); with either mask of the pair, in either argument: the masked form, cost weighted by mask * mask2.  An unknown kind raises
+    ValueError before anything touches the device."""
     if kind not in SIMILARITY_TERMS:
         raise ValueError(f"similarity: term {kind!r} - one of {SIMILARITY_TERMS} expected")
     if mask is None:
@@ -2410,6 +2503,8 @@ def similarity(kind: str, pred, true, mask=None, mask2=None, *, win: int = 9, ga
         return ncc_loss(pred, true, win, gamma) if mask is None else ncc_loss_masked(pred, true, mask, mask2, win, gamma)
     if kind == "mse":
         return l2_loss(pred, true) if mask is None else l2_loss_masked(pred, true, mask, mask2)
+    if kind == "mi":
+        return mi_loss(pred, true, bins, gamma) if mask is None else mi_loss_masked(pred, true, mask, mask2, bins, gamma)
     return mind_loss(pred, true, dilation, eps) if mask is None else mind_loss_masked(pred, true, mask, mask2, dilation, eps)
 
 

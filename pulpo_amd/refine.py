@@ -17,7 +17,7 @@ import torch
 from . import ops
 from .losses import HierarchicalReconstructionLoss
 
-RECON_TERMS = ("ncc", "mse", "mind")
+RECON_TERMS = ("ncc", "mse", "mind", "mi")
 # The step size of refine(): the best objective after 50 iterations among lr in {0.01, 0.03, 0.1, 0.3} whose history has no rise larger than
 # 1 % of the total drop, from the prediction and from zero fields, on synthetic.oasis_like_pair at 160^3 / T5 / L4 with an untrained model
 # (scripts/refine_bench.py, profiles/refine_bench.txt: 0.1 ends lower but rises by 39 % of the drop on the way from zero fields)
@@ -72,6 +72,8 @@ class Objective:
         self.recon = ref if recon_loss is None else HierarchicalReconstructionLoss(
             recon_loss=recon, weight_dict=dict(ref.weight_dict), similarity_pyramid=False, ndims=ref.ndims, window_size=ref.window_size,
             mind_dilation=ref.mind_dilation, mind_eps=ref.mind_eps)
+        if self.recon is not ref:
+            self.recon.mi_bins = ref.mi_bins          # (an attribute, not a constructor argument: the bins of the model's "mi" term)
         self.decoders = model.autoencoder.decoders
         with torch.no_grad():
             self.level_x = model.autoencoder.level_images(x)
@@ -121,7 +123,7 @@ def refine(model, x: torch.Tensor, y: torch.Tensor, *, individual_dfs: Optional[
     posterior samples, drawn one at a time, whose unbiased per-voxel variance is the anchor's var (1 in the other two cases).  The network
     runs once, without gradients, in the caller's mode (call model.eval() first, as for any prediction: in training mode a forward pass
     moves the BatchNorm statistics).
-    similarity    HierarchicalReconstructionLoss with the model's weight table, windows and MIND hyper-parameters over `recon_loss`
+    similarity    HierarchicalReconstructionLoss with the model's weight table, windows, MIND hyper-parameters and mi_bins over `recon_loss`
                   (None: the model's list; e.g. ["mind"] refines a model trained with NCC across contrasts; "dice" raises ValueError),
                   gamma (None: the model's).  mask_x / mask_y (weight volumes (B,1,...) at full resolution) switch the masked terms on,
                   whatever the model's `mask` hyper-parameter; mask_x is re-warped by the current field every iteration, without gradient.
