@@ -565,7 +565,8 @@ int pulpo_conv3d_k3_fwd_wino3g(const float* in, int64_t in_bs, int64_t in_ps, in
  * No counterpart in the reference (fp32 throughout).  On top of the bf16-operand convolutions the multi-channel activation
  * tensors of a ConvUnit - the pre-norm output y (src/network_blocks.py:23), the output z (:25), pooled / concatenated / up-sampled feature
  * maps (components/pulpo.py:58, 195-206, 250) - and their gradients may live in HBM as bf16: every kernel below computes in fp32 and
- * rounds to nearest even on the store; BatchNorm statistics describe the tensor AS STORED.  These are the typed forms of the entry points
+ * rounds to nearest even on the store; BatchNorm statistics describe the tensor AS STORED, and so do the conv-bias gradient rows (partial2) of
+ * the second BatchNorm-backward pass: the column sums of the dy it stores.  These are the typed forms of the entry points
  * above: activation operands are `void*` with a dtype code (0 = fp32, 1 = bf16), strides in ELEMENTS, everything else (coefficients,
  * partial sums, planar fields, parameters) stays fp32; with code 0 they are the fp32 entry points.  The convolution and weight-gradient
  * kernels take operand and result in ONE storage type (dt). */
@@ -578,6 +579,17 @@ int pulpo_conv3d_k3_fwd_bn_lrelu_bf16_t(const void* in, int64_t in_bs, int64_t i
 int pulpo_conv3d_k3_wgrad_bf16_t(const void* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const void* dy, int64_t dy_bs, int64_t dy_ps,
                                  int64_t dy_cs, int dt, float* dw, int accumulate, float* scratch, int B, int D, int H, int W, int Cin, int Cout,
                                  void* stream);
+/* Which kernel the two launchers above pick (read-only queries, added without a version bump), for 16-byte-aligned channels-last operands
+ * (channel stride 1, batch stride = D*H*W * voxel stride) with the given voxel strides in elements:
+ *  - forward (also the fused eval-mode store and the data gradient, which are the same entry with another pack): 0 the staged kernel on
+ *    2x8x8 tiles, 1 the staged kernel on 4x8x8 tiles (D % 4 == 0 and at least 40^3 voxels), 2 the persistent pw<1,9> (32-cout tiles),
+ *    3 the persistent pw<2,3> (64-cout tiles); + 16 with split-K (pulpo_conv3d_k3_fwd_bf16_scratch_floats() > 0).  The persistent kernel
+ *    takes dt = 1, whole 4x8x8 tiles, K % 32 == 0, whole cout tiles, voxel strides in 16-byte pieces and tensors below 2 GB per batch element.
+ *  - weight gradient: ntw (1, 2, 4 or 7 row tiles per wave) + 16 tr (transposing LDS reads, Cin % 16 == 0) + 32 pf (register-prefetched
+ *    staging: tr, dt = 1, channels and voxel strides in 16-byte pieces, H % 8 == 0, W % 8 == 0, tensors below 2 GB per batch element).
+ * -1 for a bad argument. */
+int pulpo_conv3d_k3_fwd_bf16_kernel(int B, int D, int H, int W, int K, int N, int dt, int64_t in_ps, int64_t out_ps);
+int pulpo_conv3d_k3_wgrad_bf16_kernel(int B, int D, int H, int W, int Cin, int Cout, int dt, int64_t in_ps, int64_t dy_ps);
 int pulpo_bn_lrelu_apply_t(const void* y, int y_dt, int64_t yps, void* z, int z_dt, int64_t zps, const float* coef, int64_t npix, int C, float slope,
                            void* stream);
 int pulpo_bn_lrelu_apply_pool2_t(const void* y, int y_dt, int64_t yps, void* z /* nullable since ABI 4: only the pooled tensor is written */, int z_dt, int64_t zps,

@@ -915,6 +915,32 @@ int launch_bf16_pw(const ConvArgsH& a, long nwork, hipStream_t st) {
     return pulpo::check_launch("conv3d_k3_mfma_bf16_pw");
 }
 
+// Which kernel a forward call runs, from its shape, storage type and voxel strides alone (the launcher ANDs in what only it can see: unit
+// channel strides, batch strides in 16-byte pieces, 16-byte-aligned pointers).  0 / 1: the staged kernel on 2x8x8 / 4x8x8 tiles; 2 / 3: the
+// persistent pw<1,9> / pw<2,3> - bf16-stored activations in 16-byte pieces, whole 32-channel chunks, whole 4 x 8 x 8 tiles, whole cout tiles;
+// + 16 with split-K.
+int conv_fwd_bf16_route(int B, int D, int H, int W, int K, int N, int dt, int64_t in_ps, int64_t out_ps) {
+    const int tz = conv_tz(D, H, W), NT = nt_for(N);
+    const int ksplit = conv_ksplit_bf16(B, D, H, W, K, N);
+    const bool pw_ok = dt == 1 && in_ps % 8 == 0 && tz == 4 && ksplit == 1 && K % CH == 0 && N % NT == 0 && D % 4 == 0 && H % TY == 0 &&
+                       W % TX == 0 && (long)D * H * W * in_ps * 2 < (1L << 31) && (long)D * H * W * out_ps * 2 < (1L << 31) && out_ps % 8 == 0;
+    return (pw_ok ? (NT == 64 ? 3 : 2) : (tz == 4 ? 1 : 0)) + (ksplit > 1 ? 16 : 0);
+}
+
+// Which weight-gradient kernel a call runs, likewise: ntw (1, 2, 4 or 7 row tiles per wave) + 16 tr + 32 pf.
+//   tr: transposing LDS reads where every 16-lane group's rows are 16 channels of one tap (else the 2-byte gathers)
+//   pf: register-prefetched staging (else the staged form): bf16 tensors in 16-byte pieces below 2 GB, tiles whole in x / y
+int wgrad_bf16_route(int B, int D, int H, int W, int Cin, int Cout, int dt, int64_t in_ps, int64_t dy_ps) {
+    (void)B;
+    const int nrt_max = (27 * std::min(Cin, CH) + 31) / 32;
+    const int n4 = (nrt_max + 3) / 4;
+    const int ntw = n4 <= 1 ? 1 : n4 <= 2 ? 2 : n4 <= 4 ? 4 : 7;
+    const bool tr = Cin % 16 == 0;
+    const bool pf = tr && dt == 1 && in_ps % 8 == 0 && dy_ps % 8 == 0 && Cin % 8 == 0 && Cout % 8 == 0 && H % TY == 0 && W % TX == 0 &&
+                    (long)D * H * W * in_ps * 2 < (1L << 31) && (long)D * H * W * dy_ps * 2 < (1L << 31);
+    return ntw + (tr ? 16 : 0) + (pf ? 32 : 0);
+}
+
 }  // namespace
 
 // ================================================================================================ C ABI
@@ -970,12 +996,11 @@ static int conv_fwd_bf16_impl(const void* in, int64_t in_bs, int64_t in_ps, int6
                           "conv3d_k3_fwd_bf16: bf16 channels-last output must be 4-byte aligned with even strides");
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    // the persistent kernel: bf16-stored activations in 16-byte pieces, whole 32-channel chunks, whole 4 x 8 x 8 tiles, whole cout tiles.
-    // On the 32- and the 64-cout tiles alike: measured on one MI355X with the persistent kernel on neither / the 32-cout tiles only / both,
-    // config 4 step 61.7 / 65.4 / 67.3 pairs/s, config 5 step 38.1 / 40.4 / 41.6, config 4 inference 190 / 211 / 222.
-    const bool pw_ok = dt == 1 && vec && tz == 4 && a.ksplit == 1 && K % CH == 0 && N % NT == 0 && D % 4 == 0 && H % TY == 0 && W % TX == 0 &&
-                       (long)D * H * W * in_ps * 2 < (1L << 31) && out_cs == 1 && (long)D * H * W * out_ps * 2 < (1L << 31) &&
-                       out_ps % 8 == 0 && out_bs % 8 == 0 && (((uintptr_t)out & 15) == 0);
+    // the persistent kernel (conv_fwd_bf16_route).  On the 32- and the 64-cout tiles alike: measured on one MI355X with the persistent kernel
+    // on neither / the 32-cout tiles only / both, config 4 step 61.7 / 65.4 / 67.3 pairs/s, config 5 step 38.1 / 40.4 / 41.6, config 4
+    // inference 190 / 211 / 222.
+    const bool pw_ok = ((conv_fwd_bf16_route(B, D, H, W, K, N, dt, in_ps, out_ps) & 15) >= 2) && vec && out_cs == 1 && out_bs % 8 == 0 &&
+                       (((uintptr_t)out & 15) == 0);
     if (pw_ok) return NT == 64 ? launch_bf16_pw<2, 3>(a, nblk_l, st) : launch_bf16_pw<1, 9>(a, nblk_l, st);
 #define PULPO_BF16(NTV, VECV, TT) (tz == 4 ? launch_bf16<NTV, VECV, 4, TT>(a, nblk, st) : launch_bf16<NTV, VECV, 2, TT>(a, nblk, st))
 #define PULPO_BF16_T(TT)                                                                          \
@@ -1062,15 +1087,12 @@ static int wgrad_bf16_impl(const void* in, int64_t in_bs, int64_t in_ps, int64_t
     const int g = dt ? 8 : 4;             // channels per 16-byte piece
     const bool vec = (in_cs == 1) && (in_ps % g == 0) && (in_bs % g == 0) && (Cin % g == 0) && (((uintptr_t)in & 15) == 0) &&
                      (dy_cs == 1) && (dy_ps % g == 0) && (dy_bs % g == 0) && (Cout % g == 0) && (((uintptr_t)dy & 15) == 0);
-    const int nrt_max = (27 * std::min(Cin, CH) + 31) / 32;
-    const int ntw = (nrt_max + 3) / 4;
+    const int route = wgrad_bf16_route(B, D, H, W, Cin, Cout, dt, in_ps, dy_ps);
+    const int ntw = route & 15;
     constexpr size_t lds = (size_t)(WHV + WMV) * CP * sizeof(uint16_t);
     const int nblk = npair * a.nsplit;
-    // transposing LDS reads where every 16-lane group's rows are 16 channels of one tap (else the 2-byte gathers)
-    const bool tr = Cin % 16 == 0;
-    // register-prefetched staging (else the staged form): bf16 tensors in 16-byte pieces below 2 GB, tiles whole in x / y
-    const bool pf = tr && dt == 1 && vec && H % TY == 0 && W % TX == 0 && (long)D * H * W * in_ps * 2 < (1L << 31) &&
-                    (long)D * H * W * dy_ps * 2 < (1L << 31);
+    const bool tr = (route & 16) != 0;
+    const bool pf = (route & 32) != 0 && vec;
 #define PULPO_WGRAD_H(NTWV, VECV, TT)                                                                                             \
     do {                                                                                                                            \
         if constexpr (VECV && sizeof(TT) == 2) {                                                                                    \
@@ -1110,6 +1132,17 @@ PULPO_API int pulpo_conv3d_k3_wgrad_bf16_det_t(const void* in, int64_t in_bs, in
                                                int nslab, int B, int D, int H, int W, int Cin, int Cout, void* stream) {
     PULPO_REQUIRE(slabs && nslab >= 1, "conv3d_k3_wgrad_bf16_det: slabs of nslab >= 1 copies of the packed scratch required");
     return wgrad_bf16_impl(in, in_bs, in_ps, in_cs, dy, dy_bs, dy_ps, dy_cs, dt, dw, accumulate, scratch, slabs, nslab, B, D, H, W, Cin, Cout, stream);
+}
+
+// the kernel selection of the two launchers above for 16-byte-aligned channels-last operands (see conv_fwd_bf16_route / wgrad_bf16_route)
+PULPO_API int pulpo_conv3d_k3_fwd_bf16_kernel(int B, int D, int H, int W, int K, int N, int dt, int64_t in_ps, int64_t out_ps) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || K <= 0 || N <= 0 || (dt != 0 && dt != 1)) return -1;
+    return conv_fwd_bf16_route(B, D, H, W, K, N, dt, in_ps, out_ps);
+}
+
+PULPO_API int pulpo_conv3d_k3_wgrad_bf16_kernel(int B, int D, int H, int W, int Cin, int Cout, int dt, int64_t in_ps, int64_t dy_ps) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (dt != 0 && dt != 1)) return -1;
+    return wgrad_bf16_route(B, D, H, W, Cin, Cout, dt, in_ps, dy_ps);
 }
 
 PULPO_API int pulpo_conv3d_k3_wgrad_bf16(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* dy, int64_t dy_bs,

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_bwd_reduce_kernel(const TG* __re
     }
 }
 
-// pass 2: dy = scale * (dbn - mean(dbn) - xhat * mean(dbn*xhat));  partial2[blk][c] = sum dy  (conv-bias gradient)
+// pass 2: dy = scale * (dbn - mean(dbn) - xhat * mean(dbn*xhat));  partial2[blk][c] = sum dy AS STORED  (conv-bias gradient)
 // Per element in fp32 as  dy = A*dbn + B*(y - m32) + C  with per-channel constants formed in double from the exact means:
 //   A = scale,  B = -scale * c2 * rstd,  C = -scale * (c1 + c2 * rstd * (m32 - mean)),  C carried as a (hi, lo) pair of floats.
 // A mean rounded to fp32 would shift every dy of the channel by the same amount, an error that the following weight-gradient sum
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_bwd_apply_kernel(const TG* __res
                 Vec<VEC>::ld(kst + 5 * C + cl, clo);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
-                    o[k] = (g[k] + v[k]) + clo[k];
+                    o[k] = pulpo::as_stored<TY>((g[k] + v[k]) + clo[k]);     // (the bias-gradient rows sum dy as stored: what the convolution's backward reads)
                     s0[k] += o[k];
                 }
             }

@@ -2,7 +2,7 @@
 softplus, cumsum, index_select, grid_sample) so that they also run on the GPU at the pyramid's sizes, and the element-wise comparison the
 pyramid tests use.  tests/test_oracle_golden.py pins every helper to oracle/pulpo_oracle.py and torch.nn.functional at small shapes;
 tests/test_gpu_pyramid_ops.py, tests/test_gpu_pyramid_convunit.py and tests/test_gpu_vecint.py (the VecInt helpers and field generators) hold
-the HIP kernels to them."""
+the HIP kernels to them; tests/test_gpu_bf16_storage.py holds the bf16-storing kernels to the ROUNDED reference (held_bf16, at the end)."""
 from typing import Optional, Sequence
 
 import torch
@@ -389,3 +389,88 @@ def perturbed(ref, index: int, rel: float = 1e-3):
     bad = ref.detach().clone(memory_format=torch.contiguous_format)
     bad.view(-1)[index] += rel * float(ref.detach().abs().max())
     return bad
+
+
+# ------------------------------------------------------------------------------------------------ bf16-stored results
+BF16_MIN_EXP = -133                     # log2 of the bf16 subnormal spacing (the smallest binade's ulp)
+
+
+def bf16_grid(r):
+    """(ulp, q) of a float64 tensor on the bf16 grid: ulp = the spacing of bf16 values in r's binade (8 significant bits; the subnormal
+    spacing below 2^-126), q = |r| / ulp: 128 <= q < 256 for normal values.  Both exact: the powers of two are assembled from their exponent
+    bits (torch.ldexp multiplies by pow(2, n), which a GPU's pow may round) and q is a product with one"""
+    a = r.abs()
+    e = ((a.view(torch.int64) >> 52) - 1022 - 8).clamp_min(BF16_MIN_EXP)          # frexp's exponent of |r|, less the 8 significant bits
+    ulp = ((e + 1023) << 52).view(torch.float64)
+    return ulp, a * ((1023 - e) << 52).view(torch.float64)
+
+
+def rne_bf16(r):
+    """a float64 tensor rounded to the nearest bf16 value, ties to even, in ONE rounding (r.float().bfloat16() rounds twice), as float64"""
+    ulp, q = bf16_grid(r)
+    fl = torch.floor(q)
+    frac = q - fl                                            # (exact: q has at most 53 - 8 fraction bits)
+    up = (frac > 0.5) | ((frac == 0.5) & (torch.remainder(fl, 2) == 1))       # half to even, spelled out; 255.5 -> 256: the next binade's first value
+    return torch.sign(r) * (fl + up) * ulp
+
+
+def bf16_midpoint_distance(r):
+    """distance from r to the nearest midpoint between two adjacent bf16 values.  Inside a binade the midpoints are (k + 1/2) ulp; just above
+    a power of two the midpoint below it belongs to the finer binade underneath, (128 - 1/4) ulp.  0 for r = 0 (its neighbours' midpoints
+    are 2^-134 away)"""
+    ulp, q = bf16_grid(r)
+    fl = torch.floor(q)
+    d = (q - (fl + 0.5)).abs()
+    d = torch.where(fl == 128, torch.minimum(d, q - 127.75), d)
+    return torch.where(r == 0, torch.zeros_like(r), d * ulp)
+
+
+def judge_bf16(got, ref, T, exempt=None):
+    """the two rules a bf16-storing kernel is held to (its fp32 value v obeys |v - ref| <= T and it stores RNE_bf16(v)):
+      1. got is finite and |got - ref| <= T + 2^-8 (|ref| + T): half a bf16 ulp at the far end of the interval;
+      2. where ref lies farther than T from every midpoint between adjacent bf16 values (or T = 0: the arithmetic is exact, ties included),
+         v rounds as ref does: got == RNE_bf16(ref) bit for bit (int16 views; +0 and -0 count as equal).
+    exempt: elements taken out of rule 2 on top (bool).  Returns (rule-1 ratio, covered mask, mismatch mask among the covered)"""
+    assert got.dtype == torch.bfloat16 and ref.dtype == torch.float64 and got.shape == ref.shape
+    T = T if isinstance(T, torch.Tensor) else torch.full_like(ref, float(T))
+    r1 = ratio(got, ref, T + 2.0 ** -8 * (ref.abs() + T) + 1e-300)
+    covered = (bf16_midpoint_distance(ref) > T) | (T == 0)
+    if exempt is not None:
+        covered &= ~exempt
+    want = rne_bf16(ref).to(torch.bfloat16)
+    g = got.contiguous()
+    same = (g.view(torch.int16) == want.view(torch.int16)) | ((g == 0) & (want == 0))
+    return r1, covered, covered & ~same
+
+
+def held_bf16(name, got, ref, T, cap, power=None, exempt=None):
+    """judge_bf16 asserted.  Prints RATIO (rule 1) and NEARMID (the share of elements outside rule 2), asserts that share <= cap, and shows
+    power: ref with ONE element moved by one bf16 ulp of that element must be rejected.  power: the channel of the last voxel of the last
+    batch element to move (default: the last one that rule 2 covers in the interior of its binade - one must exist)"""
+    r1, covered, bad = judge_bf16(got, ref, T, exempt)
+    share = 1.0 - float(covered.double().mean())
+    print(f"RATIO {name} {r1:.3g}")
+    print(f"NEARMID {name} {share:.4g}")
+    if bool(bad.any()):
+        i = int(bad.reshape(-1).to(torch.int8).argmax())
+        idx = []
+        for n in reversed(ref.shape):
+            idx.append(i % n)
+            i //= n
+        idx = tuple(reversed(idx))
+        print(f"WORST {name} first of {int(bad.sum())} bit mismatches at {idx} of {tuple(ref.shape)}: got {float(got[idx])!r} ref {float(ref[idx])!r}")
+    assert r1 <= 1.0, f"{name}: rule 1, max error / (T + 2^-8 (|ref| + T)) = {r1:.3g}"
+    assert not bool(bad.any()), f"{name}: rule 2, {int(bad.sum())} of {int(covered.sum())} covered elements are not RNE_bf16(ref)"
+    assert share <= cap, f"{name}: {share:.4g} of the elements lie within T of a bf16 midpoint (cap {cap}): the inputs leave rule 2 too little to check"
+    last = (ref.shape[0] - 1, slice(None)) + tuple(n - 1 for n in ref.shape[2:])
+    _, q = bf16_grid(ref[last])
+    if power is None:
+        ok = covered[last] & (q >= 130) & (q <= 253)
+        assert bool(ok.any()), f"{name}: no channel of the last voxel is covered by rule 2"
+        power = int(ok.nonzero()[-1])
+    assert bool(covered[last][power]), f"{name}: power channel {power} is not covered by rule 2"
+    moved = ref.detach().clone(memory_format=torch.contiguous_format)
+    at = (ref.shape[0] - 1, power) + tuple(n - 1 for n in ref.shape[2:])
+    moved[at] += bf16_grid(ref[at])[0]
+    r1m, _, badm = judge_bf16(got, moved, T, exempt)
+    assert r1m > 1.0 or bool(badm.any()), f"{name}: a one-ulp error in channel {power} of the last voxel is not rejected"

@@ -1258,7 +1258,8 @@ def _bf(t):
 
 
 @pytest.mark.parametrize("Cin,Cout,size,pool", [(32, 32, (16, 16, 16), False), (16, 96, (8, 16, 16), True), (3, 32, (12, 8, 16), False), (40, 24, (9, 7, 10), True),
-                                                # from 64^3 up with whole 32-channel chunks: the persistent kernel (one chunk; two / three chunks and three cout tiles)
+                                                # whole 4x8x8 tiles from 40^3 voxels up with whole 32-channel chunks: the persistent kernel (one chunk; two chunks and three cout
+                                                # tiles); per kernel and per element: tests/test_gpu_bf16_storage.py
                                                 (32, 32, (64, 72, 64), False), (64, 96, (64, 64, 64), True)])
 def test_bf16_storage_conv_unit_vs_definition(ops, Cin, Cout, size, pool):
     """One ConvUnit with bf16 ACTIVATION STORAGE (ops.ACT_BF16, BASELINE configs 4-5) against the oracle's definition (O.ACT_PRECISION:
