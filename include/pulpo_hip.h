@@ -547,6 +547,12 @@ int pulpo_conv3d_k3_fwd_wino3(const float* in, int64_t in_bs, int64_t in_ps, int
 int pulpo_conv3d_k3_dgrad_wino3_bnred(const float* in, int64_t in_bs, int64_t in_ps, int64_t in_cs, const float* wp, float* out, int64_t out_bs,
                                       int64_t out_ps, const float* bn_y, int64_t bn_y_bs, int64_t bn_y_ps, const float* bn_coef, float slope, float* part,
                                       int B, int D, int H, int W, int K, int N, void* stream);
+/* Which form of a kernel a channel pair runs (read-only, added without a version bump; the launchers decide through it).  kind 0: the forward /
+ * data-gradient F(2x2x2,3x3x3) entries above with K reduction and N output channels - 1: the 16-column form on v_mfma_f32_16x16x4_f32 (N == 16:
+ * the feedback layers' data gradient), 0: 32-wide cout tiles.  kind 1: the F(2x2x2,3x3x3) weight gradient (pulpo_conv3d_k3_wgrad_algo() == 3) with
+ * K = Cin, N = Cout - 1: the workgroups of the last ci tile run the 16-input-channel form (Cin % 32 == 16), 0: 32-channel tiles only.  Same packs,
+ * same operands, same results to fp32 rounding.  Other kinds: 0. */
+int pulpo_conv3d_k3_narrow16(int kind, int K, int N);
 /* The same F(2x2x2,3x3x3) convolution as 64 batched GEMMs in the transformed domain (added without a version bump), for the coarse pyramid
  * levels whose extents are not whole 4x8x8 tiles (20^3, 10^3): an input transform writes V[64][rows][K] (one row per 2x2x2 output block, rows
  * padded to 128), a batched MFMA GEMM forms M[p] = V[p] U[p] with U = the pack of pulpo_conv3d_k3_pack_weight_wino3 read as it is, an output

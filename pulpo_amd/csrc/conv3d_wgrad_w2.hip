@@ -23,10 +23,13 @@
 #include "conv_shared.h"
 #include <type_traits>
 
+PULPO_API int pulpo_conv3d_k3_narrow16(int kind, int K, int N);      // (conv3d_wino3.hip)
+
 namespace {
 
 using namespace pulpo_conv;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int W2G_VROW = 44, W2G_EROW = 36;                       // floats per (px, slot, channel) row
 constexpr int W2G_VSLOT = 32 * W2G_VROW, W2G_ESLOT = 32 * W2G_EROW; // floats per (px, slot)
@@ -44,6 +47,7 @@ struct Wgrad2Args {
     int nty, ntx, ncit, ncot, nsplit;
     long split_stride;            // 0, or (deterministic mode) floats between the per-split copies of dwp (see WgradArgs in conv3d_wgrad.hip)
     long in_kb;                   // F(2x2x2) kernel: the same block stride for the INPUT operand (8 = channels-last)
+    int narrow_last;              // F(2x2x2) kernel: the last ci tile holds 16 channels and runs the 16x16x4 form (pulpo_conv3d_k3_narrow16(1, ..))
     long go_kb;                   // F(2x2x2) kernel: floats between consecutive 8-channel blocks of a gradient voxel - 8 = channels-last, B * V * 8 (go_ps = 8) = the
                                   // channel-blocked layout [Cout / 8][B][D][H][W][8] of pulpo_bn_lrelu_bwd_apply_kb_t
 };
@@ -591,14 +595,27 @@ constexpr size_t W3G_LDS = (size_t)(W2G_VX + W3G_EX) * sizeof(float);     // 163
 
 // SG: the group of a half step behind whose first MFMAs a wave starts transforming / writing the fetched planes (groups SG, SG + 1; the next planes'
 // loads are issued in group SG + 1)
-template <int SG>
+// NARROW: a ci tile of 16 input channels (the feedback layers' 16 -> 96, or the last tile of Cin = 32 n + 16).  The accumulator rows are input
+// channels: on 32x32x2 instructions half of them would be zero rows of V.  This form multiplies on v_mfma_f32_16x16x4_f32 instead - 16 ci x 16 co
+// tiles, two per 32-wide cout tile, half the matrix clocks - with lane l = (channel i = l % 16, k slot kk = l / 16): block row yb = 2 g + kk / 2,
+// blocks xb = 2 (kk % 2), + 1 are the lane's two k steps, read as EIGHT bytes of its V row and of its two E rows (co i and 16 + i).  Only the 16
+// real channel rows are staged and x-transformed (160 staging items instead of 320) into an input ring of half the size; slots, cadence and
+// barriers are the wide form's, and the LDS the 16 rows leave free stays unused: a workgroup learns its form from its ci tile, both forms run in
+// ONE launch with one LDS size, and a deeper ring would need a second staging cadence for this form only.
+template <int SG, bool NARROW>
 __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    // NARROW: 16 input-channel rows per (px, slot) - half the input ring; the gradient ring follows it directly and 44 KB stay unused (a deeper
+    // ring would need a staging cadence of its own for this form).  Both slot pitches carry one more 8-byte column: the pitch is then neither below
+    // 2 KB nor a multiple of 512 bytes and the compiler cannot fuse two ds_read_b64 of different slots into ds_read2st64_b64, which runs at half
+    // the rate and - banked on 32 dwords in groups of 16 lanes - with a two-way conflict on these rows.
+    constexpr int VSL = NARROW ? 16 * W2G_VROW + 2 : W2G_VSLOT, ESL = NARROW ? W2G_ESLOT + 2 : W2G_ESLOT;
+    static_assert(!NARROW || ((VSL * 4) % 512 != 0 && VSL * 4 > 2040 && (ESL * 4) % 512 != 0 && ESL * 4 > 2040 && (16 * VSL + 16 * ESL) * 4 <= (int)W3G_LDS), "slot pitch");
     float* VX = smem;
-    float* EX = smem + W2G_VX;
+    float* EX = smem + (NARROW ? 16 * VSL : W2G_VX);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31, kk = lane >> 5;
+    const int i = NARROW ? lane & 15 : lane & 31, kk = NARROW ? lane >> 4 : lane >> 5;
     const int py = wave & 3, pxh = wave >> 2;             // this wave's points: (py, px = 2 pxh, 2 pxh + 1)
     const int lid = pulpo::xcd_remap(blockIdx.x, gridDim.x);
     const int npair = a.ncit * a.ncot;
@@ -622,8 +639,9 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
 
     // ---- staging items of this thread (column-invariant geometry)
     // X plane: items (hy 0..9, channel quad q 0..7, xb 0..3) = 320 of 512 threads; four x taps (gx = x0 - 1 + 2 xb + t) of four channels
-    const bool x_item = tid < 320;
-    const int x_q = tid & 7, x_xb = (tid >> 3) & 3, x_hy = tid >> 5;
+    // (NARROW: channel quads 0..3 only = 160 threads)
+    const bool x_item = NARROW ? tid < 160 : tid < 320;
+    const int x_q = NARROW ? tid & 3 : tid & 7, x_xb = NARROW ? (tid >> 2) & 3 : (tid >> 3) & 3, x_hy = NARROW ? tid >> 4 : tid >> 5;
     // dY plane: items (y 0..7, channel quad q, xb) = 256 threads (the upper half: threads 256..511, so that the two kinds of item are spread)
     const bool e_item = tid >= 256;
     const int e_t = tid - 256;
@@ -634,6 +652,8 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
     // banks groups - a 4-way conflict on every staging write (SQ_LDS_BANK_CONFLICT: 36 % of the LDS cycles).  Permuted, the eight rows of
     // an instruction are 8 consecutive rows (all residues mod 8: conflict-free) and every ds_read_b128 lane group still covers all 16 residues
     // of its sixteen-byte slots.
+    // (NARROW: channel c = 4 q + k of the 16 lives in row 4 k + q - the four rows of a staging instruction are consecutive, at most three of its
+    //  lanes share a bank, which a ds_write_b32 absorbs; any 16 consecutive rows of 11 slots give a ds_read_b64 group 16 different slots)
     float* const x_dst = VX + x_q * W2G_VROW + x_hy * 4 + x_xb;                // + (px * 4 + slot) * VSLOT + perm-row offsets below
     float* const e_dst = EX + e_q * W2G_EROW + e_y * 4 + e_xb;                 // + (px * 4 + slot) * ESLOT + ...
     const int x_d4 = ((x_q ^ 4) - x_q) * W2G_VROW, e_d4 = ((e_q ^ 4) - e_q) * W2G_EROW;    // rows of channels 4 q + 2, 4 q + 3: 16 / 24 + (q ^ 4)
@@ -699,8 +719,9 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
             const f32x2 sg = px == 1 ? f32x2{1.f, 1.f} : f32x2{-1.f, -1.f};
             const f32x2 lo = f32x2{pa_.x, pa_.y} + sg * f32x2{pb_.x, pb_.y}, hi = f32x2{pa_.z, pa_.w} + sg * f32x2{pb_.z, pb_.w};
             const float4 v = make_float4(lo.x, lo.y, hi.x, hi.y);
-            float* o = x_dst + (px * 4 + slot) * W2G_VSLOT;
-            o[0] = v.x; o[8 * W2G_VROW] = v.y; o[16 * W2G_VROW + x_d4] = v.z; o[24 * W2G_VROW + x_d4] = v.w;
+            float* o = x_dst + (px * 4 + slot) * VSL;
+            if constexpr (NARROW) { o[0] = v.x; o[4 * W2G_VROW] = v.y; o[8 * W2G_VROW] = v.z; o[12 * W2G_VROW] = v.w; }
+            else { o[0] = v.x; o[8 * W2G_VROW] = v.y; o[16 * W2G_VROW + x_d4] = v.z; o[24 * W2G_VROW + x_d4] = v.w; }
         }
     };
     auto write_e = [&](int px, int slot) {
@@ -714,7 +735,7 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
                 const f32x2 lo = f32x2{d0.x, d0.y} + sg * f32x2{d1.x, d1.y}, hi = f32x2{d0.z, d0.w} + sg * f32x2{d1.z, d1.w};
                 v = make_float4(lo.x, lo.y, hi.x, hi.y);
             }
-            float* o = e_dst + (px * 4 + slot) * W2G_ESLOT;
+            float* o = e_dst + (px * 4 + slot) * ESL;
             o[0] = v.x; o[8 * W2G_EROW] = v.y; o[16 * W2G_EROW + e_d4] = v.z; o[24 * W2G_EROW + e_d4] = v.w;
         }
     };
@@ -726,20 +747,27 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
         for (int t2 = 0; t2 < 2; ++t2) asm volatile("" : : "v"(er[t2].x), "v"(er[t2].y), "v"(er[t2].z), "v"(er[t2].w));
     };
 
-    f32x16 acc[2][4];                                     // [px of this wave][pz]
+    constexpr int NH = NARROW ? 2 : 1, NR = NARROW ? 4 : 16;     // accumulator tiles per point (NARROW: the two 16-wide halves of the cout tile), registers of one
+    std::conditional_t<NARROW, f32x4, f32x16> acc[2][4][NH];      // [px of this wave][pz][cout half]
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int pz = 0; pz < 4; ++pz)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[p][pz][r] = 0.f;
+            for (int nh = 0; nh < NH; ++nh)
+#pragma unroll
+                for (int r = 0; r < NR; ++r) acc[p][pz][nh][r] = 0.f;
 
     // operand row addresses of this lane (floats): + (px * 4 + slot) * VSLOT + g * 16 for V, + (px * 4 + slot) * ESLOT + g * 16 for E (gradient plane q in slot q & 3)
     // (block row yb = 2 g + kk: V rows hy = 2 yb + ta / tb, E rows y = 2 yb, 2 yb + 1; four floats per row; input plane p sits in slot (p + 1) & 3)
     const int irow = 8 * (i & 3) + ((i >> 2) ^ (4 * ((i >> 1) & 1)));            // perm(i): the row of this lane's channel
-    const float* va = VX + irow * W2G_VROW + (2 * kk + ta) * 4;
-    const float* vb = VX + irow * W2G_VROW + (2 * kk + tb) * 4;
-    const float* ea = EX + irow * W2G_EROW + (2 * kk) * 4;
+    // (NARROW: block row 2 g + kk / 2, blocks 2 (kk % 2), + 1 of it; the E row of the cout tile's second half, channel 16 + i, is row irow ^ 4)
+    const int krow = NARROW ? 2 * (kk >> 1) : 2 * kk, kcol = NARROW ? 2 * (kk & 1) : 0;
+    const int vrow = NARROW ? 4 * (i & 3) + (i >> 2) : irow;
+    const float* va = VX + vrow * W2G_VROW + (krow + ta) * 4 + kcol;
+    const float* vb = VX + vrow * W2G_VROW + (krow + tb) * 4 + kcol;
+    const float* ea = EX + irow * W2G_EROW + krow * 4 + kcol;
+    const int e_hi = ((irow ^ 4) - irow) * W2G_EROW;
 
     // ---- main loop: column segments of pair steps [Js, Je) of this split's range, i.e. half steps h = 2 Js .. 2 Je - 1, each segment entered
     // through three warm-up half steps (stage only).  Half step h: barrier; its 32 MFMAs; the registers (input plane h + 2, gradient plane
@@ -777,15 +805,32 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
 #pragma unroll
             for (int gi = 0; gi < 4; ++gi) {
                 const int g = gi >> 1, px = 2 * pxh + (gi & 1), pl = gi & 1;
-                const float* eb0 = ea + (px * 4 + d0s) * W2G_ESLOT + g * 16;
-                const float* eb1 = ea + (px * 4 + d1s) * W2G_ESLOT + g * 16;
-                e0[0] = *reinterpret_cast<const float4*>(eb0 + 4 * ea_); e1[0] = *reinterpret_cast<const float4*>(eb0 + 4 * eb_);
-                e0[1] = *reinterpret_cast<const float4*>(eb1 + 4 * ea_); e1[1] = *reinterpret_cast<const float4*>(eb1 + 4 * eb_);
+                const float* eb0 = ea + (px * 4 + d0s) * ESL + g * 16;
+                const float* eb1 = ea + (px * 4 + d1s) * ESL + g * 16;
+                if constexpr (NARROW) {
+                    // E .xy: this lane's two blocks of cout i, .zw: of cout 16 + i; V: its two blocks in .xy (P[.][1], VA[1], VB[1] fold away)
+                    auto two = [&](const float* p_) {
+                        const float2 lo = *reinterpret_cast<const float2*>(p_), hi = *reinterpret_cast<const float2*>(p_ + e_hi);
+                        return make_float4(lo.x, lo.y, hi.x, hi.y);
+                    };
+                    e0[0] = two(eb0 + 4 * ea_); e1[0] = two(eb0 + 4 * eb_);
+                    e0[1] = two(eb1 + 4 * ea_); e1[1] = two(eb1 + 4 * eb_);
 #pragma unroll
-                for (int dz = 0; dz < 3; ++dz) {
-                    const int off = (px * 4 + ((HM + dz) & 3)) * W2G_VSLOT + g * 16;
-                    av[dz] = *reinterpret_cast<const float4*>(va + off);
-                    bv[dz] = *reinterpret_cast<const float4*>(vb + off);
+                    for (int dz = 0; dz < 3; ++dz) {
+                        const int off = (px * 4 + ((HM + dz) & 3)) * VSL + g * 16;
+                        const float2 a2 = *reinterpret_cast<const float2*>(va + off), b2 = *reinterpret_cast<const float2*>(vb + off);
+                        av[dz] = make_float4(a2.x, a2.y, 0.f, 0.f);
+                        bv[dz] = make_float4(b2.x, b2.y, 0.f, 0.f);
+                    }
+                } else {
+                    e0[0] = *reinterpret_cast<const float4*>(eb0 + 4 * ea_); e1[0] = *reinterpret_cast<const float4*>(eb0 + 4 * eb_);
+                    e0[1] = *reinterpret_cast<const float4*>(eb1 + 4 * ea_); e1[1] = *reinterpret_cast<const float4*>(eb1 + 4 * eb_);
+#pragma unroll
+                    for (int dz = 0; dz < 3; ++dz) {
+                        const int off = (px * 4 + ((HM + dz) & 3)) * VSL + g * 16;
+                        av[dz] = *reinterpret_cast<const float4*>(va + off);
+                        bv[dz] = *reinterpret_cast<const float4*>(vb + off);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // y combinations of the three input planes and the two gradient planes, then the z combinations (two-wide vector arithmetic)
@@ -814,8 +859,14 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
                 constexpr int PZA = HB ? 2 : 0, PZB = HB ? 3 : 1;
 #pragma unroll
                 for (int s_ = 0; s_ < 4; ++s_) {
-                    acc[pl][PZA] = __builtin_amdgcn_mfma_f32_32x32x2f32(va4[s_], ea4[s_], acc[pl][PZA], 0, 0, 0);
-                    acc[pl][PZB] = __builtin_amdgcn_mfma_f32_32x32x2f32(vb4[s_], eb4[s_], acc[pl][PZB], 0, 0, 0);
+                    if constexpr (NARROW) {               // step s_ = (k step ks, cout half nh): four instructions between two on one accumulator
+                        const int nh = s_ & 1, ks = s_ >> 1;
+                        acc[pl][PZA][nh] = __builtin_amdgcn_mfma_f32_16x16x4f32(va4[ks], ea4[2 * nh + ks], acc[pl][PZA][nh], 0, 0, 0);
+                        acc[pl][PZB][nh] = __builtin_amdgcn_mfma_f32_16x16x4f32(vb4[ks], eb4[2 * nh + ks], acc[pl][PZB][nh], 0, 0, 0);
+                    } else {
+                        acc[pl][PZA][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(va4[s_], ea4[s_], acc[pl][PZA][0], 0, 0, 0);
+                        acc[pl][PZB][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vb4[s_], eb4[s_], acc[pl][PZB][0], 0, 0, 0);
+                    }
                     if (s_ == 0 && gi >= SG && gi < SG + 2) {
                         // the planes fetched during the previous half step are transformed and written behind the group's first MFMAs; their
                         // registers are then free and the next planes are requested.  (All four points in ONE group - 30 instead of 24 of the half
@@ -859,29 +910,33 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
     __syncthreads();
     float* X = smem;
     const int Cc = min(32, a.Cin - ci0);
+    constexpr int XR = NH * NR;                           // rows of a wave's X piece: accumulator registers per point
+    // (NARROW: accumulator register r of cout half nh in lane l is input channel 4 (l / 16) + r, cout nh * 16 + l % 16; X row rr = nh * 4 + r)
 #pragma unroll 1
     for (int dz = 0; dz < 3; ++dz) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float h0 = 0.5f * (acc[0][1][r] + acc[0][2][r]), h1 = 0.5f * (acc[1][1][r] + acc[1][2][r]);
-            const float m0 = dz == 0 ? acc[0][0][r] + h0 : dz == 1 ? 0.5f * (acc[0][1][r] - acc[0][2][r]) : h0 + acc[0][3][r];
-            const float m1 = dz == 0 ? acc[1][0][r] + h1 : dz == 1 ? 0.5f * (acc[1][1][r] - acc[1][2][r]) : h1 + acc[1][3][r];
+        for (int rr = 0; rr < XR; ++rr) {
+            const int nh = rr / NR, r = rr % NR;
+            const float h0 = 0.5f * (acc[0][1][nh][r] + acc[0][2][nh][r]), h1 = 0.5f * (acc[1][1][nh][r] + acc[1][2][nh][r]);
+            const float m0 = dz == 0 ? acc[0][0][nh][r] + h0 : dz == 1 ? 0.5f * (acc[0][1][nh][r] - acc[0][2][nh][r]) : h0 + acc[0][3][nh][r];
+            const float m1 = dz == 0 ? acc[1][0][nh][r] + h1 : dz == 1 ? 0.5f * (acc[1][1][nh][r] - acc[1][2][nh][r]) : h1 + acc[1][3][nh][r];
             float t0, t1, t2;                             // kx = 0, 1, 2 from px = 2 pxh (m0), 2 pxh + 1 (m1)
             if (pxh == 0) { t0 = m0 + 0.5f * m1; t1 = 0.5f * m1; t2 = 0.5f * m1; }               // px 0: G = (1,0,0); px 1: (.5,.5,.5)
             else { t0 = 0.5f * m0; t1 = -0.5f * m0; t2 = 0.5f * m0 + m1; }                          // px 2: (.5,-.5,.5); px 3: (0,0,1)
-            X[((wave * 3 + 0) * 16 + r) * 64 + lane] = t0;
-            X[((wave * 3 + 1) * 16 + r) * 64 + lane] = t1;
-            X[((wave * 3 + 2) * 16 + r) * 64 + lane] = t2;
+            X[((wave * 3 + 0) * XR + rr) * 64 + lane] = t0;
+            X[((wave * 3 + 1) * XR + rr) * 64 + lane] = t1;
+            X[((wave * 3 + 2) * XR + rr) * 64 + lane] = t2;
         }
         __syncthreads();
-        // 3 kx x 16 r x 64 lanes = 3072 entries, 6 per thread; each yields the three ky taps
-        for (int e = tid; e < 3 * 16 * 64; e += 512) {
-            const int l = e & 63, r = (e >> 6) & 15, kx = e >> 10;
+        // 3 kx x 16 r x 64 lanes = 3072 entries, 6 per thread (NARROW: 8 rows, 1536 entries, 3 per thread); each yields the three ky taps
+        for (int e = tid; e < 3 * XR * 64; e += 512) {
+            const int l = e & 63, r = (e >> 6) % XR, kx = e / (64 * XR);
             float s[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q)                   // py = q: waves q (px half 0) and q + 4 (px half 1)
-                s[q] = X[((q * 3 + kx) * 16 + r) * 64 + l] + X[(((q + 4) * 3 + kx) * 16 + r) * 64 + l];
-            const int ci = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), co = co0 + (l & 31);
+                s[q] = X[((q * 3 + kx) * XR + r) * 64 + l] + X[(((q + 4) * 3 + kx) * XR + r) * 64 + l];
+            const int ci = NARROW ? 4 * (l >> 4) + (r & 3) : (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
+            const int co = NARROW ? co0 + 16 * (r >> 2) + (l & 15) : co0 + (l & 31);
             if (ci < Cc && co < a.Cout) {
                 const float hs = 0.5f * (s[1] + s[2]);
                 float* d = a.dwp + (long)split * a.split_stride + ((long)((dz * 3 + 0) * 3 + kx) * a.Cin + ci0 + ci) * a.NPad + co;
@@ -897,10 +952,19 @@ __device__ __forceinline__ void wgrad_w3x_body(const Wgrad2Args& a) {
 
 // Two copies of the body that differ in ONE constant (as conv3d_k3_wino3_mfma, conv3d_wino3.hip): waves 0-3 stage behind groups 0 / 1 of a half
 // step, their SIMD partners 4-7 behind groups 2 / 3 - one wave's staging arithmetic and LDS writes fall into the other's matrix instructions.
+// ... and each in the 16-channel form for the workgroups of a 16-wide last ci tile (Wgrad2Args::narrow_last): one more workgroup-uniform branch
+// at the top, nothing joins behind it.
 template <int DUMMY>
 __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_w3x(Wgrad2Args a) {
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 8) != 0) wgrad_w3x_body<2>(a);
-    else wgrad_w3x_body<0>(a);
+    const int pair = pulpo::xcd_remap(blockIdx.x, gridDim.x) % (a.ncit * a.ncot);
+    const bool narrow = a.narrow_last != 0 && pair / a.ncot == a.ncit - 1;
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 8) != 0) {
+        if (narrow) wgrad_w3x_body<2, true>(a);
+        else wgrad_w3x_body<2, false>(a);
+    } else {
+        if (narrow) wgrad_w3x_body<0, true>(a);
+        else wgrad_w3x_body<0, false>(a);
+    }
 }
 
 }  // namespace
@@ -944,6 +1008,7 @@ int launch_wgrad_w2(const float* in, long in_bs, long in_ps, const float* go, lo
     a.B = B; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.NPad = npad(Cout);
     a.nty = pulpo::cdiv(H, 8); a.ntx = pulpo::cdiv(W, 8);
     a.ncit = pulpo::cdiv(Cin, 32); a.ncot = pulpo::cdiv(Cout, 32);
+    a.narrow_last = pulpo_conv3d_k3_narrow16(1, Cin, Cout);           // (read by the F(2x2x2,3x3x3) kernel only)
     const int npair = a.ncit * a.ncot;
     const long nstep = (long)B * a.nty * a.ntx * D;
     int nsplit = wgrad_w2_splits(npair, nstep, max_workgroups);       // (default: one workgroup per CU)

@@ -32,6 +32,7 @@ namespace {
 
 using namespace pulpo_conv;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int Q_CH = 8, Q_NT = 32;
 constexpr int Q_PL = HY * 4;                     // rows of one px slice of a plane: (hy, x-pair)
@@ -48,8 +49,19 @@ constexpr size_t Q_LDS = (size_t)(2 * Q_IMG + Q_TAB + Q_R + Q_RED + Q_PART) * si
 static_assert(Q_LDS <= 160 * 1024, "one workgroup per CU");
 
 
+// one point row of the packed weights in a lane's registers: four reduction channels of one output channel (32-wide tile), two in the 16-wide form
+__device__ __forceinline__ void unpack_w(const float4& w, float (&v)[4]) { v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w; }
+__device__ __forceinline__ void unpack_w(const float2& w, float (&v)[4]) { v[0] = w.x; v[1] = w.y; v[2] = 0.f; v[3] = 0.f; }
+
 // SP: the pair of a chunk behind whose first MFMAs a wave transforms and stores its staging item (SP) and requests the next taps (SP + 1)
-template <bool BNR, int SP>
+// N16: the 16-output-channel form (the feedback layers' data gradient, 96 -> 16).  Same tile, chunks, staging, images and barriers; the products
+// run on v_mfma_f32_16x16x4_f32 - two per k quad, one per 16-row half of the tile, against a 16-column weight operand - instead of
+// 32x32x2 instructions whose upper 16 columns multiply the pack's zero padding: half the matrix clocks.  Lane l = (row i = l % 16, k slot
+// kk = l / 16) holds reduction channels 2 kk, 2 kk + 1 of the chunk: it reads EIGHT bytes of row i of each half where the wide form reads
+// sixteen of one row (same LDS bytes, the image as store_item writes it), and eight bytes of a weight row.  Accumulators 8 x 2 x 4 registers
+// instead of 8 x 16: the room goes to an exchange buffer pass that carries BOTH output z parities at once (16 channels: 2 x 32 KB = the
+// buffer), i.e. one barrier pair less per tile, and every thread finishes one voxel pair.
+template <bool BNR, int SP, bool N16>
 __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
     constexpr int CH = Q_CH, NT = Q_NT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -59,8 +71,10 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
     float* const part = red + Q_RED;                    // [8 waves][64 lanes][8]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31, kk = lane >> 5;
-    const int py = wave & 3, pzh = wave >> 2;
+    const int i = N16 ? lane & 15 : lane & 31, kk = N16 ? lane >> 4 : lane >> 5;
+    // (N16: wave >> 2 is the copy of the body the wave runs, i.e. SP / 2 - as a constant it takes the issue-priority branches out of the matrix loop:
+    //  behind a wave-uniform branch every wait for a load is for ALL loads, the taps just requested included)
+    const int py = wave & 3, pzh = N16 ? SP / 2 : wave >> 2;
     const int nchunk = a.Cin / CH;                      // (host: >= 2)
     const int nwork = a.B * a.ntz * a.nty * a.ntx * a.ncot;
     const int nwg = gridDim.x;
@@ -91,9 +105,15 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
     const int zu = (pzh == 0 ? 0 : 2) * Q_PLROWS * 4, zv = (pzh == 0 ? 1 : 3) * Q_PLROWS * 4, zw = (pzh == 0 ? 2 : 1) * Q_PLROWS * 4;
     const float bw = pzh == 0 ? 1.f : -1.f;
     // MFMA row i = block (zb = i >> 4, yb = (i >> 2) & 3, xb = i & 3): halo plane 2 zb + (0..3), halo row 2 yb + (0..3)
-    const int lrow = (i >> 4) * 2 * Q_PLROWS + ((i >> 2) & 3) * 8 + (i & 3);
-    const int pa_off = (kk * Q_QROWS + lrow + ta * 4) * 4;
-    const int pb_off = (kk * Q_QROWS + lrow + tb * 4) * 4;
+    // N16: the tile's 32 rows split into halves by yb / 2, row i of a half = block (zb = i >> 3, yb = 2 half + ((i >> 2) & 1), xb = i & 3): the 16
+    // rows of a half then start in 16 different sixteen-byte bank slots (xb + 4 zb + 8 (yb & 1)) and the 32 lanes of a ds_read_b64 group - 16 rows x
+    // the two channel pairs of a quad - cover the 64 banks once (halves by zb: rows of yb and yb + 2 share a slot, every read two-way conflicted,
+    // measured 0.265 against 0.240 ms for the 32-wide form at 96 -> 16 / 80^3).  Channel quad kk / 2, channel pair kk % 2 of row i; the second half
+    // lies A_HALF floats on.
+    const int lrow = N16 ? (i >> 3) * 2 * Q_PLROWS + ((i >> 2) & 1) * 8 + (i & 3) : (i >> 4) * 2 * Q_PLROWS + ((i >> 2) & 3) * 8 + (i & 3);
+    const int pa_off = N16 ? ((kk >> 1) * Q_QROWS + lrow + ta * 4) * 4 + 2 * (kk & 1) : (kk * Q_QROWS + lrow + ta * 4) * 4;
+    const int pb_off = N16 ? ((kk >> 1) * Q_QROWS + lrow + tb * 4) * 4 + 2 * (kk & 1) : (kk * Q_QROWS + lrow + tb * 4) * 4;
+    constexpr int A_HALF = 2 * 8 * 4;
 
     constexpr unsigned OOB = 0x80000000u;
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wp), 0, -1, 0x00020000);
@@ -161,9 +181,12 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
     };
     const unsigned w_chunk_stride = 64u * CH * a.NPad * 4u;     // bytes between consecutive chunks
     const unsigned w_pt_stride = (unsigned)CH * a.NPad * 4u;    // bytes between consecutive points (px fastest, then py, then pz)
-    const int wl_off = (i * CH + 4 * kk) * 4;                   // this lane's 16 bytes inside a point's [32 n][8 k] piece
+    const int wl_off = N16 ? (i * CH + 2 * kk) * 4 : (i * CH + 4 * kk) * 4;     // this lane's 16 (N16: 8) bytes inside a point's [32 n][8 k] piece
+    using wrow_t = std::conditional_t<N16, float2, float4>;
     auto load_w = [&](unsigned wofs, int s) {                   // point step s = pz_local * 4 + px
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wl_off, (int)(wofs + ((s >> 2) * 16 + (s & 3)) * w_pt_stride), 0));
+        const int so = (int)(wofs + ((s >> 2) * 16 + (s & 3)) * w_pt_stride);
+        if constexpr (N16) return __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(w_rsrc, wl_off, so, 0));
+        else return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wl_off, so, 0));
     };
 
     // ---- per-channel constants of the epilogue, once per workgroup
@@ -183,7 +206,13 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
     Tile cur = describe(work);
     int cb = 0;                                         // image being read
     // ---- prologue: chunk 0 of the first tile staged, chunk 1 requested; the first weight rows
-    float4 wr[2][2];                                    // ring of two pairs of point rows: pair pp uses wr[pp & 1], which then takes pair pp + 2
+    // N16: a ring of FOUR pairs - a row is re-loaded for the same pair of the NEXT chunk - and the taps are requested in the pair that stores the
+    // staging item, not the one after.  Loads return in order: the wait for a weight row requested behind the taps is a wait for the taps.  With
+    // 32-clock matrix instructions two pairs are 1000 clocks of the SIMD, less than a trip to HBM under load; a whole chunk is the 2000 clocks the
+    // 32-wide form gives them (reasoned from the wait counts in the ISA, not measured on its own: the build it replaced also read through flat
+    // loads).  Eight more registers.
+    constexpr int WRING = N16 ? 4 : 2;
+    wrow_t wr[WRING][2];                                // ring of two pairs of point rows: pair pp uses wr[pp & 1], which then takes pair pp + 2 (N16: see above)
     {
         const __amdgpu_buffer_rsrc_t rs0 = in_rsrc(cur.b);
         halo_offsets(cur);
@@ -197,7 +226,7 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
     //  edge, and with the taps as the youngest loads here every chunk's transform waited for vmcnt(0) - the weight rows of the pair after next)
     __builtin_amdgcn_sched_barrier(0);                  // (... and the scheduler would hoist them back in front)
 #pragma unroll
-    for (int pp = 0; pp < 2; ++pp) { wr[pp][0] = load_w(cur.wbase, pp); wr[pp][1] = load_w(cur.wbase, 4 + pp); }
+    for (int pp = 0; pp < WRING; ++pp) { wr[pp][0] = load_w(cur.wbase, pp); wr[pp][1] = load_w(cur.wbase, 4 + pp); }
     __syncthreads();
 
     float4 ra[3], rb[3];                                // the operand rows of a PAIR of point steps (pz local 0 / 1 at one px): rows ta / tb of planes U, V, W
@@ -217,13 +246,16 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
         const bool has_next = next_work < nwork;
         const Tile nxt = has_next ? describe(next_work) : cur;
 
-        f32x16 acc[2][4];                               // [pz local][px]
+        constexpr int NH = N16 ? 2 : 1, NR = N16 ? 4 : 16;         // accumulator tiles per point (N16: the two 16-row halves), registers of one
+        std::conditional_t<N16, f32x4, f32x16> acc[2][4][NH];   // [pz local][px][half]
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
             for (int x = 0; x < 4; ++x)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[p][x][r] = 0.f;
+                for (int h = 0; h < NH; ++h)
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) acc[p][x][h][r] = 0.f;
 
         unsigned wcur = cur.wbase;                      // weights of the chunk being multiplied
         for (int chunk = 0; chunk < nchunk; ++chunk) {
@@ -237,8 +269,26 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
             float* img_w = smem + (cb ^ 1) * Q_IMG;
             const float* pa = img_r + pa_off;
             const float* pb = img_r + pb_off;
+            // (N16: the second half's rows through addresses of their own - fused into ds_read2_b64 the pair of reads would run at half the rate, on
+            //  32 banks)
+            // (the OFFSET is hidden from the compiler, not the pointer: a pointer that has passed through an asm statement is no longer known to point
+            //  into the LDS and is read with flat loads, whose waits are for everything)
+            int a_half = A_HALF;
+            if constexpr (N16) asm volatile("" : "+v"(a_half));
+            const float* pa_h = pa + a_half;
+            const float* pb_h = pb + a_half;
             auto fetch_a = [&](int px) {
                 const int o = px * Q_PL * 4;
+                if constexpr (N16) {                    // .xy: channels 2 kk, 2 kk + 1 of row i in half 0, .zw: in half 1
+                    auto two = [](const float* p_, const float* h_) {
+                        const float2 lo = *reinterpret_cast<const float2*>(p_), hi = *reinterpret_cast<const float2*>(h_);
+                        return make_float4(lo.x, lo.y, hi.x, hi.y);
+                    };
+                    ra[0] = two(pa + zu + o, pa_h + zu + o); rb[0] = two(pb + zu + o, pb_h + zu + o);
+                    ra[1] = two(pa + zv + o, pa_h + zv + o); rb[1] = two(pb + zv + o, pb_h + zv + o);
+                    ra[2] = two(pa + zw + o, pa_h + zw + o); rb[2] = two(pb + zw + o, pb_h + zw + o);
+                    return;
+                }
                 ra[0] = *reinterpret_cast<const float4*>(pa + zu + o); rb[0] = *reinterpret_cast<const float4*>(pb + zu + o);
                 ra[1] = *reinterpret_cast<const float4*>(pa + zv + o); rb[1] = *reinterpret_cast<const float4*>(pb + zv + o);
                 ra[2] = *reinterpret_cast<const float4*>(pa + zw + o); rb[2] = *reinterpret_cast<const float4*>(pb + zw + o);
@@ -269,6 +319,8 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
             float avn0[4], avn1[4];                     // the operands of the pair in flight / of the next pair
             fetch_a(0);
             combine(avn0, avn1);
+            // (N16: keeps the px 0 / px 1 requests apart - fused pairwise into ds_read2_b64 they run at half the rate and on 32 banks, two-way conflicted)
+            if constexpr (N16) __builtin_amdgcn_sched_barrier(0);
             fetch_a(1);
 #pragma unroll
             for (int pp = 0; pp < 4; ++pp) {
@@ -279,20 +331,27 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
                 // idle in its gaps.
                 if (((pp + pzh) & 1) != 0) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
                 const float av0[4] = {avn0[0], avn0[1], avn0[2], avn0[3]}, av1[4] = {avn1[0], avn1[1], avn1[2], avn1[3]};
-                const float wv0[4] = {wr[pp & 1][0].x, wr[pp & 1][0].y, wr[pp & 1][0].z, wr[pp & 1][0].w};
-                const float wv1[4] = {wr[pp & 1][1].x, wr[pp & 1][1].y, wr[pp & 1][1].z, wr[pp & 1][1].w};
+                float wv0[4], wv1[4];
+                unpack_w(wr[pp % WRING][0], wv0);
+                unpack_w(wr[pp % WRING][1], wv1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int s2 = 0; s2 < 4; ++s2) {
-                    acc[s0 >> 2][s0 & 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s2], wv0[s2], acc[s0 >> 2][s0 & 3], 0, 0, 0);
-                    acc[s1 >> 2][s1 & 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s2], wv1[s2], acc[s1 >> 2][s1 & 3], 0, 0, 0);
+                    if constexpr (N16) {                // step s2 = (k quad ks, half hf): four instructions lie between two on one accumulator
+                        const int hf = s2 & 1, ks = s2 >> 1;
+                        acc[0][pp][hf] = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[2 * hf + ks], wv0[ks], acc[0][pp][hf], 0, 0, 0);
+                        acc[1][pp][hf] = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[2 * hf + ks], wv1[ks], acc[1][pp][hf], 0, 0, 0);
+                    } else {
+                        acc[s0 >> 2][s0 & 3][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[s2], wv0[s2], acc[s0 >> 2][s0 & 3][0], 0, 0, 0);
+                        acc[s1 >> 2][s1 & 3][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[s2], wv1[s2], acc[s1 >> 2][s1 & 3][0], 0, 0, 0);
+                    }
                     if (s2 == 0) {                      // behind the pair's first MFMAs: the staging work of the pair
                         __builtin_amdgcn_sched_barrier(0);
                         if (pp == SP) {
                             store_item(img_w);
                             if (chunk + 2 == nchunk) halo_offsets(has_next ? nxt : cur);
                         }
-                        if (pp == SP + 1) { load_raw(st_rs, st_c0, 0); load_raw(st_rs, st_c0, 1); load_raw(st_rs, st_c0, 2); load_raw(st_rs, st_c0, 3); }
+                        if (pp == (N16 ? SP : SP + 1)) { load_raw(st_rs, st_c0, 0); load_raw(st_rs, st_c0, 1); load_raw(st_rs, st_c0, 2); load_raw(st_rs, st_c0, 3); }
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     if (s2 == 1 && pp + 1 < 4) {        // behind the fourth MFMA: the next pair's combinations, then the request for the pair after it
@@ -305,8 +364,13 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
                 }
                 // the pair's weights are consumed: a ring of two pairs - the rows take the points of the pair two on (the same chunk's, or the
                 // next chunk's first two)
-                wr[pp & 1][0] = pp < 2 ? load_w(wcur, s0 + 2) : load_w(wnext, s0 - 2);
-                wr[pp & 1][1] = pp < 2 ? load_w(wcur, s1 + 2) : load_w(wnext, s1 - 2);
+                if constexpr (N16) {
+                    wr[pp][0] = load_w(wnext, s0);
+                    wr[pp][1] = load_w(wnext, s1);
+                } else {
+                    wr[pp & 1][0] = pp < 2 ? load_w(wcur, s0 + 2) : load_w(wnext, s0 - 2);
+                    wr[pp & 1][1] = pp < 2 ? load_w(wcur, s1 + 2) : load_w(wnext, s1 - 2);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
             wcur += w_chunk_stride;
@@ -320,117 +384,203 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
         const int z0 = cur.z0, y0 = cur.y0, x0 = cur.x0, co0 = cur.co0;
         int elane = lane;
         asm volatile("" : "+v"(elane));
-        const int q = elane & 7, kh = (elane >> 3) & 1, g = elane >> 4;
         const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
         float4 s4 = zero4, q4 = zero4;
         const bool fuse = !BNR && a.coef != nullptr;
-        const float4 b4 = BNR ? zero4 : *reinterpret_cast<const float4*>(tab + co0 + 4 * q);
-        const float4 bm4 = *reinterpret_cast<const float4*>(tab + co0 + 4 * q);
-        const float4 sc4 = *reinterpret_cast<const float4*>(tab + ctab + co0 + 4 * q);
-        const float4 sh4 = *reinterpret_cast<const float4*>(tab + 2 * ctab + co0 + 4 * q);
-        const float* bn_b = BNR ? a.bn_y + (long)cur.b * a.bn_y_bs + co0 + 4 * q : nullptr;
-        // this lane finishes (ox, r) = combo of the exchange buffer, rows of half kh, channels 4 q .. 4 q + 3
-        const int combo = wave * 4 + g;
-        const int ox = combo >> 4, rr = combo & 15;
-        const int row = (rr & 3) + 8 * (rr >> 2) + 4 * kh;          // = MFMA row = block (zb, yb, xb)
-        const int vzb = row >> 4, vyb = (row >> 2) & 3, vxb = row & 3;
-        // x inverse transform (4 px -> 2 ox), once and in place: acc[p][0] <- out x0 = q0 + q1 + q2, acc[p][1] <- out x1 = q1 - q2 - q3
-        // BNR: the pre-norm values of this lane's two output voxels of a parity are requested EARLY - parity 0 in front of the x inverse transform,
-        // parity 1 as soon as parity 0's have been used - so that a miss (y is read once per step: HBM) lands under the transform and the exchange
-        // instead of in front of the sums that need it
-        float4 yv0 = zero4, yv1 = zero4;
-        const bool qok = co0 + 4 * q < a.Cout;         // (a partly empty cout tile: channel quads beyond the tensor are neither read nor stored)
-        auto load_y = [&](int oz_) {
-            if (BNR && qok) {
-                const long vox_ = (long)((z0 + 2 * vzb + oz_) * a.H + y0 + 2 * vyb) * a.W + x0 + 2 * vxb + ox;
-                yv0 = *reinterpret_cast<const float4*>(bn_b + vox_ * a.bn_y_ps);
-                yv1 = *reinterpret_cast<const float4*>(bn_b + (vox_ + a.W) * a.bn_y_ps);
-            }
-        };
-        load_y(0);
-        __builtin_amdgcn_sched_barrier(0);
-        // a - b below is fma(m1, b, a) with m1 = -1 the compiler cannot see through: exact (the product is), and it stays ONE two-wide instruction
-        // (v_pk_fma_f32) - a two-wide subtraction is expanded into two scalar ones by the backend
-        f32x2 m1 = {-1.f, -1.f};
-        asm volatile("" : "+s"(m1));
-        // (two-wide: the accumulator registers of rows r, r + 1 are an aligned pair - v_pk_add_f32 with the association of the scalar form,
-        //  (a0 + a1) + a2 and (a1 - a2) - a3: 64 instead of 128 vector instructions per wave, which the SIMD's two waves issue at the same time)
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const f32x2 a0 = {acc[p][0][r], acc[p][0][r + 1]}, a1 = {acc[p][1][r], acc[p][1][r + 1]};
-                const f32x2 a2 = {acc[p][2][r], acc[p][2][r + 1]}, a3 = {acc[p][3][r], acc[p][3][r + 1]};
-                const f32x2 o0 = (a0 + a1) + a2, o1 = __builtin_elementwise_fma(m1, a3, __builtin_elementwise_fma(m1, a2, a1));
-                acc[p][0][r] = o0.x; acc[p][0][r + 1] = o0.y;
-                acc[p][1][r] = o1.x; acc[p][1][r + 1] = o1.y;
-            }
-#pragma unroll
-        for (int oz = 0; oz < 2; ++oz) {
-            if (oz > 0) __syncthreads();                // every wave has left the exchange buffer (previous parity)
-            // this wave's share of the z inverse transform: out z0 = q0 + q1 + q2, out z1 = q1 - q2 - q3; wave pzh = 0 holds (q0, q1), pzh = 1
-            // holds (q2, -q3) (the second accumulator of those waves holds MINUS its point, see the matrix loop).  A branch per wave (pzh is
-            // wave-uniform) instead of two selects per value.
-            float* const r0 = R + ((wave * 2 + 0) * 16) * 64 + elane;
-            float* const r1 = R + ((wave * 2 + 1) * 16) * 64 + elane;
-            if (pzh == 0) {
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const f32x2 u0 = f32x2{acc[0][0][r], acc[0][0][r + 1]} + f32x2{acc[1][0][r], acc[1][0][r + 1]};
-                    const f32x2 u1 = f32x2{acc[0][1][r], acc[0][1][r + 1]} + f32x2{acc[1][1][r], acc[1][1][r + 1]};
-                    r0[r * 64] = oz == 0 ? u0.x : acc[1][0][r]; r0[(r + 1) * 64] = oz == 0 ? u0.y : acc[1][0][r + 1];
-                    r1[r * 64] = oz == 0 ? u1.x : acc[1][1][r]; r1[(r + 1) * 64] = oz == 0 ? u1.y : acc[1][1][r + 1];
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const f32x2 u0 = __builtin_elementwise_fma(m1, f32x2{acc[0][0][r], acc[0][0][r + 1]}, f32x2{acc[1][0][r], acc[1][0][r + 1]});
-                    const f32x2 u1 = __builtin_elementwise_fma(m1, f32x2{acc[0][1][r], acc[0][1][r + 1]}, f32x2{acc[1][1][r], acc[1][1][r + 1]});
-                    r0[r * 64] = oz == 0 ? acc[0][0][r] : u0.x; r0[(r + 1) * 64] = oz == 0 ? acc[0][0][r + 1] : u0.y;
-                    r1[r * 64] = oz == 0 ? acc[0][1][r] : u1.x; r1[(r + 1) * 64] = oz == 0 ? acc[0][1][r + 1] : u1.y;
-                }
-            }
+        if constexpr (N16) {
+            // Accumulator register r of half hf in lane l: block (zb = l / 32, yb = 2 hf + (l / 16) % 2, xb = r), output channel l % 16.  The eight
+            // waves write their x- and z-inverse-transformed rows of BOTH output z parities into R = [oz][wave][ox][hf * 4 + r][lane] (2 x 32 KB);
+            // behind ONE barrier thread (wave = (oz, ox, hf), lane = (xb, zb, yb % 2, channel quad q)) sums the z halves, finishes the y transform
+            // and stores its voxel pair (the 16 lanes of a ds_read_b128 group read 64 consecutive floats).
+            const int q = elane & 3, vzb = (elane >> 3) & 1, vxb = elane >> 4;
+            const int hf_ = wave & 1, ox = (wave >> 1) & 1, oz = wave >> 2;
+            const int vyb = 2 * hf_ + ((elane >> 2) & 1);
+            const float4 b4 = BNR ? zero4 : *reinterpret_cast<const float4*>(tab + co0 + 4 * q);
+            const float4 bm4 = *reinterpret_cast<const float4*>(tab + co0 + 4 * q);
+            const float4 sc4 = *reinterpret_cast<const float4*>(tab + ctab + co0 + 4 * q);
+            const float4 sh4 = *reinterpret_cast<const float4*>(tab + 2 * ctab + co0 + 4 * q);
+            const bool qok = co0 + 4 * q < a.Cout;
             const int gz = z0 + 2 * vzb + oz, gy = y0 + 2 * vyb, gx = x0 + 2 * vxb + ox;
             const long vox = (long)(gz * a.H + gy) * a.W + gx;
+            float4 yv0 = zero4, yv1 = zero4;                // BNR: the pre-norm values of the voxel pair, requested in front of the transforms
+            if (BNR && qok) {
+                const float* bn_b = a.bn_y + (long)cur.b * a.bn_y_bs + co0 + 4 * q;
+                yv0 = *reinterpret_cast<const float4*>(bn_b + vox * a.bn_y_ps);
+                yv1 = *reinterpret_cast<const float4*>(bn_b + (vox + a.W) * a.bn_y_ps);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            f32x2 m1 = {-1.f, -1.f};                        // (a - b as fma(m1, b, a): see the 32-wide form below)
+            asm volatile("" : "+s"(m1));
+            // x inverse transform in place: acc[p][0] <- q0 + q1 + q2, acc[p][1] <- q1 - q2 - q3
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                    for (int r = 0; r < 4; r += 2) {
+                        const f32x2 a0 = {acc[p][0][hf][r], acc[p][0][hf][r + 1]}, a1 = {acc[p][1][hf][r], acc[p][1][hf][r + 1]};
+                        const f32x2 a2 = {acc[p][2][hf][r], acc[p][2][hf][r + 1]}, a3 = {acc[p][3][hf][r], acc[p][3][hf][r + 1]};
+                        const f32x2 o0 = (a0 + a1) + a2, o1 = __builtin_elementwise_fma(m1, a3, __builtin_elementwise_fma(m1, a2, a1));
+                        acc[p][0][hf][r] = o0.x; acc[p][0][hf][r + 1] = o0.y;
+                        acc[p][1][hf][r] = o1.x; acc[p][1][hf][r + 1] = o1.y;
+                    }
+            // z inverse transform, this wave's share (out z0 = q0 + q1 + q2, out z1 = q1 - q2 - q3; pzh = 0 holds (q0, q1), pzh = 1 (q2, -q3))
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float c0 = acc[0][x][hf][r], c1 = acc[1][x][hf][r];
+                        float* const w0 = R + (((0 * 8 + wave) * 2 + x) * 8 + hf * 4 + r) * 64 + elane;
+                        float* const w1 = R + (((1 * 8 + wave) * 2 + x) * 8 + hf * 4 + r) * 64 + elane;
+                        if (pzh == 0) { *w0 = c0 + c1; *w1 = c1; }
+                        else { *w0 = c0; *w1 = c1 - c0; }
+                    }
             __syncthreads();
             float4 t[4];
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {               // point row p: the two z halves summed
-                const float4 u0 = *reinterpret_cast<const float4*>(R + (((0 * 4 + p) * 2 + ox) * 16 + rr) * 64 + kh * 32 + 4 * q);
-                const float4 u1 = *reinterpret_cast<const float4*>(R + (((1 * 4 + p) * 2 + ox) * 16 + rr) * 64 + kh * 32 + 4 * q);
+            for (int p = 0; p < 4; ++p) {                   // point row p: the two z halves summed
+                const float4 u0 = *reinterpret_cast<const float4*>(R + (((oz * 8 + p) * 2 + ox) * 8 + hf_ * 4 + vxb) * 64 + 4 * (elane & 15));
+                const float4 u1 = *reinterpret_cast<const float4*>(R + (((oz * 8 + 4 + p) * 2 + ox) * 8 + hf_ * 4 + vxb) * 64 + 4 * (elane & 15));
                 t[p] = make_float4(u0.x + u1.x, u0.y + u1.y, u0.z + u1.z, u0.w + u1.w);
             }
             float4 v0, v1;
             inverse_last(t[0], t[1], t[2], t[3], b4, v0, v1);
-            if (BNR) {
-                bn_bwd_reduce_pair(v0, v1, yv0, yv1, sc4, sh4, bm4, a.slope, s4, q4);     // (pulpo::bn_bwd_reduce_step, head_bn.h)
-                if (oz == 0) { __builtin_amdgcn_sched_barrier(0); load_y(1); __builtin_amdgcn_sched_barrier(0); }
-            } else {
-                stats_add_pair(v0, v1, s4, q4);
-            }
+            if (BNR) bn_bwd_reduce_pair(v0, v1, yv0, yv1, sc4, sh4, bm4, a.slope, s4, q4);
+            else stats_add_pair(v0, v1, s4, q4);
             if (fuse) {
                 v0 = bn_lrelu4(v0, sc4, sh4, a.slope);
                 v1 = bn_lrelu4(v1, sc4, sh4, a.slope);
             }
-            float* obase = out_b + (long)((co0 + 4 * q) >> 3) * a.out_kb + ((4 * q) & 7);      // (out_kb = 8: channels-last, co0 + 4 q)
+            float* obase = out_b + (long)((co0 + 4 * q) >> 3) * a.out_kb + ((4 * q) & 7);
             if (qok) {
                 *reinterpret_cast<float4*>(obase + vox * a.out_ps) = v0;
                 *reinterpret_cast<float4*>(obase + (vox + a.W) * a.out_ps) = v1;
             }
-        }
-        // per-tile BatchNorm partial sums: over the lanes that hold the same channels, then over the eight waves
-        // (through the wave's own LDS rows - DS operations of one wave execute in order, no barrier - instead of three rounds of cross-lane
-        //  shuffles: lane l then owns ONE of the wave's 64 sums (which = l / 32, channel l % 32) and adds the eight lanes that hold its channel quad)
-        if (a.stats != nullptr) {
-            float* pw_ = part + (wave * 64 + elane) * 8;
-            *reinterpret_cast<float4*>(pw_) = s4;
-            *reinterpret_cast<float4*>(pw_ + 4) = q4;
-            const int c_ = elane & 31, wh_ = elane >> 5;
-            const float* pr_ = part + (wave * 64 + (c_ >> 2)) * 8 + wh_ * 4 + (c_ & 3);
-            float t_ = 0.f;
+            // per-tile partial sums: lane l owns ONE of the wave's sums (which = l / 32, channel l % 32 < 16) and adds the sixteen lanes q + 4 j
+            // that hold its channel quad, through the wave's own LDS rows (in order, no barrier)
+            if (a.stats != nullptr) {
+                float* pw_ = part + (wave * 64 + elane) * 8;
+                *reinterpret_cast<float4*>(pw_) = s4;
+                *reinterpret_cast<float4*>(pw_ + 4) = q4;
+                const int c_ = elane & 31, wh_ = elane >> 5;
+                const float* pr_ = part + (wave * 64 + ((c_ >> 2) & 3)) * 8 + wh_ * 4 + (c_ & 3);
+                float t_ = 0.f;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) t_ += pr_[j * 64];          // lanes q + 8 j
-            red[(wave * 2 + wh_) * NT + c_] = t_;
+                for (int j = 0; j < 16; ++j) t_ += pr_[j * 32];         // lanes q + 4 j
+                red[(wave * 2 + wh_) * NT + c_] = c_ < 16 ? t_ : 0.f;
+            }
+        } else {
+            const int q = elane & 7, kh = (elane >> 3) & 1, g = elane >> 4;
+            const float4 b4 = BNR ? zero4 : *reinterpret_cast<const float4*>(tab + co0 + 4 * q);
+            const float4 bm4 = *reinterpret_cast<const float4*>(tab + co0 + 4 * q);
+            const float4 sc4 = *reinterpret_cast<const float4*>(tab + ctab + co0 + 4 * q);
+            const float4 sh4 = *reinterpret_cast<const float4*>(tab + 2 * ctab + co0 + 4 * q);
+            const float* bn_b = BNR ? a.bn_y + (long)cur.b * a.bn_y_bs + co0 + 4 * q : nullptr;
+            // this lane finishes (ox, r) = combo of the exchange buffer, rows of half kh, channels 4 q .. 4 q + 3
+            const int combo = wave * 4 + g;
+            const int ox = combo >> 4, rr = combo & 15;
+            const int row = (rr & 3) + 8 * (rr >> 2) + 4 * kh;          // = MFMA row = block (zb, yb, xb)
+            const int vzb = row >> 4, vyb = (row >> 2) & 3, vxb = row & 3;
+            // x inverse transform (4 px -> 2 ox), once and in place: acc[p][0] <- out x0 = q0 + q1 + q2, acc[p][1] <- out x1 = q1 - q2 - q3
+            // BNR: the pre-norm values of this lane's two output voxels of a parity are requested EARLY - parity 0 in front of the x inverse transform,
+            // parity 1 as soon as parity 0's have been used - so that a miss (y is read once per step: HBM) lands under the transform and the exchange
+            // instead of in front of the sums that need it
+            float4 yv0 = zero4, yv1 = zero4;
+            const bool qok = co0 + 4 * q < a.Cout;         // (a partly empty cout tile: channel quads beyond the tensor are neither read nor stored)
+            auto load_y = [&](int oz_) {
+                if (BNR && qok) {
+                    const long vox_ = (long)((z0 + 2 * vzb + oz_) * a.H + y0 + 2 * vyb) * a.W + x0 + 2 * vxb + ox;
+                    yv0 = *reinterpret_cast<const float4*>(bn_b + vox_ * a.bn_y_ps);
+                    yv1 = *reinterpret_cast<const float4*>(bn_b + (vox_ + a.W) * a.bn_y_ps);
+                }
+            };
+            load_y(0);
+            __builtin_amdgcn_sched_barrier(0);
+            // a - b below is fma(m1, b, a) with m1 = -1 the compiler cannot see through: exact (the product is), and it stays ONE two-wide instruction
+            // (v_pk_fma_f32) - a two-wide subtraction is expanded into two scalar ones by the backend
+            f32x2 m1 = {-1.f, -1.f};
+            asm volatile("" : "+s"(m1));
+            // (two-wide: the accumulator registers of rows r, r + 1 are an aligned pair - v_pk_add_f32 with the association of the scalar form,
+            //  (a0 + a1) + a2 and (a1 - a2) - a3: 64 instead of 128 vector instructions per wave, which the SIMD's two waves issue at the same time)
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const f32x2 a0 = {acc[p][0][0][r], acc[p][0][0][r + 1]}, a1 = {acc[p][1][0][r], acc[p][1][0][r + 1]};
+                    const f32x2 a2 = {acc[p][2][0][r], acc[p][2][0][r + 1]}, a3 = {acc[p][3][0][r], acc[p][3][0][r + 1]};
+                    const f32x2 o0 = (a0 + a1) + a2, o1 = __builtin_elementwise_fma(m1, a3, __builtin_elementwise_fma(m1, a2, a1));
+                    acc[p][0][0][r] = o0.x; acc[p][0][0][r + 1] = o0.y;
+                    acc[p][1][0][r] = o1.x; acc[p][1][0][r + 1] = o1.y;
+                }
+#pragma unroll
+            for (int oz = 0; oz < 2; ++oz) {
+                if (oz > 0) __syncthreads();                // every wave has left the exchange buffer (previous parity)
+                // this wave's share of the z inverse transform: out z0 = q0 + q1 + q2, out z1 = q1 - q2 - q3; wave pzh = 0 holds (q0, q1), pzh = 1
+                // holds (q2, -q3) (the second accumulator of those waves holds MINUS its point, see the matrix loop).  A branch per wave (pzh is
+                // wave-uniform) instead of two selects per value.
+                float* const r0 = R + ((wave * 2 + 0) * 16) * 64 + elane;
+                float* const r1 = R + ((wave * 2 + 1) * 16) * 64 + elane;
+                if (pzh == 0) {
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        const f32x2 u0 = f32x2{acc[0][0][0][r], acc[0][0][0][r + 1]} + f32x2{acc[1][0][0][r], acc[1][0][0][r + 1]};
+                        const f32x2 u1 = f32x2{acc[0][1][0][r], acc[0][1][0][r + 1]} + f32x2{acc[1][1][0][r], acc[1][1][0][r + 1]};
+                        r0[r * 64] = oz == 0 ? u0.x : acc[1][0][0][r]; r0[(r + 1) * 64] = oz == 0 ? u0.y : acc[1][0][0][r + 1];
+                        r1[r * 64] = oz == 0 ? u1.x : acc[1][1][0][r]; r1[(r + 1) * 64] = oz == 0 ? u1.y : acc[1][1][0][r + 1];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        const f32x2 u0 = __builtin_elementwise_fma(m1, f32x2{acc[0][0][0][r], acc[0][0][0][r + 1]}, f32x2{acc[1][0][0][r], acc[1][0][0][r + 1]});
+                        const f32x2 u1 = __builtin_elementwise_fma(m1, f32x2{acc[0][1][0][r], acc[0][1][0][r + 1]}, f32x2{acc[1][1][0][r], acc[1][1][0][r + 1]});
+                        r0[r * 64] = oz == 0 ? acc[0][0][0][r] : u0.x; r0[(r + 1) * 64] = oz == 0 ? acc[0][0][0][r + 1] : u0.y;
+                        r1[r * 64] = oz == 0 ? acc[0][1][0][r] : u1.x; r1[(r + 1) * 64] = oz == 0 ? acc[0][1][0][r + 1] : u1.y;
+                    }
+                }
+                const int gz = z0 + 2 * vzb + oz, gy = y0 + 2 * vyb, gx = x0 + 2 * vxb + ox;
+                const long vox = (long)(gz * a.H + gy) * a.W + gx;
+                __syncthreads();
+                float4 t[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {               // point row p: the two z halves summed
+                    const float4 u0 = *reinterpret_cast<const float4*>(R + (((0 * 4 + p) * 2 + ox) * 16 + rr) * 64 + kh * 32 + 4 * q);
+                    const float4 u1 = *reinterpret_cast<const float4*>(R + (((1 * 4 + p) * 2 + ox) * 16 + rr) * 64 + kh * 32 + 4 * q);
+                    t[p] = make_float4(u0.x + u1.x, u0.y + u1.y, u0.z + u1.z, u0.w + u1.w);
+                }
+                float4 v0, v1;
+                inverse_last(t[0], t[1], t[2], t[3], b4, v0, v1);
+                if (BNR) {
+                    bn_bwd_reduce_pair(v0, v1, yv0, yv1, sc4, sh4, bm4, a.slope, s4, q4);     // (pulpo::bn_bwd_reduce_step, head_bn.h)
+                    if (oz == 0) { __builtin_amdgcn_sched_barrier(0); load_y(1); __builtin_amdgcn_sched_barrier(0); }
+                } else {
+                    stats_add_pair(v0, v1, s4, q4);
+                }
+                if (fuse) {
+                    v0 = bn_lrelu4(v0, sc4, sh4, a.slope);
+                    v1 = bn_lrelu4(v1, sc4, sh4, a.slope);
+                }
+                float* obase = out_b + (long)((co0 + 4 * q) >> 3) * a.out_kb + ((4 * q) & 7);      // (out_kb = 8: channels-last, co0 + 4 q)
+                if (qok) {
+                    *reinterpret_cast<float4*>(obase + vox * a.out_ps) = v0;
+                    *reinterpret_cast<float4*>(obase + (vox + a.W) * a.out_ps) = v1;
+                }
+            }
+            // per-tile BatchNorm partial sums: over the lanes that hold the same channels, then over the eight waves
+            // (through the wave's own LDS rows - DS operations of one wave execute in order, no barrier - instead of three rounds of cross-lane
+            //  shuffles: lane l then owns ONE of the wave's 64 sums (which = l / 32, channel l % 32) and adds the eight lanes that hold its channel quad)
+            if (a.stats != nullptr) {
+                float* pw_ = part + (wave * 64 + elane) * 8;
+                *reinterpret_cast<float4*>(pw_) = s4;
+                *reinterpret_cast<float4*>(pw_ + 4) = q4;
+                const int c_ = elane & 31, wh_ = elane >> 5;
+                const float* pr_ = part + (wave * 64 + (c_ >> 2)) * 8 + wh_ * 4 + (c_ & 3);
+                float t_ = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) t_ += pr_[j * 64];          // lanes q + 8 j
+                red[(wave * 2 + wh_) * NT + c_] = t_;
+            }
         }
         pend_tile = cur.tile_lin; pend_co0 = co0;
         if (!has_next) break;
@@ -446,10 +596,10 @@ __device__ __forceinline__ void wino3_body(const ConvArgs& a) {
 // one wave's vector and LDS-write work falls into the other's matrix phase.  Two whole copies behind ONE wave-uniform branch at the top (no state
 // joins behind it: the copies share only the kernel arguments and the LDS), and a compile-time constant per copy, because a wave-uniform RUNTIME
 // branch around the tap loads makes every vmcnt behind it a worst-case guess (measured in round 4: -15 %).  Both copies pass the same barriers.
-template <bool BNR>
+template <bool BNR, bool N16>
 __global__ __launch_bounds__(512, 1) void conv3d_k3_wino3_mfma(ConvArgs a) {
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 8) != 0) wino3_body<BNR, 2>(a);
-    else wino3_body<BNR, 0>(a);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 8) != 0) wino3_body<BNR, 2, N16>(a);
+    else wino3_body<BNR, 0, N16>(a);
 }
 
 __global__ void pack_weight_wino3_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cin, int Cout, int NPad, int dgrad, long total) {
@@ -467,8 +617,8 @@ namespace pulpo_conv {
 
 // shapes the F(2x2x2,3x3x3) kernel takes: whole 4 x 8 x 8 tiles, K % 8 == 0, N % 32 == 0, at least 256 work items (one per CU)
 int wino3_shape_ok(int B, int D, int H, int W, int K, int N) {
-    // (output channels: a multiple of 4; a cout tile of 32 may be partly empty - the 16-channel data gradient of the feedback layer runs at half
-    //  the tile's columns here as it did in the (y, x) kernel, on 1.5x fewer matrix instructions)
+    // (output channels: a multiple of 4; a cout tile of 32 may be partly empty.  The 16-channel data gradient of the feedback layer is admitted
+    //  as before and runs the kernel's 16-column form: pulpo_conv3d_k3_narrow16)
     const int ncot = (N + Q_NT - 1) / Q_NT;
     if (K < WINO3_MIN_K || K % Q_CH != 0 || N % 4 != 0 || (N % Q_NT != 0 && N < 16) || 3 * ncot * Q_NT > Q_TAB) return 0;
     if (D % 4 != 0 || H % TY != 0 || W % TX != 0) return 0;
@@ -479,6 +629,16 @@ int wino3_shape_ok(int B, int D, int H, int W, int K, int N) {
 }
 
 }  // namespace pulpo_conv
+
+// which form of a kernel a channel pair runs (read-only; the launchers decide through it).  kind 0: the forward / data-gradient F(2x2x2,3x3x3)
+// kernel with K reduction and N output channels - 1: the 16-column form on v_mfma_f32_16x16x4_f32 (N == 16), 0: the 32-wide cout tiles.
+// kind 1: the F(2x2x2,3x3x3) weight-gradient kernel (conv3d_wgrad_w2.hip) with K = Cin, N = Cout - 1: the last ci tile holds 16 channels
+// (Cin % 32 == 16) and its workgroups run the 16-row form, 0: 32-row tiles only.  Any other kind: 0.
+PULPO_API int pulpo_conv3d_k3_narrow16(int kind, int K, int N) {
+    if (kind == 0) return K >= WINO3_MIN_K && K % Q_CH == 0 && N == 16;
+    if (kind == 1) return K > 0 && N > 0 && K % 32 == 16;
+    return 0;
+}
 
 PULPO_API size_t pulpo_conv3d_k3_packed_wino3_floats(int K, int N) { return (size_t)((K + Q_CH - 1) / Q_CH) * 64 * Q_CH * npad(N); }
 
@@ -522,16 +682,19 @@ static int fwd_wino3_impl(const float* in, int64_t in_bs, int64_t in_ps, int64_t
     PULPO_REQUIRE(nwork < (1L << 31), "conv3d_k3_fwd_wino3: grid too large");
     hipStream_t st = (hipStream_t)stream;
     const bool bnr = bn_y != nullptr;
-    static bool attr_set[2] = {false, false};
-    const void* fn = bnr ? reinterpret_cast<const void*>(&conv3d_k3_wino3_mfma<true>) : reinterpret_cast<const void*>(&conv3d_k3_wino3_mfma<false>);
-    if (!attr_set[bnr]) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Q_LDS);
+    const bool n16 = pulpo_conv3d_k3_narrow16(0, K, N) != 0;     // 16 output channels: the 16x16x4 form of the kernel
+    using kernel_t = void (*)(ConvArgs);
+    static const kernel_t kernels[2][2] = {{conv3d_k3_wino3_mfma<false, false>, conv3d_k3_wino3_mfma<false, true>},
+                                           {conv3d_k3_wino3_mfma<true, false>, conv3d_k3_wino3_mfma<true, true>}};
+    static bool attr_set[2][2] = {{false, false}, {false, false}};
+    const kernel_t fn = kernels[bnr][n16];
+    if (!attr_set[bnr][n16]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Q_LDS);
         if (e != hipSuccess) return pulpo::fail((int)e, "hipFuncSetAttribute(conv3d wino3): %s", hipGetErrorString(e));
-        attr_set[bnr] = true;
+        attr_set[bnr][n16] = true;
     }
     const int nwg = (int)std::min<long>(nwork, 256);    // persistent workgroups: one per CU
-    if (bnr) hipLaunchKernelGGL((conv3d_k3_wino3_mfma<true>), dim3(nwg), dim3(512), Q_LDS, st, a);
-    else hipLaunchKernelGGL((conv3d_k3_wino3_mfma<false>), dim3(nwg), dim3(512), Q_LDS, st, a);
+    hipLaunchKernelGGL(fn, dim3(nwg), dim3(512), Q_LDS, st, a);
     return pulpo::check_launch("conv3d_k3_wino3_mfma");
 }
 
