@@ -326,9 +326,19 @@ class DataParallelStepper:
             self._in_backward = False
             self._armed = False
 
+    def _refuse_stale_arena(self) -> None:
+        """The arena holds the parameters that were trainable when it was built, and the fused Adam kernel updates all of it: a parameter frozen
+        since then would receive a zero gradient and keep moving through its Adam moments.  Refused; freeze first, then build the stepper."""
+        for p in self.arena.params:
+            if not p.requires_grad:
+                name = self.arena.module_names[next(i for i, q in enumerate(self.arena.module_order) if q is p)]
+                raise ValueError(f"DataParallelStepper: parameter '{name}' was frozen (requires_grad=False) after the stepper / optimizer was built; "
+                                 "its Adam moments would keep moving it.  Rebuild the stepper (configure_optimizers()) after freezing.")
+
     def reduce_and_update(self, reduced_elsewhere: bool = False) -> None:
         """gradient exchange (what is left of it) + fused Adam.  reduced_elsewhere: a DistributedDataParallel wrapper has already averaged
         the gradients (Lightning's ddp strategy): no exchange here, no 1/world scale."""
+        self._refuse_stale_arena()
         if reduced_elsewhere:
             self.opt.step(1.0)
             self._steps_done += 1

@@ -184,6 +184,8 @@ def backward_pass(direct: bool, side=None, window=None, module: Optional[torch.n
 def _grad_slot(p: torch.Tensor) -> Optional[torch.Tensor]:
     if not _PASS.direct or not p.is_leaf:         # (lifted 2-D weights are derived tensors: their gradient goes through autograd)
         return None
+    if not p.requires_grad:                      # (a frozen parameter may still carry a .grad tensor - frozen after the optimizer was built: never written)
+        return None
     g = getattr(p, "grad", None)
     if g is None or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
         return None

@@ -157,6 +157,24 @@ def test_flat_arena_views_and_zero_grad():
     assert float(arena.grad.abs().sum()) == 0 and all(float(p.grad.abs().sum()) == 0 for p in lin.parameters())
 
 
+def test_stepper_refuses_a_parameter_frozen_after_it_was_built():
+    """the arena and the Adam moments cover what was trainable when the stepper was built: a parameter frozen afterwards is not moved through
+    stale moments - the update raises and says to rebuild; a stepper built after freezing leaves the parameter out"""
+    import pytest
+    from pulpo_amd.dp import DataParallelStepper
+    net = torch.nn.Sequential(torch.nn.Linear(3, 5), torch.nn.Linear(5, 2))
+    stepper = DataParallelStepper(net, lr=1e-3)
+    stepper._refuse_stale_arena()                      # (nothing frozen: no objection)
+    net[0].weight.requires_grad_(False)
+    before = [p.detach().clone() for p in net.parameters()]
+    with pytest.raises(ValueError, match=r"'0\.weight'.*Rebuild the stepper"):
+        stepper.reduce_and_update()
+    assert all(torch.equal(p.detach(), b) for p, b in zip(net.parameters(), before)) and stepper.opt.t == 0
+    rebuilt = DataParallelStepper(net, lr=1e-3)
+    assert all(p is not net[0].weight for p in rebuilt.arena.params) and len(rebuilt.arena.params) == 3
+    rebuilt._refuse_stale_arena()
+
+
 def test_fused_adam_state_dict_is_torch_adam_layout_whatever_the_arena_order():
     """FusedAdam.state_dict() is torch.optim.Adam's layout (per parameter, module.parameters() order), independent of the arena's internal
     (bucket) order: round trip through torch.optim.Adam and into an arena with a different permutation"""
