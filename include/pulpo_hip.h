@@ -517,6 +517,23 @@ int pulpo_augment_apply(const float* theta, const float* phi, int spacing, int G
 int pulpo_bspline_field(const float* phi, const float* theta, float* out, int spacing, int Gz, int Gy, int Gx, int B, int D, int H, int W, void* stream);
 int pulpo_philox4x32(const void* counters, const void* key, void* out, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------- cubic B-spline interpolation (added within ABI 8: nothing else changed)
+ * No counterpart in the reference, whose SpatialTransformer stores `mode` and resamples trilinearly; DESIGN.md section 3t holds the definition:
+ * scipy.ndimage's order-3 spline, mode="mirror", at the deformable warp's clamped sample coordinate (csrc/sampling.h).  fp32, planar.
+ * pulpo_bspline_prefilter: coef = the interpolating coefficients of `planes` volumes img (D,H,W), out of place: per axis of N >= 2 samples the
+ *   solution of s[k] = (coef[m(k-1)] + 4 coef[k] + coef[m(k+1)]) / 6 with the whole-sample mirror m (period 2 (N - 1)), by the recursive filter
+ *   of pole sqrt(3) - 2 and gain 6; an axis of one sample is left alone (= scipy.ndimage.spline_filter(order=3, mode="mirror")).
+ * pulpo_warp3d_cubic_fwd: out (B,C,Dg,Hg,Wg) = per voxel and axis, with pulpo_warp3d_fwd's coordinate c (clamped to [0, Si - 1]), i = floor(c),
+ *   f = c - i: the tensor-product sum over the taps m(i - 1 + l), l = 0..3, of B_l(fz) B_l(fy) B_l(fx) coef (B,C,Di,Hi,Wi); a depth-1 grid is
+ *   the 2-D form (16 taps).  coef is pulpo_bspline_prefilter of the image; the result may leave the image's range (overshoot).
+ * pulpo_warp3d_cubic_bwd: gdf (B,3,Dg,Hg,Wg) = the gradient with respect to df given gout (B,C,Dg,Hg,Wg): the same gather with B'_l along
+ *   the axis, times d c / d df (0 where the coordinate was clamped).  Every element written, no atomics: the same bits on every call.  The
+ *   coefficients are data (no gradient with respect to the image). */
+int pulpo_bspline_prefilter(const float* img, float* coef, int planes, int D, int H, int W, void* stream);
+int pulpo_warp3d_cubic_fwd(const float* df, const float* coef, float* out, int B, int C, int Dg, int Hg, int Wg, int Di, int Hi, int Wi, void* stream);
+int pulpo_warp3d_cubic_bwd(const float* df, const float* coef, const float* gout, float* gdf, int B, int C, int Dg, int Hg, int Wg, int Di, int Hi,
+                           int Wi, void* stream);
+
 /* --------------------------------------------------------------------------------------------------- optimizer
  * torch.optim.Adam(lr) defaults (src/models.py:398-400) over a flat fp32 arena; gscale pre-multiplies the gradient.  beta1, beta2 are doubles
  * (since ABI 8): 1 - beta and 1 - beta^step are formed in double. */

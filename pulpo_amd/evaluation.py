@@ -174,7 +174,7 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
                 mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
                 mind_eps: float = 1e-5, refine: Optional[Dict[str, object]] = None, surface: bool = False,
                 include_background: bool = False, affine=None, bending: bool = False, mi: bool = False,
-                mi_bins: int = 32) -> Dict[str, Dict[int, torch.Tensor]]:
+                mi_bins: int = 32, interpolation: str = "linear") -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
@@ -190,7 +190,13 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
     fits one.  The model (and a refinement) then sees ops.affine_warp(theta, x), and every row that reads a field reads
     ops.affine_compose(theta, final_dfs[l], x's size) - "affine first, deformable second" as one field - together with the ORIGINAL seg_x /
     lm_x / mask_x: one interpolation carries them through both transforms.  With inverse=True it raises NotImplementedError (the inverse of
-    the composition is not built)."""
+    the composition is not built).
+    interpolation: "linear" - the trilinear outputs, today's path; "cubic" - the image rows (RMSE, RMSE_masked, MIND, MI)
+    are scored on cubic B-spline outputs (model.predict_deterministic / model.refine with interpolation="cubic"; a refinement then descends on
+    the cubic image model too, unless its dict names an interpolation of its own).  With affine= the ORIGINAL x goes once through
+    ops.warp3d_cubic under the composed field: one interpolation, as for the segmentations.  Segmentation, landmark and field rows do not
+    depend on it; masks and label maps stay on their own samplers.  Cubic outputs may leave x's range by overshoot (the MI row clamps)."""
+    ops.check_interpolation(interpolation, "performance")
     final_dfs_inv = None
     if surface and seg_x is None:
         raise ValueError("performance: surface=True needs seg_x and seg_y")
@@ -199,20 +205,24 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
         if inverse:
             raise NotImplementedError("performance: inverse=True together with affine= (the inverse of the composed transform) is not implemented")
         theta = affine_mod.fit(x, y, **affine)["theta"] if isinstance(affine, dict) else affine
-        x = ops.affine_warp(theta, x)
+        x_original, x = x, ops.affine_warp(theta, x)
     if refine is not None:
-        res = model.refine(x, y, **refine)
+        res = model.refine(x, y, **(refine if interpolation == "linear" else {"interpolation": interpolation, **refine}))
         outputs, individual_dfs, final_dfs = res["outputs"], res["individual_dfs"], res["final_dfs"]
         if inverse:
             _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
     else:
-        outputs, individual_dfs = model.predict_deterministic(x, y)
+        outputs, individual_dfs = model.predict_deterministic(x, y) if interpolation == "linear" else \
+            model.predict_deterministic(x, y, interpolation=interpolation)
         if inverse:
             _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
         else:
             _, final_dfs = model.combine_dfs(individual_dfs)
     if theta is not None:
         final_dfs = {l: ops.affine_compose(theta, df, x.shape[2:]) for l, df in final_dfs.items()}
+        if interpolation == "cubic":                    # affine and deformable in one cubic resample of the original image
+            coef = ops.bspline_prefilter(x_original)
+            outputs = {l: ops.warp3d_cubic(df, coef=coef) for l, df in final_dfs.items()}
     return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv,
                         mask_x=mask_x, mask_y=mask_y, mind=mind, mind_dilation=mind_dilation, mind_eps=mind_eps,
                         surface=surface, include_background=include_background, bending=bending, mi=mi, mi_bins=mi_bins)

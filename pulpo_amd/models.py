@@ -267,42 +267,64 @@ class PULPo(ABC, LightningModule):
         fold = lambda t: t.view([N, bs] + list(t.shape[1:])).transpose(0, 1)
         return {k: fold(v) for k, v in outputs.items()}, {k: fold(v) for k, v in individual_dfs.items()}
 
-    def predict(self, x: torch.Tensor, y: torch.Tensor, N: int = 1):
+    def _resample(self, interpolation: str, fields: Dict[int, torch.Tensor], images) -> Dict[int, torch.Tensor]:
+        """the images handed back: images (one tensor for every level, or {level: tensor}) under the final fields, trilinear
+        (SpatialTransformer: today's route) or through the cubic B-spline interpolant (ops.warp3d_cubic).  The fields are
+        the same either way; cubic values may leave the image's range by overshoot at edges."""
+        img = (lambda k: images[k]) if isinstance(images, dict) else (lambda k: images)
+        if interpolation == "cubic":
+            coef = {}                                                          # one prefilter per distinct image
+            for k in fields:
+                if id(img(k)) not in coef:
+                    coef[id(img(k))] = ops.bspline_prefilter(img(k).detach())
+            return {k: ops.warp3d_cubic(fields[k], coef=coef[id(img(k))]) for k in fields}
+        return {k: self.autoencoder.decoders[k].spatial_transform(fields[k], img(k)) for k in fields}
+
+    def predict(self, x: torch.Tensor, y: torch.Tensor, N: int = 1, interpolation: str = "linear"):
+        """interpolation: "linear" (trilinear) or "cubic" (cubic B-spline, ops.warp3d_cubic) for the outputs; the fields do not depend on it"""
+        ops.check_interpolation(interpolation, "predict")
         _, individual_dfs = self.predict_output_samples(x, y, N)
         avg_dfs = {k: v.mean(dim=1) for k, v in individual_dfs.items()}
         _, avg_final = self.combine_dfs(avg_dfs)
         # every level warps the FULL-resolution moving image (grid smaller than the image for l >= 1, models.py:330)
-        avg_outputs = {k: self.autoencoder.decoders[k].spatial_transform(avg_final[k], x) for k in avg_final}
+        avg_outputs = self._resample(interpolation, avg_final, x)
         return avg_outputs, avg_dfs
 
-    def predict_deterministic(self, x: torch.Tensor, y: torch.Tensor):
+    def predict_deterministic(self, x: torch.Tensor, y: torch.Tensor, interpolation: str = "linear"):
+        """interpolation="cubic": outputs[l] = ops.warp3d_cubic(final_dfs[l], the level's moving image) instead of the trilinear warp"""
+        ops.check_interpolation(interpolation, "predict_deterministic")
         outs = self.autoencoder(x, self.downpath(x, y, _needed=self._needed_levels), deterministic=True)
+        if interpolation == "cubic":
+            return self._resample(interpolation, outs[6], self.autoencoder.level_images(x)), outs[4]
         return outs[7], outs[4]
 
     @torch.no_grad()
-    def predict_bidirectional(self, x: torch.Tensor, y: torch.Tensor, N: int = 1, deterministic: bool = False):
+    def predict_bidirectional(self, x: torch.Tensor, y: torch.Tensor, N: int = 1, deterministic: bool = False, interpolation: str = "linear"):
         """predict (or, with deterministic, predict_deterministic) + combine_dfs with the inverse transform beside it: a dict of
           outputs, individual_dfs   what predict / predict_deterministic return
           final_dfs                 combine_dfs(individual_dfs)[1]
           final_dfs_inv             the inverse fields of combine_dfs_bidirectional
           outputs_inv               {l: spatial_transform(final_dfs_inv[l], y)}: the fixed image on the moving image's grid, warped the
                                     way predict warps x
+        interpolation: "linear" or "cubic" for outputs and outputs_inv (the same images under the same fields, through ops.warp3d_cubic).
         Inference only: no autograd."""
+        ops.check_interpolation(interpolation, "predict_bidirectional")
         if deterministic:
-            outputs, individual_dfs = self.predict_deterministic(x, y)
+            outputs, individual_dfs = self.predict_deterministic(x, y, interpolation=interpolation)
             _, final, final_inv = self.combine_dfs_bidirectional(individual_dfs)
         else:
             _, samples = self.predict_output_samples(x, y, N)
             individual_dfs = {k: v.mean(dim=1) for k, v in samples.items()}
             _, final, final_inv = self.combine_dfs_bidirectional(individual_dfs)
-            outputs = {k: self.autoencoder.decoders[k].spatial_transform(final[k], x) for k in final}          # as predict
-        outputs_inv = {k: self.autoencoder.decoders[k].spatial_transform(final_inv[k], y) for k in final_inv}
+            outputs = self._resample(interpolation, final, x)                                                  # as predict
+        outputs_inv = self._resample(interpolation, final_inv, y)
         return {"outputs": outputs, "individual_dfs": individual_dfs, "final_dfs": final, "final_dfs_inv": final_inv, "outputs_inv": outputs_inv}
 
-    def refine(self, x: torch.Tensor, y: torch.Tensor, **kw):
-        """instance-specific optimisation of this pair's level fields from the model's prediction: pulpo_amd.refine.refine(self, x, y, **kw)"""
-        from .refine import refine
-        return refine(self, x, y, **kw)
+    def refine(self, x: torch.Tensor, y: torch.Tensor, interpolation: str = "linear", **kw):
+        """instance-specific optimisation of this pair's level fields from the model's prediction: pulpo_amd.refine.refine(self, x, y, **kw);
+        interpolation="cubic" descends on, and hands back, the cubic B-spline image model (pulpo_amd.refine.refine_interpolated)"""
+        from .refine import refine_interpolated
+        return refine_interpolated(self, x, y, interpolation, **kw)
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:  # type: ignore[override]
         return self.autoencoder(x, self.downpath(x, y, _needed=self._needed_levels))[7][0]

@@ -1905,6 +1905,95 @@ def warp_mask(df, mask):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ cubic B-spline interpolation
+# Images only: a label map has no cubic interpolant (warp_labels) and a weight volume would overshoot (warp_mask).
+INTERPOLATIONS = ("linear", "cubic")
+
+
+def check_interpolation(interpolation, who: str) -> str:
+    """the `interpolation` argument of the public surface: "linear" (trilinear, the default route) or "cubic"; anything else raises"""
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError(f"{who}: interpolation is {interpolation!r}; one of {INTERPOLATIONS} expected")
+    return interpolation
+
+
+def _cubic_image(t, name: str, what: str):
+    if not isinstance(t, torch.Tensor) or t.dim() not in (4, 5):
+        raise ValueError(f"{name}: {what} (B,C,D,H,W) or, for slices, (B,C,H,W) expected, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    if t.requires_grad:
+        raise ValueError(f"{name}: the image is data here (no gradient with respect to {what}); detach it")
+    if min(t.shape) < 1:
+        raise ValueError(f"{name}: {what} of shape {tuple(t.shape)} has an empty extent")
+
+
+@torch.no_grad()
+def bspline_prefilter(img):
+    """the cubic B-spline coefficients of an image (B,C,D,H,W) (slices: (B,C,H,W)): per axis of N >= 2 samples the solution of
+    s[k] = (c[m(k-1)] + 4 c[k] + c[m(k+1)]) / 6 under the whole-sample mirror m - scipy.ndimage.spline_filter(order=3, mode="mirror").
+    What warp3d_cubic(df, coef=...) samples: prefilter once, warp many times.  No autograd (the image is data)."""
+    _cubic_image(img, "bspline_prefilter", "img")
+    if _is2d(img):
+        return bspline_prefilter(_lift(img)).squeeze(2)
+    _require_gpu(img)
+    img = planar(img.detach())
+    B, C, D, H, W = img.shape
+    coef = torch.empty_like(img)
+    t0 = _hbm_begin("bspline_prefilter")
+    lib.call("pulpo_bspline_prefilter", _ptr(img), _ptr(coef), B * C, D, H, W, _stream())
+    _hbm_end(t0, "bspline_prefilter", 8.0 * img.numel() * max(1, (D > 1) + (H > 1) + (W > 1)))       # every pass: one read, one write
+    return coef
+
+
+class _WarpCubic(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, df, coef):
+        _require_gpu(df, coef)
+        df, coef = planar(df), planar(coef)
+        B, _, Dg, Hg, Wg = df.shape
+        _, C, Di, Hi, Wi = coef.shape
+        out = torch.empty((B, C, Dg, Hg, Wg), device=df.device, dtype=torch.float32)
+        t0 = _hbm_begin("warp3d_cubic_fwd")
+        lib.call("pulpo_warp3d_cubic_fwd", _ptr(df), _ptr(coef), _ptr(out), B, C, Dg, Hg, Wg, Di, Hi, Wi, _stream())
+        _hbm_end(t0, "warp3d_cubic_fwd", 4.0 * (df.numel() + coef.numel() + out.numel()))     # (3 + 2C) V 4, as warp3d
+        ctx.save_for_backward(df, coef)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        df, coef = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        g = planar(g)
+        B, _, Dg, Hg, Wg = df.shape
+        _, C, Di, Hi, Wi = coef.shape
+        gdf = torch.empty_like(df)
+        t0 = _hbm_begin("warp3d_cubic_bwd")
+        lib.call("pulpo_warp3d_cubic_bwd", _ptr(df), _ptr(coef), _ptr(g), _ptr(gdf), B, C, Dg, Hg, Wg, Di, Hi, Wi, _stream())
+        _hbm_end(t0, "warp3d_cubic_bwd", 4.0 * (df.numel() + coef.numel() + g.numel()))       # (3 + 2C) V 4: gdf replaces out
+        return gdf, None
+
+
+def warp3d_cubic(df, img=None, *, coef=None):
+    """warp3d with the cubic B-spline interpolant of the image: the same sample coordinate (clamp included), 64 taps of the coefficients
+    instead of 8 corners of the samples; equals scipy.ndimage.map_coordinates(order=3, mode="mirror") at that coordinate.  Exactly one of
+    img and coef = bspline_prefilter(img) is given (bit-identical routes; coef lets a caller prefilter once).  df (B,3,Dg,Hg,Wg), image
+    (B,C,Di,Hi,Wi) of any size; slices: df (B,2,H,W), image (B,C,H,W).  Differentiable with respect to df only - a gather, deterministic;
+    an image that requires grad raises ValueError.  The result may leave the image's range by overshoot at edges: clamp it where a range
+    is assumed.  Not for label maps or masks (warp_labels, warp_mask)."""
+    if (img is None) == (coef is None):
+        raise ValueError("warp3d_cubic: exactly one of img and coef expected")
+    src, what = (img, "img") if coef is None else (coef, "coef")
+    _cubic_image(src, "warp3d_cubic", what)
+    if not isinstance(df, torch.Tensor) or df.dim() != src.dim() or df.shape[1] != df.dim() - 2 or df.shape[0] != src.shape[0]:
+        raise ValueError(f"warp3d_cubic: a field (B,3,D,H,W) ((B,2,H,W) for slices) with {what}'s batch expected, got "
+                         f"{tuple(df.shape) if isinstance(df, torch.Tensor) else type(df)} for {what} {tuple(src.shape)}")
+    if min(df.shape[-2:]) < 2 or (df.dim() == 5 and df.shape[2] < 2 and src.shape[2] != 1):
+        raise ValueError(f"warp3d_cubic: grid extents of at least 2 expected (a depth-1 grid goes with a depth-1 image), got {tuple(df.shape)}")
+    if _is2d(df):
+        return _WarpCubic.apply(_lift_field(df), _lift(bspline_prefilter(src) if coef is None else src)).squeeze(2)
+    return _WarpCubic.apply(df, bspline_prefilter(src) if coef is None else src)
+
+
 class _VecInt(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, nsteps: int):

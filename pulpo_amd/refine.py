@@ -10,6 +10,7 @@ Adam, one ops.anchored_adam_step launch per iteration over the whole arena (anch
 for the start; it is not in the loop.  No reference counterpart: the reference stops at what one forward pass predicts."""
 from __future__ import annotations
 
+import inspect
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -63,8 +64,10 @@ class Objective:
     terms).  obj(fields) -> (similarity, regulariser, combined_dfs, final_dfs); differentiable with respect to the fields only."""
 
     def __init__(self, model, x: torch.Tensor, y: torch.Tensor, recon_loss: Optional[Sequence[str]] = None, lamb: Optional[float] = None,
-                 gamma: Optional[float] = None, mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None) -> None:
+                 gamma: Optional[float] = None, mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None,
+                 interpolation: str = "linear") -> None:
         recon = _recon_list(model, recon_loss)                      # (before anything touches the device)
+        self.interpolation = ops.check_interpolation(interpolation, "refine")
         self.model, self.y = model, y
         self.gamma = float(model.hparams.gamma if gamma is None else gamma)
         self.lamb = float(model.hparams.lamb if lamb is None else lamb)
@@ -77,11 +80,22 @@ class Objective:
         self.decoders = model.autoencoder.decoders
         with torch.no_grad():
             self.level_x = model.autoencoder.level_images(x)
+            # cubic: the level images' B-spline coefficients, once; every iteration gathers from them
+            self.level_coef = None
+            if self.interpolation == "cubic":
+                coef = {}
+                for l, img in self.level_x.items():
+                    if id(img) not in coef:
+                        coef[id(img)] = ops.bspline_prefilter(img)
+                self.level_coef = {l: coef[id(img)] for l, img in self.level_x.items()}
         self.mask_x, self.mask_y = mask_x, mask_y
 
     def __call__(self, fields: Dict[int, torch.Tensor]):
         combined, final = self.model.combine_dfs(fields)
-        y_hat = {l: self.decoders[l].spatial_transform(final[l], self.level_x[l]) for l in final}
+        if self.level_coef is not None:
+            y_hat = {l: ops.warp3d_cubic(final[l], coef=self.level_coef[l]) for l in final}
+        else:
+            y_hat = {l: self.decoders[l].spatial_transform(final[l], self.level_x[l]) for l in final}
         masks = self.model.level_masks(final, self.mask_x, self.mask_y, force=True)     # (under no_grad: mask_x re-warped by the current fields)
         rec, _ = self.recon(y_hat, self.y, gamma=self.gamma, **({} if masks is None else {"masks": masks}))
         reg, _ = self.model.hierarchical_regularization(final, lamb=self.lamb)
@@ -136,6 +150,7 @@ def refine(model, x: torch.Tensor, y: torch.Tensor, *, individual_dfs: Optional[
                   anchor * kl_w[l] / (B (var + anchor_floor)) and applied inside the Adam kernel, not by autograd.  anchor = 0: no term.
     anchor_floor  voxels^2, keeps the precision finite where the samples agree.  Its default, 1e-4 (a standard deviation of 0.01 voxel), is
                   a guess: nobody has measured it.
+    The image model is trilinear; refine_interpolated (model.refine(..., interpolation="cubic")) descends on the cubic B-spline one.
     Nothing in the loop synchronises with the host, touches a model parameter's gradient, a BatchNorm statistic or a weight pack; it works
     under an outer torch.no_grad().  2-D models run through the same code, except that the "mind" term is 3-D only (ops.mind_loss
     raises NotImplementedError on slices).
@@ -144,7 +159,25 @@ def refine(model, x: torch.Tensor, y: torch.Tensor, *, individual_dfs: Optional[
     the way predict warps), history (device tensor (iters + 1, 4): total, similarity, regulariser, anchor; row i is the objective at the
     iterate before step i, the last row an extra forward pass at the result), anchor_mean / anchor_prec ({level: tensor}, None without an
     anchor)."""
-    objective = Objective(model, x, y, recon_loss, lamb, gamma, mask_x, mask_y)
+    return _run(model, x, y, "linear", individual_dfs, N, iters, lr, anchor, anchor_floor, recon_loss, lamb, gamma, mask_x, mask_y)
+
+
+def refine_interpolated(model, x: torch.Tensor, y: torch.Tensor, interpolation: str = "linear", **kw) -> Dict[str, object]:
+    """refine(model, x, y, **kw) with the image model named by `interpolation` (what model.refine calls).
+    "linear": refine itself, bit for bit.  "cubic": the level images are prefiltered once (ops.bspline_prefilter) and every iteration warps
+    their coefficients with ops.warp3d_cubic, whose gradient with respect to the field is continuous across voxel boundaries (the trilinear
+    one jumps there); the returned outputs are cubic too and may leave x's range by overshoot (the "mi" term clamps its inputs already).
+    Masks stay trilinear (warp_mask).  Anything else raises ValueError."""
+    ops.check_interpolation(interpolation, "refine")
+    if interpolation == "linear":
+        return refine(model, x, y, **kw)
+    bound = inspect.signature(refine).bind(model, x, y, **kw)
+    bound.apply_defaults()
+    return _run(model, x, y, interpolation, *list(bound.arguments.values())[3:])
+
+
+def _run(model, x, y, interpolation, individual_dfs, N, iters, lr, anchor, anchor_floor, recon_loss, lamb, gamma, mask_x, mask_y):
+    objective = Objective(model, x, y, recon_loss, lamb, gamma, mask_x, mask_y, interpolation)
     if iters < 0 or N < 1:
         raise ValueError("refine: iters >= 0 and N >= 1 expected")
     if anchor < 0 or anchor_floor <= 0:
@@ -193,7 +226,7 @@ def refine(model, x: torch.Tensor, y: torch.Tensor, *, individual_dfs: Optional[
         # own storage for what is handed out: the level fields, and the coarsest combined field, are views of the arena
         fields = {l: t.detach().clone() for l, t in fields.items()}
         combined = {l: (t.detach().clone() if l == L - 1 else t) for l, t in combined.items()}
-        outputs = {l: objective.decoders[l].spatial_transform(final[l], x) for l in final}
+        outputs = model._resample(interpolation, final, x)
     as_levels = lambda a: None if a is None else {l: t.clone() for l, t in _views(a, offsets, shapes).items()}
     return {"individual_dfs": fields, "combined_dfs": combined, "final_dfs": final, "outputs": outputs, "history": history,
             "anchor_mean": as_levels(mean), "anchor_prec": as_levels(prec)}
