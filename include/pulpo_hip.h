@@ -355,7 +355,7 @@ size_t pulpo_field_quality_ws_bytes(int B, int D, int H, int W);
 int pulpo_field_quality(const float* df, float* out /* 3 floats */, void* ws, int B, int D, int H, int W, int normalize, void* stream);
 
 /* ------------------------------------------------------------------------------------------ inverse fields (since ABI 6)
- * Inference only: no backward forms.  The level fields are stationary velocity fields, so the inverse of the flow VecInt(v) is VecInt(-v).
+ * Inference only: no backward forms (training: "paired VecInt for training" below).  The level fields are stationary velocity fields, so the inverse of the flow VecInt(v) is VecInt(-v).
  * pulpo_vecint_pair_fwd: VecInt.forward (src/network_blocks.py:160-177) on v and on -v in one call: fwd = VecInt(v), the result of
  *   pulpo_vecint_fwd (the same coordinate arithmetic and gather), inv = VecInt(-v).  v, fwd, inv planar (B,3,D,H,W); D == 1 is the 2-D form
  *   (channel 0 zero).  No intermediate field is kept: fields of up to 2048 voxels per batch element run every step in one launch out of
@@ -380,6 +380,26 @@ size_t pulpo_inverse_consistency_ws_bytes(int B, int D, int H, int W);
 int pulpo_inverse_consistency(const float* a, const float* b, float* out /* 2 floats */, void* ws, int B, int D, int H, int W, void* stream);
 int pulpo_transport_points(const float* pts /*(npts,nd)*/, const float* field /*(nsamp,nd,D,H,W)*/, float* out /*(nsamp,npts,nd)*/, int npts,
                            int nsamp, int nd, int D, int H, int W, int* flag, void* stream);
+
+/* ------------------------------------------------------------------------- paired VecInt for training (added within ABI 8: nothing else changed)
+ * Both directions of a stationary velocity field integrated with the fields a backward pass needs, and their joint gradient (DESIGN.md
+ * section 3u).  work: (nsteps+1, 2, B, 3, D, H, W) floats; work[k][0] is the field after k squarings of v / 2^nsteps, work[k][1] that of
+ * -v / 2^nsteps, each with the bits pulpo_vecint_fwd stores for v and for -v.  Fields of up to 2048 voxels per batch element: one launch
+ * of 2 B workgroups out of LDS; larger ones: one launch that writes both signs of v / 2^nsteps, then one launch per squaring step.
+ * pulpo_vecint_pair_bwd: gin = d loss / d v given gfwd = d loss / d work[nsteps][0] and ginv = d loss / d work[nsteps][1].  One of the two
+ *   may be NULL (= zero): that direction's chain is skipped, its fields in work and its share of tmp are not read.  With both, the last
+ *   squaring step (whose input gradients are two tensors) runs once per direction and every other step once for both; the last launch
+ *   writes gin = (g+ - g-) / 2^nsteps.  Kernels per step as pulpo_vecint_bwd chooses them.  tmp: pulpo_vecint_pair_bwd_tmp_floats() floats.
+ * pulpo_vecint_pair_bwd_det: ordered sums, the same bits on every call; each direction runs pulpo_vecint_bwd_det's chain with fixed-point
+ *   scales of its own, so with one gradient NULL the result has pulpo_vecint_bwd_det's bits for the other (negated for the inverse
+ *   direction).  ws: pulpo_vecint_pair_bwd_det_ws_bytes() bytes. */
+int pulpo_vecint_pair_fwd_work(const float* v, float* work, int B, int D, int H, int W, int nsteps, void* stream);
+size_t pulpo_vecint_pair_bwd_tmp_floats(int B, int D, int H, int W, int nsteps);
+int pulpo_vecint_pair_bwd(const float* work, const float* gfwd /*nullable*/, const float* ginv /*nullable*/, float* gin,
+                          float* tmp /*nullable if the query is 0*/, int B, int D, int H, int W, int nsteps, void* stream);
+size_t pulpo_vecint_pair_bwd_det_ws_bytes(int B, int D, int H, int W, int nsteps);
+int pulpo_vecint_pair_bwd_det(const float* work, const float* gfwd /*nullable*/, const float* ginv /*nullable*/, float* gin,
+                              void* ws /*nullable if the query is 0*/, int B, int D, int H, int W, int nsteps, void* stream);
 
 /* ------------------------------------------------------------------------- affine pre-alignment (added within ABI 8: nothing else changed)
  * No counterpart in the reference, whose pairs arrive affinely aligned; DESIGN.md section 3m holds the conventions.

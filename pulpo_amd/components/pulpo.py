@@ -139,12 +139,21 @@ class SVFDecoder(nn.Module):
         self.integrate = VecInt(insize, nsteps=7)
         self.spatial_transform = SpatialTransformer(outsize)
 
-    def forward(self, z: torch.Tensor, input_image: torch.Tensor, combined_df: Optional[torch.Tensor] = None):
+    def forward(self, z: torch.Tensor, input_image: torch.Tensor, combined_df: Optional[torch.Tensor] = None,
+                inverse_image: Optional[torch.Tensor] = None):
+        """inverse_image (not in the reference; bidirectional training): the fixed image on this level.  Given, the
+        combined velocity is integrated in both directions by one paired chain (ops.vecint_pair) and two items follow the five: the inverse
+        integral, resized like the forward one, and inverse_image warped by it."""
         individual_df = self.velocity_field(z)
         if combined_df is None:
             combined = individual_df
         else:
             combined = self.resizer_level(combined_df, add=individual_df)        # 2*up(combined_{l+1}) + individual, one kernel
+        if inverse_image is not None:
+            fwd, inv = ops.vecint_pair(combined, self.integrate.nsteps)
+            integrated, integrated_inv = self.resizer_output(fwd), self.resizer_output(inv)
+            warped = self.spatial_transform(integrated, input_image)
+            return individual_df, individual_df, combined, integrated, warped, integrated_inv, self.spatial_transform(integrated_inv, inverse_image)
         integrated = self.resizer_output(self.integrate(combined))
         warped = self.spatial_transform(integrated, input_image)
         # the reference hands back the individual field twice (pulpo.py:319)
@@ -238,11 +247,16 @@ class Autoencoder(nn.Module):
             level_x[0] = x
         return level_x
 
-    def forward(self, x: torch.Tensor, down_activations, deterministic: bool = False):
+    def forward(self, x: torch.Tensor, down_activations, deterministic: bool = False, y: Optional[torch.Tensor] = None):
+        """y (not in the reference; bidirectional training): the fixed image.  Given, every decoder integrates both directions and the tuple
+        gains final_dfs_inv and x_hat (y's level images under the inverse fields) at its end; only the eight forward items are fed back."""
         L, o = self.latent_levels, self.lk_offset
         level_x = self.level_images(x)
+        level_y = None if y is None else self.level_images(y)
 
         names = ("mus", "sigmas", "samples", "velocity_fields", "individual_dfs", "combined_dfs", "final_dfs", "transformed")
+        if y is not None:
+            names = names + ("final_dfs_inv", "x_hat")
         store: Dict[str, Dict[int, torch.Tensor]] = {n: {} for n in names}
         for l in reversed(range(L)):
             k = l + o
@@ -262,7 +276,10 @@ class Autoencoder(nn.Module):
                 mu, sigma, z = self.encoders[l](down_activations[k], feedback=self.up_blocks[k](fb, out=(tag[0], 0) if tag is not None else None))
                 coarser = store["combined_dfs"][l + 1]
             store["mus"][l], store["sigmas"][l], store["samples"][l] = mu, sigma, z
-            outs = self.decoders[l](mu if deterministic else z, level_x[l], combined_df=coarser)
+            if level_y is None:
+                outs = self.decoders[l](mu if deterministic else z, level_x[l], combined_df=coarser)
+            else:
+                outs = self.decoders[l](mu if deterministic else z, level_x[l], combined_df=coarser, inverse_image=level_y[l])
             for name, t in zip(names[3:], outs):
                 store[name][l] = t
         return tuple(store[n] for n in names)

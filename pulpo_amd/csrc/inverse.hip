@@ -1,4 +1,5 @@
-// Inverse deformation fields (inference only: no backward kernels).
+// Inverse deformation fields (inference only: no backward kernels; the paired integration that keeps its intermediate fields for a
+// backward pass, and that pass, sit beside the step kernels they reuse, in warp.hip: pulpo_vecint_pair_fwd_work / pulpo_vecint_pair_bwd).
 //   pulpo_vecint_pair_fwd       fwd = VecInt(v) and inv = VecInt(-v) in one call (network_blocks.py:160-177 run on v and on -v): the level
 //                               fields are stationary velocity fields, so the inverse of the flow is the integral of the negated velocity.
 //                               Coordinates are pulpo::sample_coord's, the step is pulpo::vecint_step_voxel: fwd is pulpo_vecint_fwd's result.

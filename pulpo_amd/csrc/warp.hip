@@ -602,3 +602,221 @@ PULPO_API int pulpo_vecint_bwd_det(const float* work, const float* gout, float* 
     }
     return pulpo::check_launch("vecint_bwd_det");
 }
+
+// ------------------------------------------------------------------------------------------------ paired VecInt for training
+// Both directions of a stationary velocity field, +v and -v, integrated and differentiated together.  work is (nsteps+1, 2, B, 3, D, H, W):
+// the direction is an outer batch index, so a squaring step of both directions is the step kernel of one direction run on 2 B batch
+// elements - the kernels above, unchanged, and so the bits of pulpo_vecint_fwd on v and on -v.
+namespace {
+
+// work[0][0] = v * scale, work[0][1] = -(v * scale) (scale = 2^-nsteps: both exact); inverse.hip's pair_scale_kernel for this layout
+__global__ __launch_bounds__(256) void vecint_pair_scale_kernel(const float* __restrict__ v, float* __restrict__ pos, float* __restrict__ neg, float scale, long n) {
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const float val = v[e] * scale;
+        pos[e] = val;
+        neg[e] = -val;
+    }
+}
+
+// vecint_fwd_lds_kernel for both directions: 2 B workgroups, workgroup blk integrates direction blk / B of batch element blk % B (the sign
+// enters with the scale) and stores every field at work[k][blk].
+__global__ __launch_bounds__(VI_THREADS) void vecint_pair_fwd_lds_kernel(const float* __restrict__ v, float* __restrict__ work, int B, int D, int H, int W,
+                                                                           int nsteps, float scale) {
+    extern __shared__ float fld[];                     // [3][V]
+    const int V = D * H * W, tid = threadIdx.x;
+    const long blk = blockIdx.x, b = blk % B, n = 2L * B * 3 * V;
+    const float sc = blk >= B ? -scale : scale;
+    for (int i = tid; i < 3 * V; i += VI_THREADS) {
+        const float val = v[b * 3 * V + i] * sc;
+        fld[i] = val;
+        work[blk * 3 * V + i] = val;
+    }
+    __syncthreads();
+    for (int k = 0; k < nsteps; ++k) {
+        float nv[8][3];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int vox = tid + j * VI_THREADS;
+            if (vox < V) pulpo::vecint_step_voxel(fld, V, vox, D, H, W, nv[j]);
+        }
+        __syncthreads();                               // every gather of this step is done: the field may be overwritten
+        float* out = work + (long)(k + 1) * n + blk * 3 * V;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int vox = tid + j * VI_THREADS;
+            if (vox < V) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    fld[c * V + vox] = nv[j][c];
+                    out[c * V + vox] = nv[j][c];
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// gin = (gp - gm) * scale: the two directions' gradients with respect to their scaled inputs +v / 2^nsteps and -v / 2^nsteps, folded into
+// the gradient with respect to v in one write.  Either may be null (that direction had no upstream gradient).
+__global__ __launch_bounds__(256) void vecint_pair_fold_kernel(const float* __restrict__ gp, const float* __restrict__ gm, float* __restrict__ gin, float scale,
+                                                                 long n) {
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const float d = gp == nullptr ? -gm[e] : (gm == nullptr ? gp[e] : gp[e] - gm[e]);
+        gin[e] = d * scale;
+    }
+}
+
+// one backward squaring step on nb batch elements, with pulpo_vecint_bwd's choice of kernel.  Tiled: gp is all zero on entry.
+int vecint_bwd_step(const float* cur, const float* g, float* gp, int nb, bool last, int D, int H, int W, hipStream_t st) {
+    if (vecint_bwd_tiled(D, H, W)) {
+        const int ntz = pulpo::cdiv(D, 4), nty = pulpo::cdiv(H, 8), ntx = pulpo::cdiv(W, 8);
+        const dim3 grid((unsigned)((long)nb * ntz * nty * ntx));
+        if (last && (long)D * H * W >= 64L * 64 * 64)
+            hipLaunchKernelGGL(vecint_bwd_tile_kernel<2>, grid, dim3(256), 0, st, cur, g, gp, nb, D, H, W, ntz, nty, ntx);
+        else
+            hipLaunchKernelGGL(vecint_bwd_tile_kernel<1>, grid, dim3(256), 0, st, cur, g, gp, nb, D, H, W, ntz, nty, ntx);
+    } else {
+        const long total = (long)nb * D * H * W;
+        hipError_t e = hipMemcpyAsync(gp, g, sizeof(float) * 3 * total, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return pulpo::fail((int)e, "vecint_pair_bwd copy: %s", hipGetErrorString(e));
+        hipLaunchKernelGGL(warp_bwd_kernel<true>, dim3(eblocks(total, 8192)), dim3(256), 0, st, cur, cur, g, gp, gp, nb, D, H, W, D, H, W, 3);
+    }
+    return pulpo::check_launch("vecint_pair_bwd step");
+}
+
+// pulpo_vecint_bwd_det's chain on one direction of a paired work buffer (cur_k = work + k * kstride): out = post * d loss / d work[0]
+int vecint_det_chain(const float* work, long kstride, const float* gout, float* out, void* ws, float post, int B, int D, int H, int W, int nsteps,
+                     hipStream_t st) {
+    const long n = (long)B * 3 * D * H * W, total = (long)B * D * H * W;
+    unsigned* slots = (unsigned*)ws;                       // slot k: largest |gradient| entering step k's scatter
+    long long* acc = (long long*)((char*)ws + 256);
+    float* buf[2] = {(float*)(acc + n), (float*)(acc + n) + n};
+    hipError_t e = hipMemsetAsync(ws, 0, 256 + sizeof(long long) * (size_t)n, st);
+    if (e != hipSuccess) return pulpo::fail((int)e, "vecint_pair_bwd_det memset: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(absmax_kernel, dim3(fx_blocks(n)), dim3(256), 0, st, gout, n, slots + (nsteps - 1));
+    const float* g = gout;
+    for (int k = nsteps - 1; k >= 0; --k) {
+        const float* cur = work + (long)k * kstride;
+        hipLaunchKernelGGL(warp_bwd_fx_kernel<true>, dim3(eblocks(total, 8192)), dim3(256), 0, st, cur, cur, g, (float*)nullptr, acc, slots + k, B, D, H, W, D, H, W, 3);
+        float* o = k == 0 ? out : buf[k & 1];
+        hipLaunchKernelGGL(fx_to_float_kernel, dim3(fx_blocks(n)), dim3(256), 0, st, acc, o, n, slots + k, k == 0 ? post : 1.0f, k == 0 ? (unsigned*)nullptr : slots + (k - 1));
+        g = o;
+    }
+    return pulpo::check_launch("vecint_pair_bwd_det");
+}
+
+}  // namespace
+
+// work: (nsteps+1, 2, B, 3, D, H, W); work[k][0] is the field after k squarings of v / 2^nsteps, work[k][1] that of -v / 2^nsteps.
+PULPO_API int pulpo_vecint_pair_fwd_work(const float* v, float* work, int B, int D, int H, int W, int nsteps, void* stream) {
+    PULPO_REQUIRE(v && work && B > 0 && D >= 1 && H > 1 && W > 1 && nsteps >= 0 && nsteps < 31 && (long)D * H * W < (1L << 31),
+                  "vecint_pair_fwd_work: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const long V = (long)D * H * W, n = (long)B * 3 * V;
+    const float scale = 1.0f / (float)(1 << nsteps);
+    if (V <= 2048 && nsteps > 0) {                     // pulpo_vecint_fwd's switch to the one-launch form
+        static bool attr_set = false;
+        if (!attr_set) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&vecint_pair_fwd_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)(sizeof(float) * 3 * VI_MAXV));
+            if (e != hipSuccess) return pulpo::fail((int)e, "hipFuncSetAttribute(vecint_pair_fwd_lds): %s", hipGetErrorString(e));
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(vecint_pair_fwd_lds_kernel, dim3(2 * B), dim3(VI_THREADS), sizeof(float) * 3 * (size_t)V, st, v, work, B, D, H, W, nsteps, scale);
+        return pulpo::check_launch("vecint_pair_fwd_lds");
+    }
+    hipLaunchKernelGGL(vecint_pair_scale_kernel, dim3(eblocks(n, 8192)), dim3(256), 0, st, v, work, work + n, scale, n);
+    int rc = pulpo::check_launch("vecint_pair_fwd_work scale");
+    if (rc) return rc;
+    for (int k = 0; k < nsteps; ++k) {
+        const float* cur = work + (long)k * 2 * n;
+        hipLaunchKernelGGL(warp_fwd_kernel<3>, dim3(eblocks(2 * B * V, 8192)), dim3(256), 0, st, cur, cur, cur, work + (long)(k + 1) * 2 * n, 2 * B, D, H, W, D, H, W, 3);
+        rc = pulpo::check_launch("vecint_pair_fwd_work step");
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// floats of scratch pulpo_vecint_pair_bwd needs: pulpo_vecint_bwd's buffers for both directions
+PULPO_API size_t pulpo_vecint_pair_bwd_tmp_floats(int B, int D, int H, int W, int nsteps) {
+    return B > 0 && B < (1 << 30) ? pulpo_vecint_bwd_tmp_floats(2 * B, D, H, W, nsteps) : 0;
+}
+
+// gin = d loss / d v given gfwd = d loss / d work[nsteps][0] and ginv = d loss / d work[nsteps][1]; one of the two may be NULL (zero): its
+// chain is skipped and neither its fields nor its share of tmp are touched.
+PULPO_API int pulpo_vecint_pair_bwd(const float* work, const float* gfwd, const float* ginv, float* gin, float* tmp, int B, int D, int H, int W,
+                                    int nsteps, void* stream) {
+    PULPO_REQUIRE(work && (gfwd || ginv) && gin && B > 0 && B < (1 << 30) && D >= 1 && H > 1 && W > 1 && nsteps >= 0 && nsteps < 31 &&
+                  (long)D * H * W < (1L << 31), "vecint_pair_bwd: bad arguments");
+    PULPO_REQUIRE(tmp || nsteps == 0, "vecint_pair_bwd: scratch of pulpo_vecint_pair_bwd_tmp_floats() floats required");
+    hipStream_t st = (hipStream_t)stream;
+    const long n = (long)B * 3 * D * H * W;                // one direction's field
+    const float scale = 1.0f / (float)(1 << nsteps);
+    const bool tiled = vecint_bwd_tiled(D, H, W), both = gfwd && ginv;
+    const float *gp = gfwd, *gm = ginv;                    // the gradients entering the fold
+    if (nsteps > 0) {
+        const int nb = both ? 2 * B : B;                   // batch elements of a joint step
+        const long fld = both ? 2 * n : n;                 // floats of a scratch buffer
+        const float* w0 = work + (ginv && !both ? n : 0);  // the first field the chain reads in every work[k]
+        if (tiled) {
+            hipError_t e = hipMemsetAsync(tmp, 0, sizeof(float) * fld * nsteps, st);
+            if (e != hipSuccess) return pulpo::fail((int)e, "vecint_pair_bwd fill: %s", hipGetErrorString(e));
+        }
+        auto buf = [&](int k) { return tmp + (tiled ? (long)k : (long)(k & 1)) * fld; };
+        int k = nsteps - 1, rc;
+        const float* g = gfwd ? gfwd : ginv;
+        if (both && tiled) {
+            // the upstream gradients are two tensors: the last squaring step runs once per direction; every other step is one launch
+            if ((rc = vecint_bwd_step(w0 + (long)k * 2 * n, gfwd, buf(k), B, true, D, H, W, st))) return rc;
+            if ((rc = vecint_bwd_step(w0 + (long)k * 2 * n + n, ginv, buf(k) + n, B, true, D, H, W, st))) return rc;
+            g = buf(k--);
+        } else if (both) {
+            // plain scatter (fields below 8 voxels on an axis): the step copies its input gradient anyway - gather the two into one buffer first
+            float* stage = buf(k + 1);
+            hipError_t e = hipMemcpyAsync(stage, gfwd, sizeof(float) * n, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(stage + n, ginv, sizeof(float) * n, hipMemcpyDeviceToDevice, st);
+            if (e != hipSuccess) return pulpo::fail((int)e, "vecint_pair_bwd gather: %s", hipGetErrorString(e));
+            g = stage;
+        }
+        for (; k >= 0; --k) {
+            if ((rc = vecint_bwd_step(w0 + (long)k * 2 * n, g, buf(k), nb, k == nsteps - 1, D, H, W, st))) return rc;
+            g = buf(k);
+        }
+        gp = gfwd ? g : nullptr;
+        gm = ginv ? (both ? g + n : g) : nullptr;
+    }
+    hipLaunchKernelGGL(vecint_pair_fold_kernel, dim3(eblocks(n, 8192)), dim3(256), 0, st, gp, gm, gin, scale, n);
+    return pulpo::check_launch("vecint_pair_bwd fold");
+}
+
+// Deterministic form: every direction runs pulpo_vecint_bwd_det's chain with fixed-point scale slots of its own (warp_bwd_fx_kernel takes one
+// scale per launch), so each direction's gradient has the bits pulpo_vecint_bwd_det gives it; with both present, the fold follows.
+// Layout: [pulpo_vecint_bwd_det's workspace for B][2 fields of floats].
+PULPO_API size_t pulpo_vecint_pair_bwd_det_ws_bytes(int B, int D, int H, int W, int nsteps) {
+    if (B <= 0 || D < 1 || H < 1 || W < 1 || nsteps <= 0) return 0;
+    return pulpo_vecint_bwd_det_ws_bytes(B, D, H, W, nsteps) + 2 * sizeof(float) * (size_t)B * 3 * D * H * W;
+}
+
+PULPO_API int pulpo_vecint_pair_bwd_det(const float* work, const float* gfwd, const float* ginv, float* gin, void* ws, int B, int D, int H, int W,
+                                        int nsteps, void* stream) {
+    PULPO_REQUIRE(work && (gfwd || ginv) && gin && B > 0 && D >= 1 && H > 1 && W > 1 && nsteps >= 0 && nsteps < 31 && (long)D * H * W < (1L << 31),
+                  "vecint_pair_bwd_det: bad arguments");
+    PULPO_REQUIRE(ws || nsteps == 0, "vecint_pair_bwd_det: workspace of pulpo_vecint_pair_bwd_det_ws_bytes() bytes required");
+    hipStream_t st = (hipStream_t)stream;
+    const long n = (long)B * 3 * D * H * W;
+    const float scale = 1.0f / (float)(1 << nsteps);
+    const float *gp = gfwd, *gm = ginv;
+    if (nsteps > 0) {
+        // one direction: its chain writes gin itself, the sign in the last conversion (exact)
+        if (!ginv) return vecint_det_chain(work, 2 * n, gfwd, gin, ws, scale, B, D, H, W, nsteps, st);
+        if (!gfwd) return vecint_det_chain(work + n, 2 * n, ginv, gin, ws, -scale, B, D, H, W, nsteps, st);
+        float* fin = (float*)((char*)ws + pulpo_vecint_bwd_det_ws_bytes(B, D, H, W, nsteps));
+        int rc;
+        if ((rc = vecint_det_chain(work, 2 * n, gfwd, fin, ws, 1.0f, B, D, H, W, nsteps, st))) return rc;
+        if ((rc = vecint_det_chain(work + n, 2 * n, ginv, fin + n, ws, 1.0f, B, D, H, W, nsteps, st))) return rc;
+        gp = fin;
+        gm = fin + n;
+    }
+    hipLaunchKernelGGL(vecint_pair_fold_kernel, dim3(eblocks(n, 8192)), dim3(256), 0, st, gp, gm, gin, scale, n);
+    return pulpo::check_launch("vecint_pair_bwd_det fold");
+}

@@ -24,6 +24,8 @@ from .uncertainty import _as_labels
 METRICS = ("RMSE", "JDetStd", "JDetLeq0", "Dice", "LM_MAE", "LM_Euclid")
 # the rows level_scores adds when it is given the inverse fields (no counterpart in the reference, which has no inverse transform)
 INVERSE_METRICS = ("InvCons", "InvConsMax", "LM_MAE_inv", "LM_Euclid_inv")
+# the rows level_scores adds when it is given the fixed image under the inverse fields: the scores of the inverse direction
+INVERSE_IMAGE_METRICS = ("RMSE_inv", "Dice_inv")
 # the rows level_scores adds when it is given cost-function masks
 MASK_METRICS = ("RMSE_masked", "MaskFrac")
 # the row level_scores adds with mind=True: the cross-contrast counterpart of RMSE, which means nothing between contrasts
@@ -46,7 +48,8 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
                  num_classes: Optional[int] = None, final_dfs_inv: Optional[Dict[int, torch.Tensor]] = None,
                  mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
                  mind_eps: float = 1e-5, surface: bool = False, include_background: bool = False,
-                 bending: bool = False, mi: bool = False, mi_bins: int = 32) -> Dict[str, Dict[int, torch.Tensor]]:
+                 bending: bool = False, mi: bool = False, mi_bins: int = 32, outputs_inv: Optional[Dict[int, torch.Tensor]] = None,
+                 inverse_fields: Optional[Dict[int, torch.Tensor]] = None, x: Optional[torch.Tensor] = None) -> Dict[str, Dict[int, torch.Tensor]]:
     """The level losses of evaluate.py:1433-1474 for one pair: {metric: {level: 0-d device tensor}}.
 
     outputs[l], final_dfs[l]: the warped image and the final field of level l (predict_deterministic + combine_dfs); y: the fixed image.
@@ -83,7 +86,11 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
                        = losses.Bending_reg(final_dfs[l], 1) / num_pixels_l; 0 for an affine field (every extent of a level at least 3).
     mi=True (no counterpart in the reference) adds, beside the rows above, which do not change,
       MI[l]            mean over the batch of the mutual information of outputs[l] and the target over mi_bins x mi_bins Parzen bins
-                       (ops.joint_histogram; images in [0,1]); higher is better."""
+                       (ops.joint_histogram; images in [0,1]); higher is better.
+    outputs_inv[l], inverse_fields[l] and x (the fixed image under the inverse field of level l, that field, and the moving image: what
+    bidirectional training compares; no counterpart in the reference) add, beside the rows above, which do not change,
+      RMSE_inv[l]      ops.rmse(outputs_inv[l], x resized to the level): RMSE's quantity for the inverse direction
+      Dice_inv[l]      with segmentations: the Dice row with the maps exchanged, ops.warp_labels_soft_dice(inverse_fields[l], seg_y, C, seg_x)."""
     levels = sorted(outputs.keys())
     if sorted(final_dfs.keys()) != levels:
         raise ValueError(f"level_scores: outputs has levels {levels}, final_dfs {sorted(final_dfs.keys())}")
@@ -152,6 +159,15 @@ def level_scores(outputs: Dict[int, torch.Tensor], final_dfs: Dict[int, torch.Te
             ref = lm_y.to(device=moved.device, dtype=moved.dtype)
             res["LM_MAE"][0] = eval_metrics.lm_mae(moved, ref)
             res["LM_Euclid"][0] = eval_metrics.lm_euclid(moved, ref)
+    if outputs_inv is not None:
+        if inverse_fields is None or x is None or sorted(outputs_inv.keys()) != levels or sorted(inverse_fields.keys()) != levels:
+            raise ValueError(f"level_scores: outputs_inv goes with inverse_fields and x, on the levels {levels}")
+        res["RMSE_inv"] = {}
+        for l in levels:
+            size = tuple(outputs_inv[l].shape[2:])
+            res["RMSE_inv"][l] = ops.rmse(outputs_inv[l], x if size == tuple(x.shape[2:]) else ops.resize_trilinear(x, size))
+        if seg_x is not None:
+            res["Dice_inv"] = {l: ops.warp_labels_soft_dice(inverse_fields[l], lab_y, C, lab_x)[1] for l in levels}
     if final_dfs_inv is not None:
         res["InvCons"], res["InvConsMax"] = {}, {}
         for l in levels:
@@ -174,7 +190,7 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
                 mask_y: Optional[torch.Tensor] = None, mind: bool = False, mind_dilation: int = 2,
                 mind_eps: float = 1e-5, refine: Optional[Dict[str, object]] = None, surface: bool = False,
                 include_background: bool = False, affine=None, bending: bool = False, mi: bool = False,
-                mi_bins: int = 32, interpolation: str = "linear") -> Dict[str, Dict[int, torch.Tensor]]:
+                mi_bins: int = 32, interpolation: str = "linear", inverse_image: bool = False) -> Dict[str, Dict[int, torch.Tensor]]:
     """evaluate.py:1423-1474 for one pair (x, y): model.predict_deterministic, model.combine_dfs, level_scores.  The model's mode is the
     caller's (evaluate.py:100 puts it in eval mode).  As in the reference, the deterministic prediction decodes mu at every level, but the
     feedback to the level above still carries `samples` (pulpo.py:202), a draw of the level's sampler: two calls differ in the last digits
@@ -195,13 +211,18 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
     are scored on cubic B-spline outputs (model.predict_deterministic / model.refine with interpolation="cubic"; a refinement then descends on
     the cubic image model too, unless its dict names an interpolation of its own).  With affine= the ORIGINAL x goes once through
     ops.warp3d_cubic under the composed field: one interpolation, as for the segmentations.  Segmentation, landmark and field rows do not
-    depend on it; masks and label maps stay on their own samplers.  Cubic outputs may leave x's range by overshoot (the MI row clamps)."""
+    depend on it; masks and label maps stay on their own samplers.  Cubic outputs may leave x's range by overshoot (the MI row clamps).
+    inverse_image=True adds the INVERSE_IMAGE_METRICS rows: y warped by the inverse fields
+    (model.combine_dfs_bidirectional) against x, and seg_y carried by them against seg_x - what a model trained with bidirectional=True is
+    trained on.  It does not add the INVERSE_METRICS rows (inverse=True does); with affine= it raises NotImplementedError like inverse=True."""
     ops.check_interpolation(interpolation, "performance")
     final_dfs_inv = None
     if surface and seg_x is None:
         raise ValueError("performance: surface=True needs seg_x and seg_y")
     theta = None
     if affine is not None:
+        if inverse_image:
+            raise NotImplementedError("performance: inverse_image=True together with affine= (the inverse of the composed transform) is not implemented")
         if inverse:
             raise NotImplementedError("performance: inverse=True together with affine= (the inverse of the composed transform) is not implemented")
         theta = affine_mod.fit(x, y, **affine)["theta"] if isinstance(affine, dict) else affine
@@ -209,12 +230,12 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
     if refine is not None:
         res = model.refine(x, y, **(refine if interpolation == "linear" else {"interpolation": interpolation, **refine}))
         outputs, individual_dfs, final_dfs = res["outputs"], res["individual_dfs"], res["final_dfs"]
-        if inverse:
+        if inverse or inverse_image:
             _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
     else:
         outputs, individual_dfs = model.predict_deterministic(x, y) if interpolation == "linear" else \
             model.predict_deterministic(x, y, interpolation=interpolation)
-        if inverse:
+        if inverse or inverse_image:
             _, final_dfs, final_dfs_inv = model.combine_dfs_bidirectional(individual_dfs)
         else:
             _, final_dfs = model.combine_dfs(individual_dfs)
@@ -223,9 +244,13 @@ def performance(model, x: torch.Tensor, y: torch.Tensor, *, seg_x: Optional[torc
         if interpolation == "cubic":                    # affine and deformable in one cubic resample of the original image
             coef = ops.bspline_prefilter(x_original)
             outputs = {l: ops.warp3d_cubic(df, coef=coef) for l, df in final_dfs.items()}
-    return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes, final_dfs_inv=final_dfs_inv,
+    inv_image = {}
+    if inverse_image:
+        inv_image = dict(outputs_inv=model._resample(interpolation, final_dfs_inv, y), inverse_fields=final_dfs_inv, x=x)
+    return level_scores(outputs, final_dfs, y, seg_x=seg_x, seg_y=seg_y, lm_x=lm_x, lm_y=lm_y, num_classes=num_classes,
+                        final_dfs_inv=final_dfs_inv if inverse else None,
                         mask_x=mask_x, mask_y=mask_y, mind=mind, mind_dilation=mind_dilation, mind_eps=mind_eps,
-                        surface=surface, include_background=include_background, bending=bending, mi=mi, mi_bins=mi_bins)
+                        surface=surface, include_background=include_background, bending=bending, mi=mi, mi_bins=mi_bins, **inv_image)
 
 
 @torch.no_grad()

@@ -165,6 +165,21 @@ def _weighted(weight_dict: Dict[int, float], terms: Dict[int, torch.Tensor], sca
     return total, all_levels
 
 
+def _weighted_pair(weight_dict: Dict[int, float], terms: Dict[int, torch.Tensor], terms_inv: Dict[int, torch.Tensor]):
+    """(1/2 sum_l w_l (term_l + term_inv_l), {l: w_l / 2 * (term_l + term_inv_l)}): the two directions of a bidirectional loss (DESIGN.md
+    section 3u).  Device scalars: all 2 L products and their sum in one ops.weighted_sum launch, a level's entry the sum of its two."""
+    levels = list(weight_dict.keys())
+    vals = [t[l] for l in levels for t in (terms, terms_inv)]
+    if all(isinstance(v, torch.Tensor) and v.is_cuda and v.numel() == 1 and v.dtype == torch.float32 for v in vals):
+        total, per = ops.weighted_sum(vals, [weight_dict[l] / 2 for l in levels for _ in range(2)])
+        return total, {l: per[2 * i] + per[2 * i + 1] for i, l in enumerate(levels)}
+    total, all_levels = 0.0, {}
+    for l in levels:
+        all_levels[l] = weight_dict[l] / 2 * terms[l] + weight_dict[l] / 2 * terms_inv[l]
+        total = total + all_levels[l]
+    return total, all_levels
+
+
 class HierarchicalKLLoss(nn.Module):
     """sum_l w_l * KL_l; also returns the per-level terms (losses.py:225-276)"""
 
@@ -203,38 +218,55 @@ class HierarchicalReconstructionLoss(nn.Module):
         self.ndims = ndims
         self.mode = "trilinear" if ndims == 3 else "bilinear"
 
+    def _level_term(self, l, w, fast, y_hat, y, y_hat_seg, seg_y, gamma, dice_factor, masks, dice_terms):
+        """one direction's term of level l: the bare similarity on the single-term fast path, else the w-weighted sum of the listed terms"""
+        size = y_hat[l].shape[2:]
+        # F.interpolate(y, size) of the reference; the identity resize at full resolution is skipped
+        y_target = y if tuple(size) == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
+        ma, mb = (masks.get(l) if masks is not None else None) or (None, None)
+        how = dict(win=self.window_size[l], gamma=gamma, dilation=self.mind_dilation, eps=self.mind_eps, bins=self.mi_bins)
+        if fast:
+            return ops.similarity(self.recon_loss[0], y_hat[l], y_target, ma, mb, **how)
+        term = 0.0
+        for kind in ("mse", "ncc", "mind", "mi"):
+            if kind in self.recon_loss:
+                term = term + w * ops.similarity(kind, y_hat[l], y_target, ma, mb, **how)
+        if "dice" in self.recon_loss and dice_terms is not None:
+            term = term + w * dice_terms[l]
+        elif "dice" in self.recon_loss:
+            seg_size = y_hat_seg[l].shape[2:]
+            seg_target = seg_y if tuple(seg_size) == tuple(seg_y.shape[2:]) else ops.resize_trilinear(seg_y, seg_size)
+            term = term + w * Soft_dice_loss(y_hat_seg[l], seg_target, dice_factor=dice_factor)
+        return term
+
     def forward(self, y_hat, y, y_hat_seg=None, seg_y=None, gamma: float = 0.05, dice_factor: int = 1,
                 masks: Optional[Dict[int, Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]] = None,
-                dice_terms: Optional[Dict[int, torch.Tensor]] = None):
+                dice_terms: Optional[Dict[int, torch.Tensor]] = None, inverse: Optional[dict] = None):
         """masks (not in the reference): {level: (mask_a, mask_b)}, weight volumes at the level's size, either of a pair may be None; a level
         with a pair uses the masked NCC / MSE / MIND / MI term (cost weighted by mask_a * mask_b), the Dice term is unchanged.
         dice_terms (not in the reference): {level: the level's Dice term}, computed by the caller (PULPo.label_dice_terms, from label maps);
-        dice_terms[l] stands in for Soft_dice_loss(y_hat_seg[l], ...), and y_hat_seg / seg_y are not read"""
+        dice_terms[l] stands in for Soft_dice_loss(y_hat_seg[l], ...), and y_hat_seg / seg_y are not read.
+        inverse (not in the reference; bidirectional training): the same arguments for the inverse direction, a dict
+        with "y_hat" and "y" (the fixed image under the inverse fields, and the moving image it is compared with) and optionally
+        "y_hat_seg", "seg_y", "masks", "dice_terms".  The result is then half the sum of the two directions, level by level."""
         single = len(self.recon_loss) == 1 and self.recon_loss[0] in ("mse", "ncc", "dice", "mind", "mi")
+        fast = single and self.recon_loss[0] != "dice"      # one term per level (the default, ["ncc"]): weighting and summation of all levels in one launch; x / 1 is x
         loss = 0.0
-        all_levels, terms = {}, {}
+        all_levels, terms, terms_inv = {}, {}, {}
         for l, w in self.weight_dict.items():
-            size = y_hat[l].shape[2:]
-            # F.interpolate(y, size) of the reference; the identity resize at full resolution is skipped
-            y_target = y if tuple(size) == tuple(y.shape[2:]) else ops.resize_trilinear(y, size)
-            ma, mb = (masks.get(l) if masks is not None else None) or (None, None)
-            how = dict(win=self.window_size[l], gamma=gamma, dilation=self.mind_dilation, eps=self.mind_eps, bins=self.mi_bins)
-            if single and self.recon_loss[0] != "dice":
-                # one term per level (the default, ["ncc"]): weighting and summation of all levels in one launch; x / 1 is x
-                terms[l] = ops.similarity(self.recon_loss[0], y_hat[l], y_target, ma, mb, **how)
+            term = self._level_term(l, w, fast, y_hat, y, y_hat_seg, seg_y, gamma, dice_factor, masks, dice_terms)
+            if inverse is not None:
+                term_inv = self._level_term(l, w, fast, inverse["y_hat"], inverse["y"], inverse.get("y_hat_seg"), inverse.get("seg_y"), gamma,
+                                            dice_factor, inverse.get("masks"), inverse.get("dice_terms"))
+            if fast:
+                terms[l] = term
+                if inverse is not None:
+                    terms_inv[l] = term_inv
                 continue
-            term = 0.0
-            for kind in ("mse", "ncc", "mind", "mi"):
-                if kind in self.recon_loss:
-                    term = term + w * ops.similarity(kind, y_hat[l], y_target, ma, mb, **how)
-            if "dice" in self.recon_loss and dice_terms is not None:
-                term = term + w * dice_terms[l]
-            elif "dice" in self.recon_loss:
-                seg_size = y_hat_seg[l].shape[2:]
-                seg_target = seg_y if tuple(seg_size) == tuple(seg_y.shape[2:]) else ops.resize_trilinear(seg_y, seg_size)
-                term = term + w * Soft_dice_loss(y_hat_seg[l], seg_target, dice_factor=dice_factor)
-            all_levels[l] = term / len(self.recon_loss)
+            all_levels[l] = term / len(self.recon_loss) if inverse is None else (term + term_inv) / (2 * len(self.recon_loss))
             loss = loss + all_levels[l]
+        if terms_inv:
+            return _weighted_pair(self.weight_dict, terms, terms_inv)
         if terms:
             return _weighted(self.weight_dict, terms)
         return loss, all_levels
@@ -248,6 +280,11 @@ class HierarchicalRegularization(nn.Module):
         self.regularizer = regularizer
         self.weight_dict = _apply_pyramid(weight_dict, similarity_pyramid)
 
-    def forward(self, dfs: Dict[int, torch.Tensor], lamb: float = 0):
+    def forward(self, dfs: Dict[int, torch.Tensor], lamb: float = 0, dfs_inv: Optional[Dict[int, torch.Tensor]] = None):
+        """dfs_inv (not in the reference; bidirectional training): the inverse fields; given, the result is half the sum over both"""
         assert self.weight_dict.keys() == dfs.keys()
+        if dfs_inv is not None:
+            assert dfs_inv.keys() == dfs.keys()
+            return _weighted_pair(self.weight_dict, {l: self.regularizer(dfs[l], lamb) for l in self.weight_dict},
+                                  {l: self.regularizer(dfs_inv[l], lamb) for l in self.weight_dict})
         return _weighted(self.weight_dict, {l: self.regularizer(dfs[l], lamb) for l in self.weight_dict})

@@ -55,6 +55,7 @@ class PULPo(ABC, LightningModule):
         nondiagonal: bool = False,
         cp_depth: int = 3,
         num_classes: Optional[int] = None,
+        bidirectional: bool = False,
         mind_dilation: int = 2,
         mind_eps: float = 1e-5,
     ) -> None:
@@ -62,6 +63,9 @@ class PULPo(ABC, LightningModule):
         self.validation_counter = 0
         self.save_hyperparameters()
         self.segs, self.lms, self.mask = segs, lms, mask
+        # train the velocity fields from both sides: x under the flow against y AND y under the inverse flow against x,
+        # both fields regularised.  No parameter depends on it: a checkpoint trained one way loads the other way.
+        self.bidirectional = bool(bidirectional)
         self.latent_levels = latent_levels
         self.total_levels = total_levels
         self.lk_offset = total_levels - latent_levels
@@ -154,10 +158,27 @@ class PULPo(ABC, LightningModule):
             pairs[l] = (wx, wy)
         return pairs
 
+    def _inverse_terms(self, x, final_dfs_inv, x_hat, seg_x, seg_y, mask_x, mask_y) -> dict:
+        """the `inverse` argument of HierarchicalReconstructionLoss: what _forward_and_losses prepares for y_hat against y, with the roles of
+        the two images, segmentations and masks exchanged and the inverse fields in place of the forward ones"""
+        inverse = {"y_hat": x_hat, "y": x}
+        if "dice" in self.hparams.recon_loss and self._label_maps(seg_x, seg_y):
+            inverse["dice_terms"] = self.label_dice_terms(final_dfs_inv, seg_y, seg_x)
+        elif "dice" in self.hparams.recon_loss:
+            inverse["y_hat_seg"], inverse["seg_y"] = self.transform_segmentation(final_dfs_inv, seg_y), seg_x
+        masks = self.level_masks(final_dfs_inv, mask_y, mask_x)
+        if masks is not None:
+            inverse["masks"] = masks
+        return inverse
+
     def _forward_and_losses(self, x, y, seg_x=None, seg_y=None, mask_x=None, mask_y=None):
         acts = self.downpath(x, y, _needed=self._needed_levels)
-        outs = self.autoencoder(x, acts)
-        mus, sigmas, samples, velocity_fields, individual_dfs, combined_dfs, final_dfs, y_hat = outs
+        if self.bidirectional:
+            outs = self.autoencoder(x, acts, y=y)
+            final_dfs_inv, x_hat = outs[8:]
+        else:
+            outs = self.autoencoder(x, acts)
+        mus, sigmas, samples, velocity_fields, individual_dfs, combined_dfs, final_dfs, y_hat = outs[:8]
         prior_mus, prior_sigmas = self.prior(mus, sigmas)
         dice_terms = None
         if "dice" in self.hparams.recon_loss and self._label_maps(seg_x, seg_y):
@@ -171,8 +192,10 @@ class PULPo(ABC, LightningModule):
         masks = self.level_masks(final_dfs, mask_x, mask_y)
         rec, rec_levels = self.hierarchical_recon_loss(y_hat, y, y_hat_seg, seg_y, gamma=self.hparams.gamma, dice_factor=self.hparams.dice_factor,
                                                        **({} if masks is None else {"masks": masks}),
-                                                       **({} if dice_terms is None else {"dice_terms": dice_terms}))
-        reg, reg_levels = self.hierarchical_regularization(final_dfs, lamb=self.hparams.lamb)
+                                                       **({} if dice_terms is None else {"dice_terms": dice_terms}),
+                                                       **({"inverse": self._inverse_terms(x, final_dfs_inv, x_hat, seg_x, seg_y, mask_x, mask_y)}
+                                                          if self.bidirectional else {}))
+        reg, reg_levels = self.hierarchical_regularization(final_dfs, lamb=self.hparams.lamb, **({"dfs_inv": final_dfs_inv} if self.bidirectional else {}))
         total = kl + rec + reg
         return outs, (prior_mus, prior_sigmas), (total, kl, rec, reg), (kl_levels, rec_levels, reg_levels)
 
@@ -320,11 +343,12 @@ class PULPo(ABC, LightningModule):
         outputs_inv = self._resample(interpolation, final_inv, y)
         return {"outputs": outputs, "individual_dfs": individual_dfs, "final_dfs": final, "final_dfs_inv": final_inv, "outputs_inv": outputs_inv}
 
-    def refine(self, x: torch.Tensor, y: torch.Tensor, interpolation: str = "linear", **kw):
+    def refine(self, x: torch.Tensor, y: torch.Tensor, interpolation: str = "linear", bidirectional: Optional[bool] = None, **kw):
         """instance-specific optimisation of this pair's level fields from the model's prediction: pulpo_amd.refine.refine(self, x, y, **kw);
-        interpolation="cubic" descends on, and hands back, the cubic B-spline image model (pulpo_amd.refine.refine_interpolated)"""
+        interpolation="cubic" descends on, and hands back, the cubic B-spline image model (pulpo_amd.refine.refine_interpolated);
+        bidirectional (None: this model's flag) descends on the two-sided objective of bidirectional training"""
         from .refine import refine_interpolated
-        return refine_interpolated(self, x, y, interpolation, **kw)
+        return refine_interpolated(self, x, y, interpolation, bidirectional, **kw)
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:  # type: ignore[override]
         return self.autoencoder(x, self.downpath(x, y, _needed=self._needed_levels))[7][0]
@@ -356,7 +380,7 @@ class PULPo(ABC, LightningModule):
     def combine_dfs_bidirectional(self, individual_dfs: Dict[int, torch.Tensor]):
         """combine_dfs with the inverse transform: (combined, final, final_inv).  The level fields are stationary velocity fields, so the
         inverse of the flow is the integral of -combined[l]: final_inv[l] is that integral, resized like final[l].  Both integrals come from
-        one ops.vecint_pair call per level (under no_grad: no intermediate fields kept; with gradients: two vecint calls)."""
+        one ops.vecint_pair call per level (under no_grad: no intermediate fields kept; with gradients: the paired autograd node)."""
         combined = self._combine_levels(individual_dfs)
         final, final_inv = {}, {}
         for l in reversed(range(self.latent_levels)):

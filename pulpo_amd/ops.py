@@ -2033,13 +2033,64 @@ def vecint(v, nsteps: int = 7):
     return _VecInt.apply(v, int(nsteps))
 
 
+class _VecIntPair(torch.autograd.Function):
+    """(VecInt(v), VecInt(-v)) as one node: pulpo_vecint_pair_fwd_work keeps the nsteps + 1 fields of both directions in one buffer, whose
+    last pair is the result; the backward pass is one pulpo_vecint_pair_bwd call that takes whichever upstream gradients exist.  The buffer
+    hangs on the node itself, not among its saved tensors: the two results are often differentiated in separate passes (one direction's
+    loss, then the other's), and a pass releases the saved tensors of the nodes it visits."""
+
+    @staticmethod
+    def forward(ctx, v, nsteps: int):
+        _require_gpu(v)
+        v = planar(v)
+        B, _, D, H, W = v.shape
+        work = torch.empty((nsteps + 1, 2, B, 3, D, H, W), device=v.device, dtype=torch.float32)
+        t0 = _hbm_begin("vecint_pair_fwd_work")
+        lib.call("pulpo_vecint_pair_fwd_work", _ptr(v), _ptr(work), B, D, H, W, nsteps, _stream())
+        _hbm_end(t0, "vecint_pair_fwd_work", 4.0 * v.numel() * (4 * nsteps + 3))             # v once, both signs out; every step: both fields in and out
+        ctx.work = work
+        ctx.nsteps = nsteps
+        ctx.set_materialize_grads(False)
+        return work[nsteps, 0], work[nsteps, 1]
+
+    @staticmethod
+    def backward(ctx, gf, gi):
+        work = ctx.work
+        _, _, B, _, D, H, W = work.shape
+        if gf is None and gi is None:
+            return None, None
+        gf = planar(gf) if gf is not None else None
+        gi = planar(gi) if gi is not None else None
+        gin = torch.empty((B, 3, D, H, W), device=work.device, dtype=torch.float32)
+        t0 = _hbm_begin("vecint_pair_bwd")
+        if DETERMINISTIC:
+            nws = lib.query("pulpo_vecint_pair_bwd_det_ws_bytes", B, D, H, W, ctx.nsteps)
+            ws = torch.empty(nws, device=work.device, dtype=torch.uint8) if nws else None
+            lib.call("pulpo_vecint_pair_bwd_det", _ptr(work), _ptr(gf), _ptr(gi), _ptr(gin), _ptr(ws), B, D, H, W, ctx.nsteps, _stream())
+        else:
+            ntmp = lib.query("pulpo_vecint_pair_bwd_tmp_floats", B, D, H, W, ctx.nsteps)
+            if gf is None or gi is None:
+                ntmp //= 2                                                                   # one direction's chain: half the buffers
+            tmp = torch.empty(ntmp, device=work.device, dtype=torch.float32) if ntmp else None
+            lib.call("pulpo_vecint_pair_bwd", _ptr(work), _ptr(gf), _ptr(gi), _ptr(gin), _ptr(tmp), B, D, H, W, ctx.nsteps, _stream())
+        ndir = (gf is not None) + (gi is not None)
+        _hbm_end(t0, "vecint_pair_bwd", 4.0 * gin.numel() * (3 * ctx.nsteps * ndir + ndir + 1))
+        return gin, None
+
+
 def vecint_pair(v, nsteps: int = 7):
     """(VecInt(v), VecInt(-v)): the integrated field and its inverse (a stationary velocity field's flow is inverted by integrating -v;
     network_blocks.py:160-177).  Under torch.no_grad(), or when v does not require grad, one pulpo_vecint_pair_fwd call that keeps no
     intermediate field (two results + two scratch fields; none of the nsteps + 1 fields per direction that vecint saves for its backward
-    pass).  Otherwise (vecint(v), vecint(-v)), so that a bidirectional loss backpropagates through the existing backward kernels."""
+    pass).  Otherwise one autograd node over the paired kernel chains: both directions advance in the same launches,
+    2 (nsteps + 1) fields are kept, and the backward pass writes the gradient of both directions' losses in one call."""
     if torch.is_grad_enabled() and v.requires_grad:
-        return vecint(v, nsteps), vecint(-v, nsteps)
+        if _is2d(v):
+            fwd, inv = vecint_pair(_lift_field(v), nsteps)
+            return _unlift_field(fwd), _unlift_field(inv)
+        if v.dim() != 5 or v.shape[1] != 3:
+            raise PulpoHipError(f"vecint_pair: velocity field (B,3,D,H,W) or (B,2,H,W) expected, got {tuple(v.shape)}")
+        return _VecIntPair.apply(v, int(nsteps))
     if _is2d(v):
         fwd, inv = vecint_pair(_lift_field(v), nsteps)
         return _unlift_field(fwd), _unlift_field(inv)

@@ -61,14 +61,18 @@ def _recon_list(model, recon_loss) -> List[str]:
 
 class Objective:
     """similarity + regulariser of one pair as a function of its level velocity fields - what refine() descends on (its docstring has the
-    terms).  obj(fields) -> (similarity, regulariser, combined_dfs, final_dfs); differentiable with respect to the fields only."""
+    terms).  obj(fields) -> (similarity, regulariser, combined_dfs, final_dfs); differentiable with respect to the fields only.
+    bidirectional (None: the model's flag): the step's two-sided objective - half the sum of both directions'
+    similarity and regulariser, the inverse direction being y's level images under the inverse fields against x, with the masks exchanged.
+    obj.terms(fields) returns everything by name: rec, reg, combined, final, y_hat and, bidirectional, final_inv and x_hat."""
 
     def __init__(self, model, x: torch.Tensor, y: torch.Tensor, recon_loss: Optional[Sequence[str]] = None, lamb: Optional[float] = None,
                  gamma: Optional[float] = None, mask_x: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None,
-                 interpolation: str = "linear") -> None:
+                 interpolation: str = "linear", bidirectional: Optional[bool] = None) -> None:
         recon = _recon_list(model, recon_loss)                      # (before anything touches the device)
         self.interpolation = ops.check_interpolation(interpolation, "refine")
-        self.model, self.y = model, y
+        self.model, self.x, self.y = model, x, y
+        self.bidirectional = bool(getattr(model, "bidirectional", False) if bidirectional is None else bidirectional)
         self.gamma = float(model.hparams.gamma if gamma is None else gamma)
         self.lamb = float(model.hparams.lamb if lamb is None else lamb)
         ref = model.hierarchical_recon_loss
@@ -79,27 +83,50 @@ class Objective:
             self.recon.mi_bins = ref.mi_bins          # (an attribute, not a constructor argument: the bins of the model's "mi" term)
         self.decoders = model.autoencoder.decoders
         with torch.no_grad():
-            self.level_x = model.autoencoder.level_images(x)
-            # cubic: the level images' B-spline coefficients, once; every iteration gathers from them
-            self.level_coef = None
-            if self.interpolation == "cubic":
-                coef = {}
-                for l, img in self.level_x.items():
-                    if id(img) not in coef:
-                        coef[id(img)] = ops.bspline_prefilter(img)
-                self.level_coef = {l: coef[id(img)] for l, img in self.level_x.items()}
+            self.level_x, self.level_coef = self._level_images(x)
+            self.level_y, self.level_coef_y = self._level_images(y) if self.bidirectional else (None, None)
         self.mask_x, self.mask_y = mask_x, mask_y
 
-    def __call__(self, fields: Dict[int, torch.Tensor]):
-        combined, final = self.model.combine_dfs(fields)
-        if self.level_coef is not None:
-            y_hat = {l: ops.warp3d_cubic(final[l], coef=self.level_coef[l]) for l in final}
+    def _level_images(self, img):
+        """(the image on every level, its B-spline coefficients there or None)"""
+        level = self.model.autoencoder.level_images(img)
+        # cubic: the level images' B-spline coefficients, once; every iteration gathers from them (DESIGN.md section 3t)
+        if self.interpolation != "cubic":
+            return level, None
+        coef = {}
+        for l, t in level.items():
+            if id(t) not in coef:
+                coef[id(t)] = ops.bspline_prefilter(t)
+        return level, {l: coef[id(t)] for l, t in level.items()}
+
+    def _warp(self, final, level_img, level_coef):
+        if level_coef is not None:
+            return {l: ops.warp3d_cubic(final[l], coef=level_coef[l]) for l in final}
+        return {l: self.decoders[l].spatial_transform(final[l], level_img[l]) for l in final}
+
+    def terms(self, fields: Dict[int, torch.Tensor]) -> Dict[str, object]:
+        if not self.bidirectional:
+            combined, final = self.model.combine_dfs(fields)
         else:
-            y_hat = {l: self.decoders[l].spatial_transform(final[l], self.level_x[l]) for l in final}
+            combined, final, final_inv = self.model.combine_dfs_bidirectional(fields)
+        y_hat = self._warp(final, self.level_x, self.level_coef)
         masks = self.model.level_masks(final, self.mask_x, self.mask_y, force=True)     # (under no_grad: mask_x re-warped by the current fields)
-        rec, _ = self.recon(y_hat, self.y, gamma=self.gamma, **({} if masks is None else {"masks": masks}))
-        reg, _ = self.model.hierarchical_regularization(final, lamb=self.lamb)
-        return rec, reg, combined, final
+        extra, out = {}, {"combined": combined, "final": final, "y_hat": y_hat}
+        if self.bidirectional:
+            x_hat = self._warp(final_inv, self.level_y, self.level_coef_y)
+            inverse = {"y_hat": x_hat, "y": self.x}
+            masks_inv = self.model.level_masks(final_inv, self.mask_y, self.mask_x, force=True)
+            if masks_inv is not None:
+                inverse["masks"] = masks_inv
+            extra = {"inverse": inverse}
+            out.update(final_inv=final_inv, x_hat=x_hat)
+        out["rec"], _ = self.recon(y_hat, self.y, gamma=self.gamma, **({} if masks is None else {"masks": masks}), **extra)
+        out["reg"], _ = self.model.hierarchical_regularization(final, lamb=self.lamb, **({"dfs_inv": final_inv} if self.bidirectional else {}))
+        return out
+
+    def __call__(self, fields: Dict[int, torch.Tensor]):
+        t = self.terms(fields)
+        return t["rec"], t["reg"], t["combined"], t["final"]
 
 
 @torch.no_grad()
@@ -144,6 +171,9 @@ def refine(model, x: torch.Tensor, y: torch.Tensor, *, individual_dfs: Optional[
     regulariser   model.hierarchical_regularization(final, lamb) (None: the model's lamb): the model's own regulariser - a model built with
                   regularizer="bending" is refined against the bending energy, which leaves a residual affine
                   stretch of the field free where L2 pulls it back to the identity.
+                  A model built with bidirectional=True is refined against the two-sided objective of its training step (Objective;
+                  DESIGN.md section 3u) through model.combine_dfs_bidirectional, and the result gains final_dfs_inv and outputs_inv (y
+                  warped by final_dfs_inv[l]); refine_interpolated (model.refine(..., bidirectional=)) overrides the model's flag.
     anchor        the KL divergence between two Gaussians of equal covariance, N(v, var) against the posterior N(mean, var), weighted by
                   level like the training step's KL term (kl_w, divided by B: kl_diag's normalisation): the fields move freely where the
                   model is uncertain and stay close elsewhere.  Folded once into a per-element precision
@@ -162,22 +192,24 @@ def refine(model, x: torch.Tensor, y: torch.Tensor, *, individual_dfs: Optional[
     return _run(model, x, y, "linear", individual_dfs, N, iters, lr, anchor, anchor_floor, recon_loss, lamb, gamma, mask_x, mask_y)
 
 
-def refine_interpolated(model, x: torch.Tensor, y: torch.Tensor, interpolation: str = "linear", **kw) -> Dict[str, object]:
+def refine_interpolated(model, x: torch.Tensor, y: torch.Tensor, interpolation: str = "linear", bidirectional: Optional[bool] = None,
+                        **kw) -> Dict[str, object]:
     """refine(model, x, y, **kw) with the image model named by `interpolation` (what model.refine calls).
     "linear": refine itself, bit for bit.  "cubic": the level images are prefiltered once (ops.bspline_prefilter) and every iteration warps
     their coefficients with ops.warp3d_cubic, whose gradient with respect to the field is continuous across voxel boundaries (the trilinear
     one jumps there); the returned outputs are cubic too and may leave x's range by overshoot (the "mi" term clamps its inputs already).
-    Masks stay trilinear (warp_mask).  Anything else raises ValueError."""
+    Masks stay trilinear (warp_mask).  Anything else raises ValueError.
+    bidirectional: None - the model's flag, as refine; True / False - the two-sided objective (refine's docstring) whatever the model's."""
     ops.check_interpolation(interpolation, "refine")
-    if interpolation == "linear":
+    if interpolation == "linear" and bidirectional is None:
         return refine(model, x, y, **kw)
     bound = inspect.signature(refine).bind(model, x, y, **kw)
     bound.apply_defaults()
-    return _run(model, x, y, interpolation, *list(bound.arguments.values())[3:])
+    return _run(model, x, y, interpolation, *list(bound.arguments.values())[3:], bidirectional=bidirectional)
 
 
-def _run(model, x, y, interpolation, individual_dfs, N, iters, lr, anchor, anchor_floor, recon_loss, lamb, gamma, mask_x, mask_y):
-    objective = Objective(model, x, y, recon_loss, lamb, gamma, mask_x, mask_y, interpolation)
+def _run(model, x, y, interpolation, individual_dfs, N, iters, lr, anchor, anchor_floor, recon_loss, lamb, gamma, mask_x, mask_y, bidirectional=None):
+    objective = Objective(model, x, y, recon_loss, lamb, gamma, mask_x, mask_y, interpolation, bidirectional)
     if iters < 0 or N < 1:
         raise ValueError("refine: iters >= 0 and N >= 1 expected")
     if anchor < 0 or anchor_floor <= 0:
@@ -217,7 +249,8 @@ def _run(model, x, y, interpolation, individual_dfs, N, iters, lr, anchor, ancho
         history[i, 1:] = torch.stack((rec.detach().reshape(()), reg.detach().reshape(()), anchor_val[0]))
     with torch.no_grad():
         fields = _views(arena, offsets, shapes)
-        rec, reg, combined, final = objective(fields)
+        last = objective.terms(fields)
+        rec, reg, combined, final = last["rec"], last["reg"], last["combined"], last["final"]
         if mean is not None:
             d = arena.detach() - mean
             anchor_val[0] = 0.5 * torch.sum(prec * d * d)               # (once, at the result; in the loop the kernel reduces it)
@@ -228,5 +261,9 @@ def _run(model, x, y, interpolation, individual_dfs, N, iters, lr, anchor, ancho
         combined = {l: (t.detach().clone() if l == L - 1 else t) for l, t in combined.items()}
         outputs = model._resample(interpolation, final, x)
     as_levels = lambda a: None if a is None else {l: t.clone() for l, t in _views(a, offsets, shapes).items()}
-    return {"individual_dfs": fields, "combined_dfs": combined, "final_dfs": final, "outputs": outputs, "history": history,
-            "anchor_mean": as_levels(mean), "anchor_prec": as_levels(prec)}
+    res = {"individual_dfs": fields, "combined_dfs": combined, "final_dfs": final, "outputs": outputs, "history": history,
+           "anchor_mean": as_levels(mean), "anchor_prec": as_levels(prec)}
+    if objective.bidirectional:
+        with torch.no_grad():
+            res["final_dfs_inv"], res["outputs_inv"] = last["final_inv"], model._resample(interpolation, last["final_inv"], y)
+    return res
